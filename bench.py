@@ -6,7 +6,7 @@ record per ray, outputs resident in HBM) over one synthetic nuScenes-shaped swee
 (32 768 rays), configuration C2 of BASELINE.json: (64, 64, 128) samples per ray, 8x256 view MLP, semantic + intensity
 heads, full-size hash tables (229 MiB NerfMLP table, fp32).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 N > 1 (BASELINE config C4): the ONE 32 x 1024 sweep is split into N azimuth sectors, GPU p renders sector p and one
 all-gather (RCCL over xGMI, issued on a side stream under the next sweep's first kernels) puts the packed [1024, 32, 7]
@@ -15,9 +15,17 @@ range image on every rank: "scaling": "strong" (total work fixed).  `--scaling w
 processes (`python -m torch.distributed.run`, rendezvous on 127.0.0.1) BEFORE anything in this process touches the GPU,
 and forwards their exit code; under `torch.distributed.run` it is a rank.
 
-Prints ONE JSON line on rank 0; carries `roofline` for the dominant kernel (nlr_mlp_kernel, timed with HIP events on its
-launch stream inside the timed region), `cpu_baseline` (the CPU oracle on a bounded sample) and `accuracy` (the timed
-precision against the oracle on that same sample).
+Prints ONE JSON line on rank 0.  A plain run does only what the headline figure needs: set up, warm up, time the K steps
+(no HIP events inside them), write the outputs if asked, print `metric`, `value`, `unit`, `ms_per_step`, `dtype` and the
+configuration.  `--full` adds everything else, as the default run did before the option existed: `kernel_ms` and
+`roofline` for the dominant kernel (nlr_mlp_kernel, timed with HIP events on its launch stream inside the timed region,
+the other kernels in an untimed pass after it), `cpu_baseline` (the CPU oracle on a bounded sample), `accuracy` (the timed
+precision against the oracle on that same sample), the `trained_scene` leg and, with N > 1, the collective timed alone.
+
+`--dump-outputs DIR` writes what the last timed step computed (the per-ray outputs `Model.render_rays` hands its caller, of
+rank 0's sector, and the packed [W, 32, 7] range image) as DIR/<name>.npy in float32 / float64 (int32 labels as float64),
+at most 64 MB in all (a fixed, seeded sample of rays beyond that).  Inputs depend on the arguments only, so two builds can
+be compared output for output.
 """
 import argparse
 import json
@@ -47,8 +55,13 @@ def parse_args(argv=None):
     ap.add_argument("--scaling", choices=["strong", "weak"], default="strong",
                     help="N > 1: strong = ONE 32x1024 sweep in N azimuth sectors (C4); weak = 1024*N columns")
     ap.add_argument("--log2-hashmap", type=int, default=None, help="shrink the hash tables (debug only)")
+    ap.add_argument("--full", action="store_true", help="besides the headline figure, measure and check everything else: kernel_ms and the "
+                    "roofline objects (HIP events in the timed region + an untimed pass), cpu_baseline + accuracy, the trained_scene leg, "
+                    "the collective timed alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed as "
+                    "DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     ap.add_argument("--cpu-rays", type=int, default=8192)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline / accuracy (and the trained_scene leg)")
     ap.add_argument("--table-dtype", choices=["f32", "f16"], default="f32", help="hash-table storage; f32 is the benchmark "
                     "configuration, f16 is what the reference uses under autocast (Z/gridencoder/grid.py:43-44)")
     ap.add_argument("--force-dist", action="store_true", help="rehearsal: self-launch, initialise RCCL and run the collective also with one rank")
@@ -69,8 +82,8 @@ def parse_args(argv=None):
     ap.add_argument("--inflate-log2", type=int, default=None, help="with --ckpt: re-lay the checkpoint's hash maps out at 2^N rows per hashed "
                     "level (nerflidar_hip.weights.inflate_hashmaps: the same field bit for bit, with the footprint and the access pattern "
                     "of the larger maps; 21 = the full-size configuration)")
-    ap.add_argument("--no-trained-leg", action="store_true", help="skip the `trained_scene` object (the default one-GPU run also renders "
-                    "the committed trained checkpoint, inflated to full-size maps, for a second, scene-shaped measurement)")
+    ap.add_argument("--no-trained-leg", action="store_true", help="with --full: skip the `trained_scene` object (the one-GPU --full run also "
+                    "renders the committed trained checkpoint, inflated to full-size maps, for a second, scene-shaped measurement)")
     ap.add_argument("--static-origin", action="store_true", help="render the SAME sweep every step (round 1-3 behaviour).  Default: step i "
                     "renders synthetic_sweep(sweep_idx = i mod 64) from pre-uploaded ray batches, as a LiDAR replay moves the sensor every "
                     "sweep (Z/train.py:484-485 counts rays of distinct batches), so the caches hold what a replay leaves, not the "
@@ -167,11 +180,41 @@ def accuracy(ref, r, idx):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def snapshot_outputs(r, img):
+    """Host copies of what the last timed step computed: the per-ray outputs of `render_rays` (without its `packed` view: the range
+    image carries it) and the packed range image, in float32, or float64 for integer and float64 arrays."""
+    import numpy as np
+    arrays = {k: v for k, v in (r or {}).items() if k != "packed"}
+    arrays["range_image"] = img
+    snap = {}
+    for k, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        snap[k] = a.astype(np.float32 if a.dtype in (np.float16, np.float32) else np.float64)
+    return snap
+
+
+def dump_outputs(out_dir, snap):
+    """DIR/<name>.npy per array; beyond DUMP_LIMIT_BYTES in all, the same fixed, seeded sample of rows (rays / azimuth columns) of each."""
+    import numpy as np
+    total = sum(a.nbytes for a in snap.values())
+    if total > DUMP_LIMIT_BYTES:
+        keep = DUMP_LIMIT_BYTES / total
+        for k, a in snap.items():
+            n = max(1, int(len(a) * keep))
+            snap[k] = a[np.sort(np.random.default_rng(0).choice(len(a), n, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in snap.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
+
+
 TRAINED_CKPT = os.path.join(ROOT, "tests", "golden", "ckpt_trained_c2")
 
 
 def trained_scene_leg(dev, precision, threads, steps=20, warmup=5, oracle_rays=2048):
-    """Second measurement of the default one-GPU run: the SAME configuration (C2: (64, 64, 128) samples, 8x256 NerfMLP + semantic +
+    """Second measurement of the one-GPU --full run: the SAME configuration (C2: (64, 64, 128) samples, 8x256 NerfMLP + semantic +
     intensity heads, full-size fp32 maps, one 32 x 1024 sweep per step, moving origin) on a TRAINED field instead of seeded white noise.
     The committed checkpoint (tests/golden/ckpt_trained_c2: `python -m nerflidar_hip.train_scene` on the analytic street scene, small
     hash maps so that it fits the repository) is re-laid out on 2^21-row maps by `weights.inflate_hashmaps` - the same function value
@@ -417,8 +460,9 @@ def main():
     # HIP events on the launch stream inside the timed region, around the two kernels the roofline objects are about (nlr_mlp_kernel,
     # nlr_encode8_kernel): 4 event records per step.  Bracketing all ten launches of a sweep costs 0.1 ms of a 7 ms step
     # (profiles/r03_emulated_sector_steps.txt), so the other kernels' durations come from a short untimed pass after the loop.
+    # --full only: a plain run times the steps without events.
     K_MLP, K_ENC = 4, 2  # NLR_K_MLP, NLR_K_ENCODE (include/nerflidar_hip.h)
-    prof = not os.environ.get("NLR_BENCH_NOPROF") and not caps  # (diagnostic switch: what do the HIP events themselves cost?)
+    prof = args.full and not os.environ.get("NLR_BENCH_NOPROF") and not caps  # (diagnostic switch: what do the HIP events themselves cost?)
     if prof:
         _lib.check(L.nlr_profile_begin_kinds(model._handle, (1 << K_MLP) | (1 << K_ENC)), "nlr_profile_begin_kinds")
     t0 = time.perf_counter()
@@ -427,9 +471,12 @@ def main():
     img = gat.image((args.warmup + args.steps - 1) if gat.collective else 0)
     barrier()
     dt = time.perf_counter() - t0
+    # the last timed step's outputs, copied before anything below renders into the same buffers again
+    snap = snapshot_outputs(last.get("r"), img) if (args.dump_outputs and rank == 0) else None
     ms = (C.c_float * _lib.NLR_K_COUNT)()
     cnt = (C.c_uint32 * _lib.NLR_K_COUNT)()
-    _lib.check(L.nlr_profile_end(model._handle, _lib.current_stream(), ms, cnt), "nlr_profile_end")
+    if args.full:
+        _lib.check(L.nlr_profile_end(model._handle, _lib.current_stream(), ms, cnt), "nlr_profile_end")
     if prof:  # untimed: every kernel bracketed, a few sweeps, for the `kernel_ms` breakdown of the launches outside the roofline objects
         ms2 = (C.c_float * _lib.NLR_K_COUNT)()
         cnt2 = (C.c_uint32 * _lib.NLR_K_COUNT)()
@@ -454,18 +501,66 @@ def main():
         torch.distributed.all_gather(every, own)
         ranks_seen, rank_ms = int(round(one.item())), [float(x.item()) / args.steps * 1e3 for x in every]
         dt = float(t.item())
-        # the collective alone (not overlapped), for the record
-        reps = max(args.steps, 20)
-        barrier()
-        ta = time.perf_counter()
-        for _ in range(reps):
-            torch.distributed.all_gather_into_tensor(gat.images[0], gat.tiles[0])
-        barrier()
-        ag_ms = (time.perf_counter() - ta) / reps * 1e3
+        if args.full:  # the collective alone (not overlapped), for the record
+            reps = max(args.steps, 20)
+            barrier()
+            ta = time.perf_counter()
+            for _ in range(reps):
+                torch.distributed.all_gather_into_tensor(gat.images[0], gat.tiles[0])
+            barrier()
+            ag_ms = (time.perf_counter() - ta) / reps * 1e3
     assert img.shape == (width, H_BEAMS, 7)
+    if snap is not None:
+        dump_outputs(args.dump_outputs, snap)
 
     if rank == 0:
         rays_total = n_rays * world * args.steps
+        bsha = buildinfo.binary_sha()
+        out = {
+            "metric": "LiDAR rays/sec @128 samples/ray, 8x256 MLP; depth L1 vs reference",
+            "value": rays_total / dt,
+            "unit": "rays/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": dt / args.steps * 1e3,
+            "higher_is_better": True,
+            "scaling": args.scaling,
+            "vs_baseline": None,
+            "dtype": {_lib.PREC_F32: "f32 (f32 MFMA everywhere)",
+                      _lib.PREC_MIXED: "f32 (sampling, hash grid, density/semantic/intensity layers on f32 MFMA) + bf16 MFMA (view MLP)",
+                      _lib.PREC_FAST: "f32 (sampling, hash grid) + split-bf16 x3 MFMA (density/semantic/intensity) + bf16 MFMA (view MLP)"}[args.precision],
+            "data": "synthetic",
+            "config": {"workload": f"{args.workload}: nuScenes 32-beam sweep, {H_BEAMS}x{width} rays per sweep, samples "
+                                   f"({','.join(str(x) for x in mc.level_samples())}), "
+                                   f"{mc.nerf_mlp.net_depth_viewdirs}x{mc.nerf_mlp.net_width_viewdirs} NerfMLP + semantic"
+                                   f"{' + intensity' if mc.config.use_intensity else ''} heads, "
+                                   f"{'full-size' if args.log2_hashmap is None else f'2^{args.log2_hashmap}-entry'} "
+                                   f"{'fp32' if args.table_dtype == 'f32' else 'fp16'} hash tables",
+                       "rays_per_gpu_per_step": n_rays, "azimuth_columns_total": width,
+                       "parallelism": f"azimuth-sector x{world}" + (" + 1 all_gather of the packed range image on a side stream" if use_dist else ""),
+                       "per_sample_history": bool(args.history), "hip_graph_replay": bool(caps),
+                       "weights": ("trained checkpoint" if args.ckpt else "seeded synthetic (white-noise tables, x1500 density gain)"),
+                       "sweep_origins": ("static: the same sweep every step" if args.static_origin else
+                                         f"moving: step i renders sweep i mod {n_sweeps} (pre-uploaded ray batches)"),
+                       "flops_per_ray": nflops.flops_per_ray(mc), "gather_bytes_per_ray": nflops.gather_bytes_per_ray(mc)},
+            "full": bool(args.full),
+            "debug_switches": {"force_generic_level_body": L.nlr_debug_get(_lib.DBG_FORCE_GENERIC), "mlp_workgroups": L.nlr_debug_get(_lib.DBG_MLP_WORKGROUPS),
+                               "ray_groups": L.nlr_debug_get(_lib.DBG_RAY_GROUPS)},
+            "kernel_source_sha": bsha[:16],
+            "binary_stale": buildinfo.stale(),
+        }
+        if ckpt_note:
+            out["config"]["checkpoint"] = ckpt_note
+        if emul:  # not a benchmark result: what ONE rank of an `emul`-way split does per step, measured on one GPU
+            out["emulated_world"] = emul
+            out["metric"] = f"DIAGNOSTIC per-rank step of a {emul}-way azimuth split (one GPU, no collective)"
+            out["projected_rays_per_s_at_world"] = n_rays * emul * args.steps / dt
+        if use_dist:
+            out["ranks_seen"] = ranks_seen  # all-reduce (SUM) of 1 over the process group: must equal n_gpus
+            out["rank_ms_per_step"] = {"min": round(min(rank_ms), 4), "max": round(max(rank_ms), 4), "all": [round(x, 4) for x in rank_ms]}
+            out["collective_backend"] = torch.distributed.get_backend()
+    if rank == 0 and args.full:
         kern = {KNAMES[i]: (ms[i] / cnt[i] if cnt[i] else 0.0) for i in range(_lib.NLR_K_COUNT)}
         # dominant kernel: nlr_mlp_kernel.  Algorithmic FLOPs per launch = 2 * MACs/sample (SURVEY 8d:
         # 657 408 for the 8x256 NerfMLP + heads) * samples per launch (rays * 128).
@@ -476,7 +571,7 @@ def main():
         achieved = fl_launch / mlp_s / 1e12 if mlp_s > 0 else 0.0
         # HBM traffic per launch comes from separate rocprofv3 --pmc passes (scripts/pmc_traffic.sh), which record the source hash
         # COMPILED INTO the binary they measured: a profile of other code is not a measurement of this binary.
-        bsha, ssha = buildinfo.binary_sha(), buildinfo.kernel_source_sha()
+        ssha = buildinfo.kernel_source_sha()
         prof = os.path.join(ROOT, "profiles", PMC_PROFILE)
         plain = (world == 1 and args.workload == "C2" and not args.chunk and not emul and args.width == W_COLS and args.table_dtype == "f32"
                  and args.precision == 2 and args.log2_hashmap is None and not args.ckpt and not args.static_origin and args.weight_scale is None
@@ -516,34 +611,7 @@ def main():
                    if props else 0.0)
         rg = gather_roofline("nlr_encode8_kernel", "encode", g_bytes, 1)
         rp = gather_roofline("nlr_prop8_kernel", "prop", p_bytes, len(props)) if props else None
-        out = {
-            "metric": "LiDAR rays/sec @128 samples/ray, 8x256 MLP; depth L1 vs reference",
-            "value": rays_total / dt,
-            "unit": "rays/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": args.scaling,
-            "vs_baseline": None,
-            "dtype": {_lib.PREC_F32: "f32 (f32 MFMA everywhere)",
-                      _lib.PREC_MIXED: "f32 (sampling, hash grid, density/semantic/intensity layers on f32 MFMA) + bf16 MFMA (view MLP)",
-                      _lib.PREC_FAST: "f32 (sampling, hash grid) + split-bf16 x3 MFMA (density/semantic/intensity) + bf16 MFMA (view MLP)"}[args.precision],
-            "data": "synthetic",
-            "config": {"workload": f"{args.workload}: nuScenes 32-beam sweep, {H_BEAMS}x{width} rays per sweep, samples "
-                                   f"({','.join(str(x) for x in mc.level_samples())}), "
-                                   f"{mc.nerf_mlp.net_depth_viewdirs}x{mc.nerf_mlp.net_width_viewdirs} NerfMLP + semantic"
-                                   f"{' + intensity' if mc.config.use_intensity else ''} heads, "
-                                   f"{'full-size' if args.log2_hashmap is None else f'2^{args.log2_hashmap}-entry'} "
-                                   f"{'fp32' if args.table_dtype == 'f32' else 'fp16'} hash tables",
-                       "rays_per_gpu_per_step": n_rays, "azimuth_columns_total": width,
-                       "parallelism": f"azimuth-sector x{world}" + (" + 1 all_gather of the packed range image on a side stream" if use_dist else ""),
-                       "per_sample_history": bool(args.history), "hip_graph_replay": bool(caps),
-                       "weights": ("trained checkpoint" if args.ckpt else "seeded synthetic (white-noise tables, x1500 density gain)"),
-                       "sweep_origins": ("static: the same sweep every step" if args.static_origin else
-                                         f"moving: step i renders sweep i mod {n_sweeps} (pre-uploaded ray batches)"),
-                       "flops_per_ray": nflops.flops_per_ray(mc), "gather_bytes_per_ray": nflops.gather_bytes_per_ray(mc)},
+        out.update({
             "kernel_ms": {k: round(v, 4) for k, v in kern.items()},
             "roofline": {"kernel": "nlr_mlp_kernel", "bound": "mfma", "achieved": achieved,
                          "peak": MFMA_BF16_DENSE_PEAK_TFLOPS, "unit": "TFLOP/s",
@@ -553,28 +621,16 @@ def main():
                                            "2 056 TFLOP/s at 2.39 GHz on all-zero operands): profiles/r04_power_trace.txt"},
             "roofline_gather": rg,
             "roofline_prop": rp,
-            "debug_switches": {"force_generic_level_body": L.nlr_debug_get(_lib.DBG_FORCE_GENERIC), "mlp_workgroups": L.nlr_debug_get(_lib.DBG_MLP_WORKGROUPS),
-                               "ray_groups": L.nlr_debug_get(_lib.DBG_RAY_GROUPS)},
-            "kernel_source_sha": bsha[:16],
-            "binary_stale": buildinfo.stale(),
-        }
-        if ckpt_note:
-            out["config"]["checkpoint"] = ckpt_note
+        })
         if caps:  # a captured sweep carries no per-kernel HIP events: nothing to report, rather than zeros
             out["kernel_ms"] = None
             out["roofline"].update(achieved=None, frac=None, traffic=None, traffic_note="HIP-graph replay: per-kernel durations are not measured in this mode")
             out["roofline_gather"] = out["roofline_prop"] = None
-        if emul:  # not a benchmark result: what ONE rank of an `emul`-way split does per step, measured on one GPU
-            out["emulated_world"] = emul
-            out["metric"] = f"DIAGNOSTIC per-rank step of a {emul}-way azimuth split (one GPU, no collective)"
-            out["projected_rays_per_s_at_world"] = n_rays * emul * args.steps / dt
+        if emul:
             out["roofline"]["traffic"], out["roofline"]["traffic_note"] = None, "full-sweep profile does not apply to a sector"
         if ag_ms is not None:
             out["allgather_ms"] = round(ag_ms, 4)
             out["allgather_bytes_per_rank"] = int(gat.tiles[0].numel() * 4)
-            out["ranks_seen"] = ranks_seen  # all-reduce (SUM) of 1 over the process group: must equal n_gpus
-            out["rank_ms_per_step"] = {"min": round(min(rank_ms), 4), "max": round(max(rank_ms), 4), "all": [round(x, 4) for x in rank_ms]}
-            out["collective_backend"] = torch.distributed.get_backend()
         if world == 1 and not args.no_cpu_baseline and "r" in last:
             threads = host_cores()
             idx = np.linspace(0, n_rays - 1, args.cpu_rays).astype(np.int64)
@@ -584,6 +640,7 @@ def main():
                 del model, last["r"]
                 torch.cuda.empty_cache()
                 out["trained_scene"] = trained_scene_leg(dev, args.precision, threads)
+    if rank == 0:
         print(json.dumps(out))
     if use_dist:
         torch.distributed.barrier()

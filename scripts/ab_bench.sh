@@ -7,7 +7,7 @@ ERR=${GRAFT_REPO_ROOT:-.}/gpurun_out/ab_bench.err
 mkdir -p $(dirname $ERR)
 for i in $(seq $R); do
   for L in "$@"; do
-    NLR_LIB_PATH=$L timeout -k 10 200 python bench.py --steps 30 --warmup 8 --no-cpu-baseline $ARGS 2>>$ERR | tail -1 | \
+    NLR_LIB_PATH=$L timeout -k 10 200 python bench.py --full --steps 30 --warmup 8 --no-cpu-baseline $ARGS 2>>$ERR | tail -1 | \
       python -c "
 import sys, json
 line = sys.stdin.read()

@@ -4,7 +4,7 @@ L=$PWD/nerf-lidar_amd/build/var/lib_encdbg.so
 for CH in 32 64 128 256 16; do
   for W in white trained; do
     if [ $W = trained ]; then A="--ckpt tests/golden/ckpt_trained_c2 --inflate-log2 21"; else A=""; fi
-    NLR_ENC_CHUNK=$CH NLR_LIB_PATH=$L timeout -k 10 200 python bench.py --steps 30 --warmup 8 --no-cpu-baseline --no-trained-leg $A 2>/dev/null | tail -1 | \
+    NLR_ENC_CHUNK=$CH NLR_LIB_PATH=$L timeout -k 10 200 python bench.py --full --steps 30 --warmup 8 --no-cpu-baseline --no-trained-leg $A 2>/dev/null | tail -1 | \
       CH=$CH W=$W python -c "
 import sys, json, os
 d = json.loads(sys.stdin.read()); k = d['kernel_ms']

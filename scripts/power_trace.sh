@@ -12,11 +12,11 @@ SP=$!
 sleep 3
 ph() { echo "$1 $(date +%s.%N)" >> $OUT/phases.txt; }
 ph idle_end
-ph soak_noise_start;   python3 bench.py --steps 1500 --warmup 20 --no-cpu-baseline --no-trained-leg > $OUT/soak_noise.json 2> $OUT/soak_noise.err;   ph soak_noise_end
+ph soak_noise_start;   python3 bench.py --full --steps 1500 --warmup 20 --no-cpu-baseline --no-trained-leg > $OUT/soak_noise.json 2> $OUT/soak_noise.err;   ph soak_noise_end
 sleep 3
-ph soak_zero_start;    python3 bench.py --steps 1500 --warmup 20 --no-cpu-baseline --weight-scale 0 > $OUT/soak_zero.json 2> $OUT/soak_zero.err;    ph soak_zero_end
+ph soak_zero_start;    python3 bench.py --full --steps 1500 --warmup 20 --no-cpu-baseline --weight-scale 0 > $OUT/soak_zero.json 2> $OUT/soak_zero.err;    ph soak_zero_end
 sleep 3
-ph soak_trained_start; python3 bench.py --steps 800 --warmup 20 --no-cpu-baseline --ckpt tests/golden/ckpt_trained_c2 --inflate-log2 21 > $OUT/soak_trained.json 2> $OUT/soak_trained.err; ph soak_trained_end
+ph soak_trained_start; python3 bench.py --full --steps 800 --warmup 20 --no-cpu-baseline --ckpt tests/golden/ckpt_trained_c2 --inflate-log2 21 > $OUT/soak_trained.json 2> $OUT/soak_trained.err; ph soak_trained_end
 sleep 3
 ph micro_random_start; timeout -k 5 60 nerf-lidar_amd/build/mfma_shape4 10 > $OUT/micro_random.txt 2>&1;      ph micro_random_end
 sleep 3

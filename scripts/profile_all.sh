@@ -9,11 +9,11 @@ R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd $R
-python3 bench.py --steps 50 --warmup 10 > $OUT/bench.json 2> $OUT/bench.err
+python3 bench.py --full --steps 50 --warmup 10 > $OUT/bench.json 2> $OUT/bench.err
 python3 -c "import sys; sys.path.insert(0, \"nerf-lidar_amd\"); from nerflidar_hip import buildinfo; print(buildinfo.binary_sha()); print(\"stale:\", buildinfo.stale())" > $OUT/kernel_source_sha.txt
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-trained-leg > $OUT/bench_under_rocprof.json 2> $OUT/trace.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_tr -- python3 $R/bench.py --ckpt $R/tests/golden/ckpt_trained_c2 --inflate-log2 21 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_trained_under_rocprof.json 2> $OUT/trace_tr.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-trained-leg > $OUT/bench_under_rocprof.json 2> $OUT/trace.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_tr -- python3 $R/bench.py --full --ckpt $R/tests/golden/ckpt_trained_c2 --inflate-log2 21 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_trained_under_rocprof.json 2> $OUT/trace_tr.err
 # FETCH_SIZE calibration on a known count of random 64-byte lines (scripts/micro/gather_rand.hip prints the line count per launch)
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/calib -- $R/nerf-lidar_amd/build/gather_rand > $OUT/gather_rand_under_pmc.txt 2> $OUT/calib.err
 cd $R

@@ -14,10 +14,10 @@ cd $R/nerf-lidar_amd
 python3 -m nerflidar_hip.train_scene --workload C2 --steps $STEPS --rays 16384 --depth-lam 1.0 --log-every 500 --out $CK > $OUT/train.log 2> $OUT/train.err || exit 1
 cp $CK/train_summary.json $OUT/train_summary.json
 cd $R
-python3 bench.py --ckpt $CK > $OUT/bench_trained.json 2> $OUT/bench_trained.err || exit 1
-python3 bench.py --ckpt $CK --static-origin --no-cpu-baseline > $OUT/bench_trained_static_origin.json 2>> $OUT/bench_trained.err
-python3 bench.py > $OUT/bench_noise.json 2> $OUT/bench_noise.err
-python3 bench.py --static-origin --no-cpu-baseline > $OUT/bench_noise_static_origin.json 2>> $OUT/bench_noise.err
+python3 bench.py --full --ckpt $CK > $OUT/bench_trained.json 2> $OUT/bench_trained.err || exit 1
+python3 bench.py --full --ckpt $CK --static-origin --no-cpu-baseline > $OUT/bench_trained_static_origin.json 2>> $OUT/bench_trained.err
+python3 bench.py --full > $OUT/bench_noise.json 2> $OUT/bench_noise.err
+python3 bench.py --full --static-origin --no-cpu-baseline > $OUT/bench_noise_static_origin.json 2>> $OUT/bench_noise.err
 # L2 hit rates and bytes past L2 on the trained field (separate --pmc passes)
 cd /tmp && export TMPDIR=/tmp
 for C in "TCC_HIT_sum TCC_MISS_sum" "FETCH_SIZE"; do

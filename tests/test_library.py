@@ -231,6 +231,34 @@ def test_binary_carries_its_source_hash_and_stale_builds_lose_traffic(tmp_path, 
     assert t is None and "was measured on kernel source 000000000000" in note
 
 
+def test_bench_dump_outputs_are_float_files_within_the_limit(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR`: one float32 / float64 .npy per output (int32 labels exact in float64, the `packed` view left to
+    `range_image`); beyond the size limit a fixed, seeded sample of rows, the same from run to run.  `--full` is off by default."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    a = bench.parse_args([])
+    assert not a.full and a.dump_outputs is None
+    a = bench.parse_args(["--full", "--dump-outputs", str(tmp_path)])
+    assert a.full and a.dump_outputs == str(tmp_path)
+    r = {"depth": torch.arange(10, dtype=torch.float32), "labels": torch.arange(10, dtype=torch.int32) * 3, "packed": torch.zeros(10, 7)}
+    snap = bench.snapshot_outputs(r, torch.ones(5, 2, 7))
+    assert set(snap) == {"depth", "labels", "range_image"}
+    assert snap["depth"].dtype == np.float32 and snap["labels"].dtype == np.float64 and snap["range_image"].dtype == np.float32
+    bench.dump_outputs(str(tmp_path / "all"), dict(snap))
+    np.testing.assert_array_equal(np.load(tmp_path / "all" / "labels.npy"), np.arange(10) * 3)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 100)   # 400 bytes of outputs: a quarter of the rows of each
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), dict(snap))
+    names = sorted(os.listdir(tmp_path / "s1"))
+    assert names == ["depth.npy", "labels.npy", "range_image.npy"]
+    assert sum(np.load(tmp_path / "s1" / n).nbytes for n in names) <= 100
+    for n in names:
+        np.testing.assert_array_equal(np.load(tmp_path / "s1" / n), np.load(tmp_path / "s2" / n))
+    assert set(np.load(tmp_path / "s1" / "depth.npy")) <= set(snap["depth"])
+
+
 def test_fast_level_body_envelope_is_what_32_bit_arithmetic_needs():
     """`nlr_level_fast_ok` just inside / outside each of its limits (host arithmetic only, no table is touched).  A level of
     2^28 sixteen-byte entries is 4 GiB = 2^32 bytes: the last size whose byte offsets fit; 2^29 is out.  Smoothstep, align_corners and
