@@ -365,7 +365,14 @@ int nlr_hash_decay_backward(const float *embeddings, const int32_t *offsets_host
  *       layouts of nlr_mlp_level; acts [M, nlr_train_act_width()] bf16 = [hid 64 | bottleneck | head hidden | x_0 .. x_{D-1}].
  *     backward: upstream gradients in the layouts of the outputs (NULL = zero); gacts [M, act_width + 64] bf16 = the gradient of
  *       every pre-activation in the columns of acts, then [d head outputs 32 | d rgb_layer outputs 32]; d_features [M, F] f32.
- *       The weight gradients are GEMMs over these tensors, dW_l = gacts_l^T . acts_{l-1} (plain library GEMMs, host side).
+ *     wgrad: the weight gradients are GEMMs over these tensors, dW_l = gacts_l^T . input_l, and the bias gradients their column
+ *       sums; nlr_mlp_train_wgrad computes all of them in one MFMA kernel (bf16 operands read from LDS with the transposed read,
+ *       f32 accumulation) plus one reduce kernel.  features / enc as the forward took them (rounded to bf16 inside the kernel, enc
+ *       row m / S, its first 3 + 6 deg_view columns); d_params [n_params] f32 in the order of the flat parameter buffer, every
+ *       element OVERWRITTEN (layers whose upstream gradient was NULL get zeros).  M is split into 8 slices whose partial results
+ *       go to f32 slabs in the workspace and are summed in slice order: no atomics, the same inputs give the same bits.
+ *       nlr_mlp_train_wgrad_workspace_bytes = 8 * n_params * 4 bytes, independent of M (largest plan: 32 MiB).
+ *       Refused with nothing launched: NULL argument, M == 0, M % S != 0, workspace_bytes below that size.
  * ------------------------------------------------------------------------------------------ */
 typedef struct NlrTrainPlan NlrTrainPlan;
 int nlr_train_plan_create(uint32_t F, uint32_t W, uint32_t WB, uint32_t D, uint32_t deg_view, uint32_t class_num,
@@ -380,6 +387,9 @@ int nlr_mlp_train_forward(const NlrTrainPlan *p, const float *features, const fl
 int nlr_mlp_train_backward(const NlrTrainPlan *p, uint32_t M, uint32_t S, const float *density, const float *rgb,
                            const float *semantic, const void *acts, const float *g_density, const float *g_rgb,
                            const float *g_semantic, const float *g_intensity, void *gacts, float *d_features, void *stream);
+size_t nlr_mlp_train_wgrad_workspace_bytes(const NlrTrainPlan *p, uint32_t M);
+int nlr_mlp_train_wgrad(const NlrTrainPlan *p, uint32_t M, uint32_t S, const float *features, const float *enc, const void *acts,
+                        const void *gacts, float *d_params, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * (7) Dynamic-object branch: owner of every sample.  winner [N,S] int32 = index of the LAST

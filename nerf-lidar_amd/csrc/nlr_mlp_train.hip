@@ -12,12 +12,14 @@
 //   backward tape: RGB^T L(D-1)^T..L2^T V1a^T H2^T BIG D2^T D0^T with BIG = [V1 skip^T | V0^T | H1^T | e_0]: the gradient of the
 //            bottleneck collects its four sources (skip concat, view layer 0, heads, raw density) in ONE accumulator chain.
 //            Every layer's pre-activation gradient is stored row-major in `gacts`; the gradient of the features goes out in f32.
-// Weight gradients are plain GEMMs over the saved tensors (dW_l = gacts_l^T . acts_{l-1}, M-long reductions): library GEMMs on the
-// host side (nerflidar_hip/training.py), as are the bias sums.  The tapes are re-packed on the device from the flat parameter
-// buffer before every step (nlr_train_pack: one gather through an index map built once).
+// Weight gradients are GEMMs over the saved tensors (dW_l = gacts_l^T . acts_{l-1}, M-long reductions), as are the bias sums:
+// nlr_mlp_train_wgrad (nlr_mlp_wgrad.hip) computes all of them in one MFMA kernel plus a slab reduce; nerflidar_hip/training.py
+// also keeps the older form, library GEMMs on the host side, as its default.  The tapes are re-packed on the device from the flat
+// parameter buffer before every step (nlr_train_pack: one gather through an index map built once).
 #include <vector>
 
 #include "nlr_mlp_kernel.h"
+#include "nlr_train_plan.h"
 
 struct TrainParams {
     uint32_t M, S, F, depth, K, int_row, act_w;
@@ -541,17 +543,6 @@ static void tape_add(std::vector<int32_t> &t, const IMat &w, uint32_t out_pad, u
 }
 static void tape_pad(std::vector<int32_t> &t) { t.resize((t.size() + 16383) / 16384 * 16384, -1); }  // 32 KiB of bf16
 
-struct NlrTrainPlan {
-    uint32_t F, W, WB, HT, D, K, int_row, act_w, n_params, cus;
-    bool sem, inten;
-    float density_bias, rgb_premul, rgb_bias, rgb_padding;
-    int32_t *fidx = nullptr, *bidx = nullptr, *biasidx = nullptr;
-    uint32_t fn = 0, bn = 0, biasn = 0;
-    __bf16 *ftape = nullptr, *btape = nullptr;
-    float *bias = nullptr;
-    std::vector<uint32_t> offs;  // flat offsets: see nlr_train_param_layout
-};
-
 static IMat lin(uint32_t off, uint32_t rows, uint32_t cols) {
     IMat m(rows, cols);
     for (uint32_t r = 0; r < rows; ++r)
@@ -575,7 +566,7 @@ extern "C" int nlr_train_plan_create(uint32_t F, uint32_t W, uint32_t WB, uint32
     NLR_CHECK_ARG(WB == 256 && (W == 128 || W == 256) && F % 4 == 0 && F > 32 && F <= 64 && D >= 2 && D <= 10 && E <= 32 && class_num <= 31,
                   "train_plan_create: unsupported NerfMLP shape (bottleneck 256, view width 128/256, 33..64 grid features, depth 2..10)");
     NlrTrainPlan *p = new NlrTrainPlan();
-    p->F = F, p->W = W, p->WB = WB, p->D = D, p->sem = use_semantic != 0, p->inten = use_intensity != 0;
+    p->F = F, p->W = W, p->WB = WB, p->D = D, p->E = E, p->sem = use_semantic != 0, p->inten = use_intensity != 0;
     p->K = p->sem ? class_num : 0;
     p->int_row = p->inten ? p->K : 0xffffffffu;
     p->HT = (p->sem ? 2 : 0) + (p->inten ? 2 : 0);

@@ -87,7 +87,7 @@ EXPORTS = ["nlr_last_error", "nlr_version", "nlr_build_sha", "nlr_debug_set", "n
            "nlr_render_rays_dynamic", "nlr_prop_mlp_forward", "nlr_prop_mlp_backward", "nlr_encode_features_forward",
            "nlr_encode_features_backward", "nlr_encode_features_backward_ws", "nlr_grid_encode_backward_ws", "nlr_grid_backward_workspace_bytes",
            "nlr_train_plan_create", "nlr_train_plan_destroy", "nlr_train_act_width", "nlr_train_param_layout", "nlr_train_pack",
-           "nlr_mlp_train_forward", "nlr_mlp_train_backward"]
+           "nlr_mlp_train_forward", "nlr_mlp_train_backward", "nlr_mlp_train_wgrad_workspace_bytes", "nlr_mlp_train_wgrad"]
 NLR_K_COUNT = 6
 DBG_FORCE_GENERIC, DBG_MLP_WORKGROUPS, DBG_BINNED_C4, DBG_NO_XPAIR_SCATTER, DBG_SCATTER_LEVELS, DBG_NO_SCATTER_CACHE, DBG_RAY_GROUPS = 0, 1, 2, 3, 4, 5, 6
 
@@ -173,6 +173,9 @@ def lib():
         L.nlr_train_pack.argtypes = [c_fp, c_fp, c_fp]
         L.nlr_mlp_train_forward.argtypes = [c_fp, c_fp, c_fp, C.c_uint32, C.c_uint32, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]
         L.nlr_mlp_train_backward.argtypes = [c_fp, C.c_uint32, C.c_uint32] + [c_fp] * 11
+        L.nlr_mlp_train_wgrad_workspace_bytes.restype = C.c_size_t
+        L.nlr_mlp_train_wgrad_workspace_bytes.argtypes = [c_fp, C.c_uint32]
+        L.nlr_mlp_train_wgrad.argtypes = [c_fp, C.c_uint32, C.c_uint32] + [c_fp] * 6 + [C.c_size_t, c_fp]
         L.nlr_profile_begin.argtypes = [c_fp]
         L.nlr_profile_begin_kinds.argtypes = [c_fp, C.c_uint32]
         L.nlr_profile_end.argtypes = [c_fp, c_fp, c_fp, c_fp]

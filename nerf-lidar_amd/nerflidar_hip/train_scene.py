@@ -50,6 +50,8 @@ def main(argv=None) -> int:
     ap.add_argument("--steps", type=int, default=3000)
     ap.add_argument("--rays", type=int, default=16384, help="rays per step (Config.batch_size is 65 536, configs.py:29)")
     ap.add_argument("--fused", type=int, default=1, help="1: fused bf16 MFMA NerfMLP forward / backward; 0: torch Linear modules in fp32")
+    ap.add_argument("--fused-wgrad", action="store_true",
+                    help="weight gradients of the fused NerfMLP from nlr_mlp_train_wgrad (one MFMA kernel) instead of library GEMMs; requires --fused 1")
     ap.add_argument("--lr-init", type=float, default=0.01)
     ap.add_argument("--lr-final", type=float, default=0.001)
     ap.add_argument("--lr-delay-steps", type=int, default=None, help="default: a fifth of the run (5 000 of 25 000 in configs.py:87)")
@@ -62,12 +64,14 @@ def main(argv=None) -> int:
     ap.add_argument("--log-every", type=int, default=200)
     ap.add_argument("--eval-every", type=int, default=0, help="also render the held-out sweep on the fused inference path every this many steps")
     a = ap.parse_args(argv)
+    if a.fused_wgrad and not a.fused:
+        ap.error("--fused-wgrad requires --fused 1")
     if not torch.cuda.is_available():
         raise RuntimeError("train_scene needs a GPU: the training operators have no CPU fallback")
     dev = torch.device("cuda", torch.cuda.current_device())
     torch.manual_seed(a.seed)
     mc = nconfig.workload(a.workload, a.log2_hashmap)
-    tm = ntrain.TrainableModel(mc, fused_mlp=bool(a.fused)).to(dev)
+    tm = ntrain.TrainableModel(mc, fused_mlp=bool(a.fused), fused_wgrad=a.fused_wgrad).to(dev)
     delay = a.lr_delay_steps if a.lr_delay_steps is not None else max(a.steps // 5, 1)
     opt, lr_fn = ntrain.create_optimizer(tm, a.lr_init, a.lr_final, a.steps, delay)
     t0 = time.time()
@@ -94,7 +98,7 @@ def main(argv=None) -> int:
     # the round trip a user of the reference takes: file -> state_dict -> Model (weights packed for the fused kernels)
     model, step, ignored = nckpt.model_from_checkpoint(a.out, base=mc)
     ev = evaluate(model, a.scale_factor, seed=a.seed)
-    summary = dict(workload=a.workload, log2_hashmap=a.log2_hashmap, steps=a.steps, rays_per_step=a.rays, fused=bool(a.fused),
+    summary = dict(workload=a.workload, log2_hashmap=a.log2_hashmap, steps=a.steps, rays_per_step=a.rays, fused=bool(a.fused), fused_wgrad=a.fused_wgrad,
                    train_seconds=round(train_s, 1), train_rays_per_s=round(a.steps * a.rays / train_s), checkpoint=path,
                    checkpoint_bytes=os.path.getsize(path), restored_step=step, held_out_sweep=ev, final_terms=log[-1])
     print(json.dumps(summary), flush=True)

@@ -244,9 +244,66 @@ def encode_features_fused(encoder, batch, tdist, sample_n: int = 7, sample_m: in
 
 
 # ---- fused NerfMLP for training: nlr_mlp_train_forward / nlr_mlp_train_backward (csrc/nlr_mlp_train.hip) ---------------------------
+def _wgrad_bmm(level, M, f, e, acts, gacts):
+    """The weight and bias gradients of the fused NerfMLP as split-K library GEMMs over the tensors the kernels saved: the list
+    [dW, db, dW, db, ..] in the order of `TrainableNerfLevel._mlp_params`.  `_FusedMLP.backward` without `fused_wgrad` and
+    `scripts/wgrad_bench.py` call this same code."""
+    plan, cfg = level._plan, level.cfg
+    dev = f.device
+    K = cfg.class_num if cfg.use_semantic else 0
+    # ---- weight gradients: plain GEMMs over the saved tensors (f32 accumulate and result)
+    W, WB, D = cfg.net_width_viewdirs, cfg.bottleneck_width, cfg.net_depth_viewdirs
+    HH = (64 if K else 0) + (64 if cfg.use_intensity else 0)
+    c_hid, c_hbe, c_q, c_x = 0, 64, 64 + WB, 64 + WB + HH
+    a = lambda c0, n: acts[:, c0:c0 + n]
+    g = lambda c0, n: gacts[:, c0:c0 + n]
+    E = cfg.dim_dir_enc
+    enc_s = e[:, :E].to(torch.bfloat16).repeat_interleave(level._S, dim=0)  # the bf16 values the forward chain consumed
+
+    # [M, out]^T . [M, in_0 | in_1 | ..]: bf16 operands, f32 accumulation.  The reduction runs over M (10^5..10^6) into a
+    # 256 x 256 result: as ONE library GEMM that is 16 output tiles = 16 busy CUs, so M is cut into `ck` batches (split-K as a
+    # batched GEMM over strided views, no copies) whose partial results are summed in f32.
+    ck = 1
+    while ck < 128 and M % (2 * ck) == 0 and M // (2 * ck) >= 2048:
+        ck *= 2
+
+    def wgrad(gy, *xs):
+        gb = gy.reshape(ck, M // ck, gy.shape[1]).transpose(1, 2)
+        return torch.cat([torch.bmm(gb, x.reshape(ck, M // ck, x.shape[1])).float().sum(0) for x in xs], 1)
+
+    grads = []
+
+    ones = torch.ones(ck, 1, M // ck, device=dev, dtype=torch.bfloat16)
+
+    def lin(gy, *xs):
+        grads.append(wgrad(gy, *xs))
+        # bias gradient = 1^T gy, through the same split-K batched GEMM (a column reduction of a strided [M, out] view runs at
+        # a tenth of the memory bandwidth as an elementwise reduce kernel)
+        grads.append(torch.bmm(ones, gy.reshape(ck, M // ck, gy.shape[1])).float().sum(0)[0])
+
+    lin(g(c_hid, 64), f.to(torch.bfloat16))
+    lin(g(c_hbe, WB), a(c_hid, 64))
+    r0 = 0
+    if K:
+        lin(g(c_q, 64), a(c_hbe, WB))
+        lin(g(plan.act_w, K), a(c_q, 64))
+        r0 = 64
+    if cfg.use_intensity:
+        lin(g(c_q + r0, 64), a(c_hbe, WB))
+        lin(g(plan.act_w + K, 1), a(c_q + r0, 64))
+    lin(g(c_x, W), a(c_hbe, WB), enc_s)
+    if D > 1:
+        lin(g(c_x + W, W), a(c_x, W), a(c_hbe, WB), enc_s)
+    for l in range(2, D):
+        lin(g(c_x + l * W, W), a(c_x + (l - 1) * W, W))
+    lin(g(plan.act_w + 32, 3), a(c_x + (D - 1) * W, W))
+    return grads
+
+
 class _FusedMLP(torch.autograd.Function):
     """The Linear stack of ZI/models.py:1116-1251 (density trunk, heads, view MLP, rgb) as two MFMA-chain kernels.  The weight
-    gradients are GEMMs over the tensors those kernels save: dW_l = (d pre-activation_l)^T . (input_l), M-long reductions."""
+    gradients are GEMMs over the tensors those kernels save: dW_l = (d pre-activation_l)^T . (input_l), M-long reductions: library
+    GEMMs (`_wgrad_bmm`) or, with `fused_wgrad`, `nlr_mlp_train_wgrad` (csrc/nlr_mlp_wgrad.hip)."""
 
     @staticmethod
     def forward(ctx, feats, enc, level, *params):
@@ -295,52 +352,22 @@ class _FusedMLP(torch.autograd.Function):
         if getattr(level, "_keep_debug", False):  # tests look at the kernels' raw results
             level._dbg = {k: v.detach() for k, v in dict(acts=acts, gacts=gacts, d_feat=d_feat, feats=f, enc=e, density=density, rgb=rgb,
                                                         sem=sem, inten=inten).items()}
-        # ---- weight gradients: plain GEMMs over the saved tensors (f32 accumulate and result)
-        W, WB, D = cfg.net_width_viewdirs, cfg.bottleneck_width, cfg.net_depth_viewdirs
-        HH = (64 if K else 0) + (64 if cfg.use_intensity else 0)
-        c_hid, c_hbe, c_q, c_x = 0, 64, 64 + WB, 64 + WB + HH
-        a = lambda c0, n: acts[:, c0:c0 + n]
-        g = lambda c0, n: gacts[:, c0:c0 + n]
-        E = cfg.dim_dir_enc
-        enc_s = e[:, :E].to(torch.bfloat16).repeat_interleave(level._S, dim=0)  # the bf16 values the forward chain consumed
-
-        # [M, out]^T . [M, in_0 | in_1 | ..]: bf16 operands, f32 accumulation.  The reduction runs over M (10^5..10^6) into a
-        # 256 x 256 result: as ONE library GEMM that is 16 output tiles = 16 busy CUs, so M is cut into `ck` batches (split-K as a
-        # batched GEMM over strided views, no copies) whose partial results are summed in f32.
-        ck = 1
-        while ck < 128 and M % (2 * ck) == 0 and M // (2 * ck) >= 2048:
-            ck *= 2
-
-        def wgrad(gy, *xs):
-            gb = gy.reshape(ck, M // ck, gy.shape[1]).transpose(1, 2)
-            return torch.cat([torch.bmm(gb, x.reshape(ck, M // ck, x.shape[1])).float().sum(0) for x in xs], 1)
-
-        grads = []
-
-        ones = torch.ones(ck, 1, M // ck, device=dev, dtype=torch.bfloat16)
-
-        def lin(gy, *xs):
-            grads.append(wgrad(gy, *xs))
-            # bias gradient = 1^T gy, through the same split-K batched GEMM (a column reduction of a strided [M, out] view runs at
-            # a tenth of the memory bandwidth as an elementwise reduce kernel)
-            grads.append(torch.bmm(ones, gy.reshape(ck, M // ck, gy.shape[1])).float().sum(0)[0])
-
-        lin(g(c_hid, 64), f.to(torch.bfloat16))
-        lin(g(c_hbe, WB), a(c_hid, 64))
-        r0 = 0
-        if K:
-            lin(g(c_q, 64), a(c_hbe, WB))
-            lin(g(plan.act_w, K), a(c_q, 64))
-            r0 = 64
-        if cfg.use_intensity:
-            lin(g(c_q + r0, 64), a(c_hbe, WB))
-            lin(g(plan.act_w + K, 1), a(c_q + r0, 64))
-        lin(g(c_x, W), a(c_hbe, WB), enc_s)
-        if D > 1:
-            lin(g(c_x + W, W), a(c_x, W), a(c_hbe, WB), enc_s)
-        for l in range(2, D):
-            lin(g(c_x + l * W, W), a(c_x + (l - 1) * W, W))
-        lin(g(plan.act_w + 32, 3), a(c_x + (D - 1) * W, W))
+        if level.fused_wgrad:
+            # ---- weight gradients: one MFMA kernel + a slab reduce (nlr_mlp_train_wgrad); views of one [n_params] f32 buffer
+            d_params = torch.empty(plan.n_params, device=dev, dtype=torch.float32)
+            ws = level._wgrad_workspace(dev)
+            with torch.cuda.device(dev):
+                _lib.check(_lib.lib().nlr_mlp_train_wgrad(plan.handle, M, level._S, _lib.ptr(f), _lib.ptr(e), _lib.ptr(acts), _lib.ptr(gacts),
+                                                          _lib.ptr(d_params), _lib.ptr(ws), ws.numel(), _lib.current_stream()),
+                           "nlr_mlp_train_wgrad")
+            if getattr(level, "_keep_debug", False):
+                level._dbg["d_params"] = d_params.detach()
+            grads, off = [], 0
+            for p in level._mlp_params():
+                grads.append(d_params[off:off + p.numel()].view(p.shape))
+                off += p.numel()
+        else:
+            grads = _wgrad_bmm(level, M, f, e, acts, gacts)
         return (d_feat, None, None) + tuple(grads)
 
 
@@ -369,14 +396,20 @@ class TrainableNerfLevel(torch.nn.Module):
     `nerflidar_hip.models.Model` for fused inference.  forward = MLP.forward (models.py:1036-1265, inference subset:
     disable_density_normals, no GLO) on the intervals of `tdist`; `render` adds the compositing."""
 
-    def __init__(self, cfg, table_std: float = 1e-4, fused_mlp: bool = False):
+    def __init__(self, cfg, table_std: float = 1e-4, fused_mlp: bool = False, fused_wgrad: bool = False):
         """fused_mlp: run the Linear stack through nlr_mlp_train_forward / _backward (bf16 MFMA chains, f32 accumulation) instead
-        of torch Linear modules; parameters, their names and their gradients are the same objects either way."""
+        of torch Linear modules; parameters, their names and their gradients are the same objects either way.
+        fused_wgrad (needs fused_mlp): the weight and bias gradients from nlr_mlp_train_wgrad (one MFMA kernel, f32 accumulation
+        over all of M, bit-reproducible) instead of split-K library GEMMs."""
         super().__init__()
         from .gridencoder import GridEncoder
         nn = torch.nn
         self.cfg = cfg
+        if fused_wgrad and not fused_mlp:
+            raise ValueError("fused_wgrad=True needs fused_mlp=True: the weight-gradient kernel reads what the fused kernels save")
         self.fused_mlp = bool(fused_mlp)
+        self.fused_wgrad = bool(fused_wgrad)
+        self._wgrad_ws = {}  # device -> workspace of nlr_mlp_train_wgrad, allocated once
         self.fused_encode = bool(fused_mlp)  # cast + encode + re-weight + mean as one operator (encode_features_fused)
         self._plan = None
         if self.fused_mlp and cfg.use_semantic and cfg.no_sem_layer:
@@ -454,6 +487,14 @@ class TrainableNerfLevel(torch.nn.Module):
         for m in mods:
             out += [m.weight, m.bias]
         return out
+
+    def _wgrad_workspace(self, dev):
+        """The slab workspace of nlr_mlp_train_wgrad on `dev`: its size depends on the plan only, so one allocation serves every step."""
+        ws = self._wgrad_ws.get(dev)
+        if ws is None:
+            n = int(_lib.lib().nlr_mlp_train_wgrad_workspace_bytes(self._plan.handle, 0))
+            ws = self._wgrad_ws[dev] = torch.empty(n, device=dev, dtype=torch.uint8)
+        return ws
 
     def _forward_fused(self, batch, feats):
         from .objects import _pos_enc
@@ -619,7 +660,7 @@ class TrainableModel(torch.nn.Module):
     hash-grid features and their gradient from the HIP grid operator, the NerfMLP from torch Linear modules or the fused MFMA
     forward / backward (`fused_mlp=True`), compositing and its gradient from `nlr_composite_level` / `nlr_composite_backward`."""
 
-    def __init__(self, mc, fused_mlp: bool = False, tracks=None, class_names=None, obj_log2_hashmap: int = 21):
+    def __init__(self, mc, fused_mlp: bool = False, fused_wgrad: bool = False, tracks=None, class_names=None, obj_log2_hashmap: int = 21):
         super().__init__()
         self.mc = mc
         for i in range(mc.num_levels - 1):
@@ -627,7 +668,7 @@ class TrainableModel(torch.nn.Module):
         import dataclasses
         ncfg = dataclasses.replace(mc.nerf_mlp, use_semantic=mc.config.use_semantic, use_intensity=mc.config.use_intensity,
                                    no_sem_layer=mc.config.no_sem_layer)
-        self.nerf_mlp = TrainableNerfLevel(ncfg, fused_mlp=fused_mlp)
+        self.nerf_mlp = TrainableNerfLevel(ncfg, fused_mlp=fused_mlp, fused_wgrad=fused_wgrad)
         self.instance_obj = bool(mc.config.instance_obj)
         if self.instance_obj:
             from .config import obj_mlp_config

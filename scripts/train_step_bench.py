@@ -19,8 +19,8 @@ batch.update(rgb=torch.rand(n, 3, device="cuda", generator=g), depth=torch.rand(
 if mc.config.use_intensity:
     batch["intensity"] = torch.rand(n, device="cuda", generator=g)
 print(f"workload {name}: {n} rays x {mc.level_samples()} samples, NerfMLP {mc.nerf_mlp.net_depth_viewdirs} x {mc.nerf_mlp.net_width_viewdirs}")
-for fused in (False, True):
-    tm = ntrain.TrainableModel(mc, fused_mlp=fused).cuda().load_reference(sd)
+for fused, wgrad in ((False, False), (True, False), (True, True)):
+    tm = ntrain.TrainableModel(mc, fused_mlp=fused, fused_wgrad=wgrad).cuda().load_reference(sd)
     opt = torch.optim.Adam(tm.parameters(), lr=1e-3, eps=1e-15)
     # the SAME step on both paths: same weights, deterministic sample positions, no update (lr irrelevant: loss is of the forward).
     # (Round 2 printed the loss after 13 randomized Adam steps drawn from one running RNG stream, i.e. of two different random
@@ -36,6 +36,6 @@ for fused in (False, True):
     K = 10
     for _ in range(K): out = ntrain.training_step(tm, opt, batch, as_tensors=True)   # the loop reads the terms once, after the last step
     torch.cuda.synchronize(); dt = (time.perf_counter() - t0) / K
-    print(f"  {'fused MFMA NerfMLP fwd+bwd' if fused else 'torch Linear NerfMLP      '}: {dt*1e3:8.2f} ms per step, {n/dt/1e3:8.1f} k rays/s, loss of the same deterministic step {same:.4f}, after 13 randomized steps {float(out['loss']):.4f}")
+    print(f"  {('fused MFMA fwd+bwd + wgrad  ' if wgrad else 'fused MFMA NerfMLP fwd+bwd ') if fused else 'torch Linear NerfMLP       '}: {dt*1e3:8.2f} ms per step, {n/dt/1e3:8.1f} k rays/s, loss of the same deterministic step {same:.4f}, after 13 randomized steps {float(out['loss']):.4f}")
     del tm, opt
     torch.cuda.empty_cache()
