@@ -229,6 +229,16 @@ typedef struct NlrOut {              /* renderings[-1] (render.py:219-284); any 
 size_t nlr_workspace_bytes(const NlrModel *m, uint32_t N);
 int nlr_render_rays(const NlrModel *m, const NlrRays *rays, uint32_t N, const NlrRenderCfg *cfg,
                     const NlrOut *out, void *workspace, size_t workspace_bytes, void *stream);
+/* LiDAR-only render: nlr_render_rays for a caller that reads no colour.  Depth, semantic, intensity, acc, distance_*, labels, points,
+ * packed and every per-level history field except the last level's rgb are written exactly as nlr_render_rays writes them (same
+ * bits); the direction encoding and the view MLP of the last level - 78 % of the NerfMLP's matrix work at the shipped shape - are
+ * not executed, so rays->viewdirs may be NULL.  out->rgb and the last level's history[].rgb must be NULL (NLR_ERR_INVALID, nothing
+ * is launched).  `packed` keeps its 7-float record; slots 3..5 (rgb) hold 0.0f.  Workspace: nlr_workspace_bytes, as for
+ * nlr_render_rays.  At NLR_PREC_FAST without per-sample history of the last level the NerfMLP runs as one kernel instance of its
+ * own (trunk + heads + in-kernel segment compositing, a weight tape without the view layers); every other configuration takes the
+ * kernels of nlr_mlp_level(rgb = NULL) + nlr_composite_level(rgb = NULL). */
+int nlr_render_lidar(const NlrModel *m, const NlrRays *rays, uint32_t N, const NlrRenderCfg *cfg,
+                     const NlrOut *out, void *workspace, size_t workspace_bytes, void *stream);
 
 /* Comma-separated names of the kernels the library launches, in NLR_K_* order (host only), so that
  * bench.py can match rocprofv3 --kernel-trace rows. */
@@ -262,6 +272,10 @@ const char *nlr_build_sha(void);
 #define NLR_DBG_SCATTER_LEVELS 4
 #define NLR_DBG_NO_SCATTER_CACHE 5
 #define NLR_DBG_RAY_GROUPS 6
+/*   NLR_DBG_LAST_ROUTE (key 7): not a switch but a read-back - how the last level of the most recent render call of this process ran:
+ *     1 full render, per-sample heads + nlr_composite_kernel; 2 full render, compositing-mode MLP kernel; 3 LiDAR-only render through
+ *     the kernels of nlr_mlp_level(rgb = NULL); 4 LiDAR-only render through the LiDAR-only compositing instance.  0 = none yet. */
+#define NLR_DBG_LAST_ROUTE 7
 int nlr_debug_set(uint32_t key, int value);
 int nlr_debug_get(uint32_t key);
 /* 1 when the fused kernels' fast level body covers this grid (see csrc/nlr_level_fast.h:nlr_level_fast_ok), 0 when the generic body
@@ -451,6 +465,12 @@ int nlr_objects_apply(const NlrObjects *o, const NlrRays *rays, const float *tdi
 int nlr_render_rays_dynamic(const NlrModel *m, const NlrObjects *o, const NlrRays *rays, const float *box_params, uint32_t n_obj,
                             uint32_t N, const NlrRenderCfg *cfg, const NlrOut *out, int32_t *const *winner, void *workspace,
                             size_t workspace_bytes, void *stream);
+/* nlr_render_rays_dynamic without colour (see nlr_render_lidar: same contract for out->rgb, history[].rgb, viewdirs and packed).  The
+ * object networks replace density and semantic only (nlr_objects_apply with rgb = NULL); the merge sits between the MLP and the
+ * compositing, so this path always takes the per-sample kernels. */
+int nlr_render_lidar_dynamic(const NlrModel *m, const NlrObjects *o, const NlrRays *rays, const float *box_params, uint32_t n_obj,
+                             uint32_t N, const NlrRenderCfg *cfg, const NlrOut *out, int32_t *const *winner, void *workspace,
+                             size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * (8) PropMLP density network for training (ZI/models.py:887-889,996-997 with disable_rgb = True):

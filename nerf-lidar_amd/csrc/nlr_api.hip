@@ -63,6 +63,8 @@ struct LevelModel {
     uint32_t prec = NLR_PREC_MIXED;
     void *tape = nullptr;
     uint32_t tape_chunks = 0;
+    void *tape_lidar = nullptr;  // LiDAR-only tile program [T | T] (NLR_PREC_FAST): trunk + heads of both halves, no view layers
+    uint32_t tape_lidar_chunks = 0;
     float rgb_premul = 1.0f, rgb_bias = 0.0f, rgb_padding = 0.001f;
     float *bias_all = nullptr;
     uint32_t bias_count = 0;
@@ -345,6 +347,15 @@ static int build_level(NlrModel *m, LevelModel &lv, const NlrMlpDesc &d, uint32_
     lv.tape_chunks = (uint32_t)(tb.bytes.size() / NLR_TAPE_CHUNK);
     tb.bytes.resize(tb.bytes.size() + 3 * NLR_TAPE_CHUNK, 0);  // slack: the kernel prefetches up to 3 chunks past the end
     if ((rc = dev_upload(m, tb.bytes.data(), tb.bytes.size(), &lv.tape))) return rc;
+    if (prec == NLR_PREC_FAST) {  // the LiDAR-only instances' tape (nlr_mlp_kernel.h, CM = 2): same fragments, same 3-chunk slack
+        TapeBuilder tl;
+        tl.bytes.insert(tl.bytes.end(), trunk.bytes.begin(), trunk.bytes.end());
+        tl.bytes.insert(tl.bytes.end(), trunk.bytes.begin(), trunk.bytes.end());
+        tl.pad_to_chunk();
+        lv.tape_lidar_chunks = (uint32_t)(tl.bytes.size() / NLR_TAPE_CHUNK);
+        tl.bytes.resize(tl.bytes.size() + 3 * NLR_TAPE_CHUNK, 0);
+        if ((rc = dev_upload(m, tl.bytes.data(), tl.bytes.size(), &lv.tape_lidar))) return rc;
+    }
     return NLR_OK;
 }
 
@@ -497,10 +508,12 @@ extern "C" size_t nlr_workspace_bytes(const NlrModel *m, uint32_t N) {
 
 // Run encode + MLP of one NerfMLP level (or the fused proposal kernel) for given tdist.
 // seg != NULL: compositing mode (rgb / sem / inten are not written; see nlr_mlp_kernel.h) - needs dnorm [N] scratch
+// lidar (with seg): the LiDAR-only compositing instance - no direction encoding, no view MLP, rays->viewdirs is not read
 static int run_mlp_level(const NlrModel *m, const LevelModel &lv, const NlrRays *rays, const float *tdist, uint32_t N,
                          uint32_t n, uint32_t mloops, const float *rand_deg, float *feat, float *raybias, float *density,
                          float *rgb, float *sem, float *inten, float *prop_feat, hipStream_t st, bool internal_feat = false,
-                         float *seg = nullptr, float *dnorm = nullptr, uint32_t ray_groups = 0, const uint32_t *votes = nullptr) {
+                         float *seg = nullptr, float *dnorm = nullptr, uint32_t ray_groups = 0, const uint32_t *votes = nullptr,
+                         bool lidar = false) {
     // features in the workspace (never seen by the caller) take the piece-major layout when the fast kernels apply
     const int piece_major = (internal_feat && !lv.is_prop && n <= 8 && lv.F % 4 == 0) ? 1 : 0;  // any level_dim in {1, 2, 4, 8}: nlr_feat_ptr
     CastParams cp;
@@ -517,7 +530,11 @@ static int run_mlp_level(const NlrModel *m, const LevelModel &lv, const NlrRays 
         ProfScope ps(&m->prof, NLR_K_ENCODE, st);
         if ((rc = nlr_launch_encode(cp, lv.gp, lv.re_weights, feat, piece_major, st))) return rc;
     }
-    if (rgb || seg) {
+    if (seg && lidar) {  // the per-ray pre-kernel of the LiDAR-only mode: |directions| alone
+        NLR_CHECK_ARG(lv.tape_lidar != nullptr, "NerfMLP: no LiDAR-only tape at this precision");
+        ProfScope ps(&m->prof, NLR_K_DIRBIAS, st);
+        if ((rc = nlr_launch_dnorm(rays->directions, N, dnorm, st))) return rc;
+    } else if (rgb || seg) {
         NLR_CHECK_ARG(rays->viewdirs != nullptr, "NerfMLP: viewdirs is NULL");
         DirEncParams dp;
         dp.viewdirs = rays->viewdirs;
@@ -557,6 +574,13 @@ static int run_mlp_level(const NlrModel *m, const LevelModel &lv, const NlrRays 
     P.rgb = seg ? seg : rgb;  // (compositing mode: non-NULL = run the view MLP; nothing is stored through it)
     P.sem = sem;
     P.inten = (lv.use_int && (inten || seg)) ? (seg ? seg : inten) : nullptr;  // (compositing mode: non-NULL = the records carry the intensity)
+    if (seg && lidar) {
+        P.lidar = 1;
+        P.tape = (const uint4 *)lv.tape_lidar;
+        P.tape_chunks = lv.tape_lidar_chunks;
+        P.enc = nullptr;
+        P.rgb = nullptr;
+    }
     ProfScope ps(&m->prof, NLR_K_MLP, st);
     return nlr_launch_mlp(P, lv.W, lv.WB, lv.HT, lv.prec, m->cus, st);
 }
@@ -592,10 +616,18 @@ struct DynScene {
     int32_t *const *winner;  // optional per-level owner maps
 };
 
+// lidar_only (nlr_render_lidar): nobody wants rgb.  The last level runs without direction encoding and view MLP - through the
+// LiDAR-only compositing instance of the MLP kernel where one exists (same conditions as `fuse`), else through the kernel's
+// rgb == NULL path and nlr_composite_level(rgb = NULL); every other output is what the full render writes.
 static int render_impl(const NlrModel *m, const NlrRays *rays, uint32_t N, const NlrRenderCfg *cfg, const NlrOut *out, void *workspace,
-                       size_t workspace_bytes, void *stream, const DynScene *dyn) {
+                       size_t workspace_bytes, void *stream, const DynScene *dyn, bool lidar_only) {
     NLR_CHECK_ARG(m && rays && cfg && out, "render_rays: NULL argument");
     NLR_CHECK_ARG(rays->origins && rays->directions && rays->near && rays->far && rays->radii, "render_rays: ray batch has NULL tensors");
+    if (lidar_only) {
+        NLR_CHECK_ARG(out->rgb == nullptr, "render_lidar: out->rgb must be NULL (a LiDAR-only render computes no colour)");
+        NLR_CHECK_ARG(out->history[m->num_levels - 1].rgb == nullptr,
+                      "render_lidar: history[%u].rgb must be NULL (a LiDAR-only render computes no colour)", m->num_levels - 1);
+    }
     if (N == 0) return NLR_OK;
     size_t need = nlr_workspace_bytes(m, N), obj_ws = 0;
     if (dyn) {
@@ -643,8 +675,10 @@ static int render_impl(const NlrModel *m, const NlrRays *rays, uint32_t N, const
         float *feat = nullptr, *rb = nullptr, *rgb = nullptr, *sem = nullptr, *inten = nullptr, *seg = nullptr, *dnorm = nullptr;
         // Compositing mode: nobody asked for the per-sample heads of the last level (ray_history), so the MLP kernel composites
         // inside its 32-sample segments and 24 floats per sample never go to HBM.
+        const bool lidar = lidar_only && last;
         const bool fuse = !dyn && last && !lv.is_prop && !ho.rgb && !ho.semantic && !ho.intensity && lv.gp.C == 4 && n <= 8 &&
-                          nlr_mlp_can_composite(lv.W, lv.WB, lv.HT, lv.prec, lv.F, S, lv.K, lv.use_int, (uint64_t)N * S);
+                          nlr_mlp_can_composite(lv.W, lv.WB, lv.HT, lv.prec, lv.F, S, lv.K, lv.use_int, (uint64_t)N * S, lidar ? 2 : 1);
+        if (last) (void)nlr_debug_set(NLR_DBG_LAST_ROUTE, (lidar ? 2 : 0) + (fuse ? 1 : 0) + 1);
         if (!lv.is_prop) {
             feat = c.take((size_t)N * S * lv.F + 256);
             rb = c.take((size_t)N * 32);
@@ -652,7 +686,7 @@ static int render_impl(const NlrModel *m, const NlrRays *rays, uint32_t N, const
                 dnorm = c.take((size_t)N);
                 seg = c.take((size_t)N * S);
             } else {
-                rgb = ho.rgb ? ho.rgb : c.take((size_t)N * S * 3);
+                rgb = lidar ? nullptr : (ho.rgb ? ho.rgb : c.take((size_t)N * S * 3));
                 sem = lv.K ? (ho.semantic ? ho.semantic : c.take((size_t)N * S * lv.K)) : nullptr;
                 inten = lv.use_int ? (ho.intensity ? ho.intensity : c.take((size_t)N * S)) : nullptr;
             }
@@ -664,7 +698,7 @@ static int render_impl(const NlrModel *m, const NlrRays *rays, uint32_t N, const
         if (groups == 2u && n > 8) groups = 0u;  // (the sample-parallel kernels of sample_n > 8 have one order)
         if (groups == 2u && (rc = nlr_launch_ray_vote(tdist, N, S, votes + l, st))) return rc;
         rc = run_mlp_level(m, lv, rays, tdist, N, n, mloops, cfg->rand_deg[l], feat, rb, density, rgb, sem, inten, nullptr, st, true, seg,
-                           dnorm, groups, votes + l);
+                           dnorm, groups, votes + l, lidar);
         if (rc) return rc;
         if (dyn) {  // (the object networks have no intensity head: DynamicModel refuses use_intensity, like the reference's merge)
             rc = nlr_objects_apply_impl(dyn->objs, rays, tdist, dyn->box_params, N, S, dyn->n_obj, density, rgb, sem, lv.K,
@@ -675,10 +709,12 @@ static int render_impl(const NlrModel *m, const NlrRays *rays, uint32_t N, const
             ProfScope ps(&m->prof, NLR_K_COMPOSITE, st);
             if (fuse)
                 rc = nlr_composite_segments(density, tdist, rays->directions, seg, lv.K, lv.use_int ? 1 : 0, rays->far, rays->origins, N, S,
-                                            (int)m->opaque, m->bg, (int)cfg->compute_extras, cfg->scale_factor, weights, out, ho.depth, st);
+                                            (int)m->opaque, m->bg, (int)cfg->compute_extras, cfg->scale_factor, weights, out, ho.depth, st,
+                                            lidar);
             else if (last)
-                rc = nlr_composite_level(density, tdist, rays->directions, rgb, sem, inten, rays->far, rays->origins, N, S, lv.K,
-                                         (int)m->opaque, m->bg, (int)cfg->compute_extras, cfg->scale_factor, weights, out, ho.depth, st);
+                rc = nlr_composite_level_impl(density, tdist, rays->directions, rgb, sem, inten, rays->far, rays->origins, N, S, lv.K,
+                                              (int)m->opaque, m->bg, (int)cfg->compute_extras, cfg->scale_factor, weights, out, ho.depth,
+                                              st, lidar);
             else {  // a level before the last: weights for the next resampling, its depth, and (on request) the rest of its rendering
                 NlrOut lo;
                 memset(&lo, 0, sizeof(lo));
@@ -704,15 +740,32 @@ static int render_impl(const NlrModel *m, const NlrRays *rays, uint32_t N, const
 
 extern "C" int nlr_render_rays(const NlrModel *m, const NlrRays *rays, uint32_t N, const NlrRenderCfg *cfg, const NlrOut *out,
                                void *workspace, size_t workspace_bytes, void *stream) {
-    return render_impl(m, rays, N, cfg, out, workspace, workspace_bytes, stream, nullptr);
+    return render_impl(m, rays, N, cfg, out, workspace, workspace_bytes, stream, nullptr, false);
+}
+
+extern "C" int nlr_render_lidar(const NlrModel *m, const NlrRays *rays, uint32_t N, const NlrRenderCfg *cfg, const NlrOut *out,
+                                void *workspace, size_t workspace_bytes, void *stream) {
+    return render_impl(m, rays, N, cfg, out, workspace, workspace_bytes, stream, nullptr, true);
+}
+
+static int render_dynamic(const NlrModel *m, const NlrObjects *o, const NlrRays *rays, const float *box_params, uint32_t n_obj, uint32_t N,
+                          const NlrRenderCfg *cfg, const NlrOut *out, int32_t *const *winner, void *workspace, size_t workspace_bytes,
+                          void *stream, bool lidar_only) {
+    NLR_CHECK_ARG(m && o && (box_params || n_obj == 0), "render_rays_dynamic: NULL argument");
+    for (uint32_t l = 0; l < m->num_levels; ++l)
+        NLR_CHECK_ARG(!m->lv[l].use_int, "render_rays_dynamic: the object networks have no intensity head (ZI/models.py:469 assigns None)");
+    DynScene d{o, box_params, n_obj, winner};
+    return render_impl(m, rays, N, cfg, out, workspace, workspace_bytes, stream, &d, lidar_only);
 }
 
 extern "C" int nlr_render_rays_dynamic(const NlrModel *m, const NlrObjects *o, const NlrRays *rays, const float *box_params, uint32_t n_obj,
                                        uint32_t N, const NlrRenderCfg *cfg, const NlrOut *out, int32_t *const *winner, void *workspace,
                                        size_t workspace_bytes, void *stream) {
-    NLR_CHECK_ARG(m && o && (box_params || n_obj == 0), "render_rays_dynamic: NULL argument");
-    for (uint32_t l = 0; l < m->num_levels; ++l)
-        NLR_CHECK_ARG(!m->lv[l].use_int, "render_rays_dynamic: the object networks have no intensity head (ZI/models.py:469 assigns None)");
-    DynScene d{o, box_params, n_obj, winner};
-    return render_impl(m, rays, N, cfg, out, workspace, workspace_bytes, stream, &d);
+    return render_dynamic(m, o, rays, box_params, n_obj, N, cfg, out, winner, workspace, workspace_bytes, stream, false);
+}
+
+extern "C" int nlr_render_lidar_dynamic(const NlrModel *m, const NlrObjects *o, const NlrRays *rays, const float *box_params, uint32_t n_obj,
+                                        uint32_t N, const NlrRenderCfg *cfg, const NlrOut *out, int32_t *const *winner, void *workspace,
+                                        size_t workspace_bytes, void *stream) {
+    return render_dynamic(m, o, rays, box_params, n_obj, N, cfg, out, winner, workspace, workspace_bytes, stream, true);
 }

@@ -169,7 +169,7 @@ __global__ void __launch_bounds__(256) nlr_composite_kernel(CompositeParams P) {
             pk[1] = (P.inten || (P.seg && P.seg_int)) ? sint : 0.0f;
             pk[2] = acc;
 #pragma unroll
-            for (int c = 0; c < 3; ++c) pk[3 + c] = srgb[c] + bgw * P.bg;
+            for (int c = 0; c < 3; ++c) pk[3 + c] = P.no_rgb ? 0.0f : srgb[c] + bgw * P.bg;
             pk[6] = (float)label;
         }
     }
@@ -239,11 +239,10 @@ int nlr_launch_composite(const CompositeParams &P, hipStream_t st) {
     return NLR_OK;
 }
 
-extern "C" int nlr_composite_level(const float *density, const float *tdist, const float *directions, const float *rgb,
-                                   const float *semantic, const float *intensity, const float *far, const float *origins,
-                                   uint32_t N, uint32_t S, uint32_t class_num, int opaque_background, float bg,
-                                   int compute_extras, float scale_factor, float *weights, const NlrOut *out,
-                                   float *level_depth, void *stream) {
+int nlr_composite_level_impl(const float *density, const float *tdist, const float *directions, const float *rgb, const float *semantic,
+                             const float *intensity, const float *far, const float *origins, uint32_t N, uint32_t S, uint32_t class_num,
+                             int opaque_background, float bg, int compute_extras, float scale_factor, float *weights, const NlrOut *out,
+                             float *level_depth, hipStream_t st, bool no_rgb) {
     if (N == 0) return NLR_OK;
     CompositeParams P;
     memset(&P, 0, sizeof(P));
@@ -264,6 +263,7 @@ extern "C" int nlr_composite_level(const float *density, const float *tdist, con
     P.scale_factor = scale_factor > 0 ? scale_factor : 1.0f;
     P.weights = weights;
     P.level_depth = level_depth;
+    P.no_rgb = no_rgb ? 1 : 0;
     if (out) {
         P.o_rgb = out->rgb;
         P.o_depth = out->depth;
@@ -283,15 +283,24 @@ extern "C" int nlr_composite_level(const float *density, const float *tdist, con
             NLR_CHECK_ARG(out->packed_w > 0 && (uint64_t)out->packed_h * out->packed_w == N,
                           "composite: packed tile %u x %u does not match N = %u rays", out->packed_h, out->packed_w, N);
     }
-    return nlr_launch_composite(P, (hipStream_t)stream);
+    return nlr_launch_composite(P, st);
+}
+
+extern "C" int nlr_composite_level(const float *density, const float *tdist, const float *directions, const float *rgb,
+                                   const float *semantic, const float *intensity, const float *far, const float *origins,
+                                   uint32_t N, uint32_t S, uint32_t class_num, int opaque_background, float bg,
+                                   int compute_extras, float scale_factor, float *weights, const NlrOut *out,
+                                   float *level_depth, void *stream) {
+    return nlr_composite_level_impl(density, tdist, directions, rgb, semantic, intensity, far, origins, N, S, class_num, opaque_background,
+                                    bg, compute_extras, scale_factor, weights, out, level_depth, (hipStream_t)stream, false);
 }
 
 // Compositing-mode tail of nlr_render_rays: weights / depth / acc / percentiles from density and tdist as above, the per-ray rgb /
-// semantic / intensity from the segment records nlr_mlp_kernel<..., COMP = true> wrote (nlr_mlp_kernel.h).
+// semantic / intensity from the segment records nlr_mlp_kernel<..., CM = 1 or 2> wrote (nlr_mlp_kernel.h).
 int nlr_composite_segments(const float *density, const float *tdist, const float *directions, const float *seg, uint32_t class_num,
                            int has_intensity, const float *far, const float *origins, uint32_t N, uint32_t S, int opaque_background,
                            float bg, int compute_extras, float scale_factor, float *weights, const NlrOut *out, float *level_depth,
-                           hipStream_t st) {
+                           hipStream_t st, bool no_rgb) {
     if (N == 0) return NLR_OK;
     NLR_CHECK_ARG(seg && out, "composite_segments: NULL argument");
     CompositeParams P;
@@ -301,6 +310,7 @@ int nlr_composite_segments(const float *density, const float *tdist, const float
     P.dirs = directions;
     P.seg = seg;
     P.seg_int = has_intensity ? 1 : 0;
+    P.no_rgb = no_rgb ? 1 : 0;
     P.far = far;
     P.origins = origins;
     P.N = N;

@@ -28,6 +28,7 @@ struct CompositeParams {
     float *o_rgb, *o_depth, *o_sem, *o_int, *o_acc, *o_dmean, *o_dmed, *o_p5, *o_p95, *o_points, *level_depth;
     int32_t *o_labels;
     const float *seg;        // (instead of rgb / sem / inten) segment records of the compositing-mode MLP kernel, int_row = K
+    uint32_t no_rgb;         // LiDAR-only render: nobody composites a colour, slots 3..5 of a packed record hold 0
     uint32_t seg_int;        // the records carry the intensity in slot K
     float *o_packed;         // [N, 7] records (see NlrOut.packed)
     uint32_t pk_h, pk_w;
@@ -63,6 +64,9 @@ struct MlpParams {
     const float *dnorm;     // [N] |directions|
     float *seg;             // [M / 32, 32]
     uint32_t opaque;
+    // LiDAR-only compositing mode (nlr_mlp_kernel.h, CM = 2): no view MLP; `tape` / `tape_chunks` are the level's LiDAR tape,
+    // `enc` and `rgb` are not read
+    uint32_t lidar;
 };
 
 struct DirEncParams {
@@ -72,6 +76,8 @@ struct DirEncParams {
     float *out;             // [N, 32]
     float *dnorm;           // [N] |dirs| or null
 };
+// |directions| alone (the LiDAR-only render runs no direction encoding): the expression of nlr_direnc_kernel
+int nlr_launch_dnorm(const float *dirs, uint32_t N, float *dnorm, hipStream_t st);
 
 int nlr_launch_resample(const float *prev_sdist, const float *prev_weights, uint32_t n_prev, float dilation, float anneal,
                         float pad, uint32_t S, const float *u_dev, const float *jitter, float max_jitter, const float *near,
@@ -85,10 +91,16 @@ int nlr_launch_prop(const CastParams &cp, const GridParams &gp, const float *w1,
                     float density_bias, int re_weights, float *density, float *feat_out, hipStream_t st);
 int nlr_launch_direnc(const DirEncParams &P, hipStream_t st);
 int nlr_launch_mlp(const MlpParams &P, uint32_t W, uint32_t WB, uint32_t HT, uint32_t prec, uint32_t cus, hipStream_t st);
-// can nlr_launch_mlp run this level in compositing mode (MlpParams.seg)?
-bool nlr_mlp_can_composite(uint32_t W, uint32_t WB, uint32_t HT, uint32_t prec, uint32_t F, uint32_t S, uint32_t K, bool use_int, uint64_t M);
+// can nlr_launch_mlp run this level in compositing mode (MlpParams.seg)?  mode 1: with the view MLP, 2: LiDAR-only (MlpParams.lidar)
+bool nlr_mlp_can_composite(uint32_t W, uint32_t WB, uint32_t HT, uint32_t prec, uint32_t F, uint32_t S, uint32_t K, bool use_int, uint64_t M,
+                           uint32_t mode = 1);
 int nlr_launch_composite(const CompositeParams &P, hipStream_t st);
 int nlr_composite_segments(const float *density, const float *tdist, const float *directions, const float *seg, uint32_t class_num,
                            int has_intensity, const float *far, const float *origins, uint32_t N, uint32_t S, int opaque_background,
                            float bg, int compute_extras, float scale_factor, float *weights, const NlrOut *out, float *level_depth,
-                           hipStream_t st);
+                           hipStream_t st, bool no_rgb = false);
+// nlr_composite_level with the choice of a LiDAR-only render (CompositeParams.no_rgb)
+int nlr_composite_level_impl(const float *density, const float *tdist, const float *directions, const float *rgb, const float *semantic,
+                             const float *intensity, const float *far, const float *origins, uint32_t N, uint32_t S, uint32_t class_num,
+                             int opaque_background, float bg, int compute_extras, float scale_factor, float *weights, const NlrOut *out,
+                             float *level_depth, hipStream_t st, bool no_rgb);

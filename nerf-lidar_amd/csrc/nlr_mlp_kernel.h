@@ -484,8 +484,16 @@ extern __device__ unsigned long long nlr_stamp_buf[1024 * NLR_NSTAMP];  // defin
 //   writes, instead of 24 floats per SAMPLE (class probabilities, intensity, rgb), one 32-float record per SEGMENT:
 //   [0,K) sum w' p_c, [K] sum w' intensity, [29,32) sum w' rgb.  nlr_composite_kernel scales each record by the transmittance at
 //   its segment start.  All of it is VALU work issued piece by piece behind the MFMAs of view layers 0 and 1.
-template <int WT, int BW, int FT, int HT, int PREC, bool COMP>
+// CM: 0 = per-sample outputs, 1 = COMP, 2 = LiDAR-only compositing (LIDAR): trunk + heads + segment records and NO view MLP, for
+//   renders whose caller wants no rgb (nlr_render_lidar).  The tile's program is [T | T] on a tape of its own (MlpParams.tape is the
+//   level's LiDAR tape: the view layers' fragments never enter LDS), the direction encoding is neither staged nor read, and slots
+//   [29,32) of every record hold 0.  Trunk, heads and the 35 compositing pieces are the code of mode 1, so density and records
+//   [0,K] are the same bits.  The pieces run serially behind each half's heads (there is no view layer 0 to hide them); the next
+//   tile's inputs are requested once both halves have read theirs and land under the second half's trunk.  WT does not enter.
+template <int WT, int BW, int FT, int HT, int PREC, int CM>
 __global__ void __launch_bounds__(256, 1) nlr_mlp_kernel(MlpParams P) {
+    constexpr bool COMP = CM != 0, LIDAR = CM == 2;
+    static_assert(!LIDAR || PREC == NLR_PREC_FAST, "the LiDAR-only instances exist for NLR_PREC_FAST");
     __shared__ __align__(16) uint4 lds_tape[NLR_NBUF * NLR_CHUNK_SLOTS];
     __shared__ __align__(16) float lds_bias[NLR_BIAS_MAX];
     __shared__ __align__(16) float lds_stage[4 * NLR_STAGE_FLOATS];
@@ -509,7 +517,10 @@ __global__ void __launch_bounds__(256, 1) nlr_mlp_kernel(MlpParams P) {
     constexpr int FR_HL = WT * (WT * VK) * 2, FR_RGB = (WT * VK);
     static_assert(FR_HL % NLR_CHUNK_FRAGS == 0, "hidden view layers must cover whole chunks (width 128 or 256)");
     // bf16 view MLP: [T V0 V1 | T V0 V1 | hidden x (depth-2) | RGB];  f32 view MLP: [T V0 V1 | hidden | RGB] once per half
-    constexpr int FR_HALF = FR_T + FR_V0 + FR_V1;
+    constexpr int FR_HALF = LIDAR ? FR_T : FR_T + FR_V0 + FR_V1;
+    // (LIDAR: a signal() of the tape, which waits for this wave's loads, lies between the request of the next tile's inputs and
+    // the end of the second half)
+    static_assert(!LIDAR || FR_T >= 2 * NLR_CHUNK_FRAGS, "LiDAR-only: the second half must span a whole chunk");
     constexpr int F_HID = VIEW_F32 ? FR_HALF : 2 * FR_HALF;
     constexpr int F_END = F_HID + FR_RGB;                 // (+ hidden layers: whole chunks)
 
@@ -523,7 +534,7 @@ __global__ void __launch_bounds__(256, 1) nlr_mlp_kernel(MlpParams P) {
     tp.sig = &lds_sig;
     tp.sig_addr = (uint32_t)(uintptr_t)(nlr_lptr)&lds_sig;
     // without the view MLP (density / semantic / intensity only: not a hot path) the view layers' fragments are stepped over
-    tp.total = P.rgb ? (int)P.tape_chunks : nlr_ceil_div(VIEW_F32 ? FR_T : F_HID, NLR_CHUNK_FRAGS);
+    tp.total = (LIDAR || P.rgb) ? (int)P.tape_chunks : nlr_ceil_div(VIEW_F32 ? FR_T : F_HID, NLR_CHUNK_FRAGS);
     tp.tid = threadIdx.x;
     tp.lane = lane;
     tp.prologue();  // ends with __syncthreads(): the bias block is visible too
@@ -538,7 +549,7 @@ __global__ void __launch_bounds__(256, 1) nlr_mlp_kernel(MlpParams P) {
     // buffer for the last, partial tile (the samples past M are computed and dropped).
     // (COMP: required, checked by the host.  The feature buffer is followed by >= 1 KiB of workspace: a window that starts inside
     // it may run past its end when M < 64; those samples are computed and dropped.)
-    const bool staged = P.feat_piece_major && P.F <= 4 * NLR_STAGE_PIECES && P.rgb != nullptr;
+    const bool staged = P.feat_piece_major && P.F <= 4 * NLR_STAGE_PIECES && (LIDAR || P.rgb != nullptr);
     float *stg = lds_stage + wave * NLR_STAGE_FLOATS;
     const uint32_t stg_lds = (uint32_t)(uintptr_t)(nlr_lptr)lds_stage + __builtin_amdgcn_readfirstlane(wave) * (NLR_STAGE_FLOATS * 4u);  // uniform
     auto stage_base = [&](uint32_t t) {
@@ -558,7 +569,7 @@ __global__ void __launch_bounds__(256, 1) nlr_mlp_kernel(MlpParams P) {
                          : [v] "v"(voff), [l] "s"(l0 + p * 1024u), [g] "s"(g)
                          : "memory");
         }
-        {  // direction-encoding rows: lane i < 32 fetches the 16 bytes [n-tile i>>3][row block (i>>2)&1][q = i&3]
+        if constexpr (!LIDAR) {  // direction-encoding rows: lane i < 32 fetches the 16 bytes [n-tile i>>3][row block (i>>2)&1][q = i&3]
             // (rows go by the tile's real sample numbers, not by the pulled-back feature window)
             const uint32_t s0 = t * NLR_TILE + wave * 64 + 16u * ((uint32_t)lane >> 3 & 3u);
             const uint32_t ray = (s0 < P.M ? s0 : P.M - 1) / P.S;
@@ -646,7 +657,8 @@ __global__ void __launch_bounds__(256, 1) nlr_mlp_kernel(MlpParams P) {
 #pragma unroll
             for (int jb = 0; jb < 2; ++jb) {
                 f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
-                if (COMP || staged) v = *reinterpret_cast<const f32x4 *>(stg + NLR_STAGE_ENC + (((2 * h + n) * 2 + jb) * 4 + q) * 4);
+                if (LIDAR) {  // (no view MLP: nothing reads the unit)
+                } else if (COMP || staged) v = *reinterpret_cast<const f32x4 *>(stg + NLR_STAGE_ENC + (((2 * h + n) * 2 + jb) * 4 + q) * 4);
                 else if (P.rgb) v = *reinterpret_cast<const f32x4 *>(P.enc + (size_t)(sc / P.S) * 32 + 16 * jb + 4 * q);
                 encu.a[jb][n] = v;
             }
@@ -711,6 +723,17 @@ __global__ void __launch_bounds__(256, 1) nlr_mlp_kernel(MlpParams P) {
         float acc[2][4];   // [row block][r]
     };
     float wpall[4] = {0.0f, 0.0f, 0.0f, 0.0f};  // segment-local weight of this lane's sample in each column tile (kept for the rgb sums)
+    // LIDAR: (t_k+1 - t_k) |d| and the last-sample flag of this lane's sample in each column tile, read from the staging area at the
+    // start of the tile so that the next tile's inputs can be requested before the compositing pieces of the second half
+    float tdd[4] = {0.0f, 0.0f, 0.0f, 0.0f}, tdf[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if constexpr (LIDAR) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const float *td = stg + NLR_STAGE_TD + 16 * g + col;
+            tdd[g] = (td[64] - td[0]) * td[128];
+            tdf[g] = td[192];
+        }
+    }
     constexpr int NHP = 35;
     auto head_piece = [&](auto hh, auto ii, HeadSt &st) {
         constexpr int h = decltype(hh)::value, I = decltype(ii)::value;
@@ -724,8 +747,8 @@ __global__ void __launch_bounds__(256, 1) nlr_mlp_kernel(MlpParams P) {
             const uint32_t smp = base + g * 16 + col;
             if (q == 0 && smp < P.M) P.density[smp] = sp;
             const float *td = stg + NLR_STAGE_TD + 16 * g + col;  // staged t_k, t_k+1, |d|, last-sample flag of this lane's sample
-            float a = sp * ((td[64] - td[0]) * td[128]);
-            if (td[192] != 0.0f) a = INFINITY;  // opaque background: infinitely wide last interval
+            float a = sp * (LIDAR ? tdd[g] : (td[64] - td[0]) * td[128]);
+            if ((LIDAR ? tdf[g] : td[192]) != 0.0f) a = INFINITY;  // opaque background: infinitely wide last interval
             st.a[n] = a;
         } else if constexpr (I == 4) {  // exclusive prefix of sigma*delta inside the segment (16-lane rows, then across the 2 tiles)
             const float i0 = nlr_row_incl_scan(st.a[0]);
@@ -793,6 +816,10 @@ __global__ void __launch_bounds__(256, 1) nlr_mlp_kernel(MlpParams P) {
             constexpr int h = decltype(hh)::value;
             constexpr int F0 = h * FR_HALF;
             load_inputs(hh, fin, encu[h]);
+            if constexpr (LIDAR && h == 1) {  // every staged input of this tile is in registers: request the next tile's
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                if (tile + gridDim.x < ntiles) stage_issue(tile + gridDim.x);
+            }
             float raw[2] = {0.0f, 0.0f};
             Unit<2> lo;
 #pragma unroll
@@ -924,6 +951,24 @@ __global__ void __launch_bounds__(256, 1) nlr_mlp_kernel(MlpParams P) {
         };
         Unit<2> hlo;
         float hraw[2] = {0.0f, 0.0f};
+        if constexpr (LIDAR) {
+            // ---- LiDAR-only: per half trunk + heads, then the half's segment record (slots [29,32) are rows 29..31 of the heads'
+            // output unit, which no class or intensity row reaches: head_piece writes 0 there)
+            auto half = [&](auto hh) {
+                trunk(hh, hlo, hraw);
+                HeadSt hst;
+                hst.lo = hlo;
+                hst.raw[0] = hraw[0];
+                hst.raw[1] = hraw[1];
+                nlr_pend<0, NHP>([&](auto ii) {
+                    head_piece(hh, ii, hst);
+                    __builtin_amdgcn_sched_barrier(0);
+                });
+            };
+            half(ic<0>{});
+            half(ic<1>{});
+            nlr_pad<(2 * FR_T) % NLR_CHUNK_FRAGS>(tp);
+        } else {
         if (P.rgb == nullptr) {  // density / semantic / intensity only (uniform for the whole grid)
             trunk(ic<0>{}, hlo, hraw);
             nlr_skip<FR_T, FR_V0 + FR_V1>(tp);
@@ -1085,6 +1130,7 @@ __global__ void __launch_bounds__(256, 1) nlr_mlp_kernel(MlpParams P) {
             dbg[23] = __builtin_amdgcn_s_memrealtime();
         }
 #endif
+        }  // !LIDAR
     } else {
         // =================================================== exact-f32 chain: each half runs the whole tape ======================
         auto pass = [&](auto hh) {

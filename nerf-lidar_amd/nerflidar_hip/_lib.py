@@ -87,9 +87,12 @@ EXPORTS = ["nlr_last_error", "nlr_version", "nlr_build_sha", "nlr_debug_set", "n
            "nlr_render_rays_dynamic", "nlr_prop_mlp_forward", "nlr_prop_mlp_backward", "nlr_encode_features_forward",
            "nlr_encode_features_backward", "nlr_encode_features_backward_ws", "nlr_grid_encode_backward_ws", "nlr_grid_backward_workspace_bytes",
            "nlr_train_plan_create", "nlr_train_plan_destroy", "nlr_train_act_width", "nlr_train_param_layout", "nlr_train_pack",
-           "nlr_mlp_train_forward", "nlr_mlp_train_backward", "nlr_mlp_train_wgrad_workspace_bytes", "nlr_mlp_train_wgrad"]
+           "nlr_mlp_train_forward", "nlr_mlp_train_backward", "nlr_mlp_train_wgrad_workspace_bytes", "nlr_mlp_train_wgrad",
+           "nlr_render_lidar", "nlr_render_lidar_dynamic"]
 NLR_K_COUNT = 6
 DBG_FORCE_GENERIC, DBG_MLP_WORKGROUPS, DBG_BINNED_C4, DBG_NO_XPAIR_SCATTER, DBG_SCATTER_LEVELS, DBG_NO_SCATTER_CACHE, DBG_RAY_GROUPS = 0, 1, 2, 3, 4, 5, 6
+DBG_LAST_ROUTE = 7  # read-back (nlr_debug_get): how the last level of the most recent render ran
+ROUTE_FULL, ROUTE_FULL_FUSED, ROUTE_LIDAR, ROUTE_LIDAR_FUSED = 1, 2, 3, 4
 
 
 def lib():
@@ -129,6 +132,7 @@ def lib():
                                                C.c_uint32, C.c_uint32, C.c_int, c_fp]
         L.nlr_render_rays.argtypes = [c_fp, C.POINTER(NlrRays), C.c_uint32, C.POINTER(NlrRenderCfg), C.POINTER(NlrOut),
                                       c_fp, C.c_size_t, c_fp]
+        L.nlr_render_lidar.argtypes = L.nlr_render_rays.argtypes
         L.nlr_resample_level.argtypes = [c_fp, c_fp, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_uint32, c_fp, c_fp,
                                          c_fp, C.c_float, C.c_uint32, c_fp, c_fp, c_fp]
         L.nlr_mlp_level.argtypes = [c_fp, C.c_uint32, C.POINTER(NlrRays), c_fp, C.c_uint32, C.c_uint32, C.c_uint32, c_fp,
@@ -157,6 +161,7 @@ def lib():
                                         C.c_uint32, c_fp, c_fp, C.c_size_t, c_fp]
         L.nlr_render_rays_dynamic.argtypes = [c_fp, c_fp, C.POINTER(NlrRays), c_fp, C.c_uint32, C.c_uint32, C.POINTER(NlrRenderCfg),
                                               C.POINTER(NlrOut), C.POINTER(c_fp), c_fp, C.c_size_t, c_fp]
+        L.nlr_render_lidar_dynamic.argtypes = L.nlr_render_rays_dynamic.argtypes
         L.nlr_prop_mlp_forward.argtypes = [c_fp] * 5 + [C.c_uint32, C.c_uint32, c_fp, c_fp]
         L.nlr_prop_mlp_backward.argtypes = [c_fp] * 6 + [C.c_uint32, C.c_uint32] + [c_fp] * 6
         L.nlr_encode_features_forward.argtypes = [C.POINTER(NlrRays), c_fp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, c_fp,

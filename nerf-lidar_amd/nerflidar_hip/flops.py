@@ -10,6 +10,24 @@ def macs_per_sample(cfg: MLPConfig) -> int:
     return sum(o * i for _, (o, i), _ in mlp_param_shapes(cfg))
 
 
+def lidar_macs_per_sample(cfg: MLPConfig) -> int:
+    """MACs a LiDAR-only render executes per sample of this MLP: density trunk and the semantic / intensity heads; the view MLP
+    (lin_second_stage_*) and the rgb layer are not run."""
+    return sum(o * i for name, (o, i), _ in mlp_param_shapes(cfg) if not (name.startswith("lin_second_stage_") or name == "rgb_layer"))
+
+
+def lidar_flops_per_ray(mc: ModelConfig) -> int:
+    """`flops_per_ray` of `render_rays(lidar_only=True)`: EXECUTED work only.  A rate quoted for the LiDAR-only mode uses this
+    count - the skipped view MLP is not work done."""
+    s = mc.level_samples()
+    total = 0
+    for li in range(mc.num_levels):
+        last = li == mc.num_levels - 1
+        cfg = mc.nerf_mlp if last else mc.prop_cfg(li)
+        total += s[li] * (lidar_macs_per_sample(cfg) if last else macs_per_sample(cfg))
+    return 2 * total
+
+
 def flops_per_ray(mc: ModelConfig) -> int:
     s = mc.level_samples()
     total = 0

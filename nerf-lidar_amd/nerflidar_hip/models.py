@@ -158,18 +158,23 @@ class Model:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         return self._ws
 
-    def _render_call(self, rays, n: int, cfg, out) -> None:
-        """The library call of `render_rays` (DynamicModel substitutes nlr_render_rays_dynamic)."""
+    def _render_call(self, rays, n: int, cfg, out, lidar_only: bool = False) -> None:
+        """The library call of `render_rays` (DynamicModel substitutes nlr_render_rays_dynamic / nlr_render_lidar_dynamic)."""
         ws = self._workspace(n)
-        rc = _lib.lib().nlr_render_rays(self._handle, C.byref(rays), n, C.byref(cfg), C.byref(out), _lib.ptr(ws), ws.numel(),
-                                        _lib.current_stream())
-        _lib.check(rc, "nlr_render_rays")
+        name = "nlr_render_lidar" if lidar_only else "nlr_render_rays"
+        rc = getattr(_lib.lib(), name)(self._handle, C.byref(rays), n, C.byref(cfg), C.byref(out), _lib.ptr(ws), ws.numel(),
+                                       _lib.current_stream())
+        _lib.check(rc, name)
 
     def render_rays(self, batch: Dict[str, torch.Tensor], train_frac: float = 1.0, compute_extras: bool = True,
                     sample_n: int = 7, sample_m: int = 3, want_history: bool = False, scale_factor: float = 0.0,
                     rand_jitter: Optional[List[torch.Tensor]] = None, rand_deg: Optional[List[torch.Tensor]] = None,
-                    packed: Optional[torch.Tensor] = None):
+                    packed: Optional[torch.Tensor] = None, lidar_only: bool = False):
         """One `nlr_render_rays` call.  Returns (rendering dict of the last level, list of per-level dicts).
+
+        lidar_only: one `nlr_render_lidar` call instead - for a caller that reads depth / semantic / intensity / labels / points and
+        no colour.  Every other output is the same bits; the direction encoding and the view MLP are not run, `batch["viewdirs"]`
+        is not needed, the dicts carry no "rgb" and slots 3..5 of a `packed` record hold 0.
 
         packed: optional float32 CUDA buffer for the 7-float-per-ray records (depth, intensity, acc, rgb, label) the
         compositing kernel writes besides the named outputs: shape [n, 7] (ray order) or [wp, H, 7] with wp * H == n
@@ -179,6 +184,8 @@ class Model:
         keep = []
         for k in _RAY_KEYS:
             t = batch.get(k)
+            if t is None and lidar_only and k == "viewdirs":
+                continue  # (NlrRays.viewdirs stays NULL)
             if t is None:
                 raise RuntimeError(f"batch['{k}'] is missing")
             if not t.is_cuda:
@@ -190,7 +197,7 @@ class Model:
         K = self.mc.nerf_mlp.class_num if self.config.use_semantic else 0
         new = lambda *shape, dtype=f32: torch.empty(*shape, device=dev, dtype=dtype)
         out = _lib.NlrOut()
-        r: Dict[str, torch.Tensor] = {"rgb": new(n, 3), "depth": new(n)}
+        r: Dict[str, torch.Tensor] = {"depth": new(n)} if lidar_only else {"rgb": new(n, 3), "depth": new(n)}
         if K:
             r["semantic"] = new(n, K)
         if self.config.use_intensity:
@@ -223,7 +230,8 @@ class Model:
                         for k in ("distance_mean", "distance_median", "distance_percentile_5", "distance_percentile_95"):
                             h["r_" + k] = new(n)
                 if li == len(samples) - 1:  # the library writes per-sample heads channel-/class-major
-                    h["rgb"] = new(3, n, S)
+                    if not lidar_only:
+                        h["rgb"] = new(3, n, S)
                     if K:
                         h["semantic"] = new(K, n, S)
                     if self.config.use_intensity:
@@ -247,10 +255,11 @@ class Model:
                 keep.append(t)
                 cfg.rand_deg[li] = t.data_ptr()
         with torch.cuda.device(dev):
-            self._render_call(rays, n, cfg, out)
+            self._render_call(rays, n, cfg, out, lidar_only)
         if want_history:  # back to the reference's [N, S, C] layout (ZI/models.py:553-557)
             last = hist[-1]
-            last["rgb"] = last["rgb"].permute(1, 2, 0)
+            if "rgb" in last:
+                last["rgb"] = last["rgb"].permute(1, 2, 0)
             if "semantic" in last:
                 last["semantic"] = last["semantic"].permute(1, 2, 0)
         return r, hist
@@ -264,6 +273,8 @@ class Model:
         per-ray jitter (stepfun.py:216) and per-multisample rotation (render.py:150) on the device.
         Every level's `renderings` entry carries the reference's keys (rgb, depth, acc, distance_* with compute_extras,
         ray_* bundles; semantic / intensity on the last level only, models.py:514-531).
+        This is the reference's contract, rgb included: the LiDAR-only mode is an option of `render_rays` alone, and `render_image`,
+        which calls this, does not have it either.
         """
         n = batch["origins"].shape[0]
         samples = self.mc.level_samples()
@@ -301,7 +312,8 @@ class CapturedRender:
     A LiDAR simulator renders sweep after sweep from ray buffers it refills in place, so the launch sequence never changes; replaying
     it costs one graph launch instead of ~10 kernel launches plus their argument marshalling (at 8 azimuth sectors a rank's step is
     ~1 ms of GPU work against ~0.3 ms of host enqueue).  The ray batch, the optional `packed` tile and the returned output
-    tensors are the buffers of the captured call: refill the inputs in place, `replay()`, read `out` / `hist`.
+    tensors are the buffers of the captured call: refill the inputs in place, `replay()`, read `out` / `hist`.  Keywords go to
+    `render_rays` unchanged (`lidar_only=True` captures the LiDAR-only sweep: `out` then has no "rgb").
 
     The captured launches carry the raw address of the workspace arena (per-level intermediates).  The capture therefore OWNS that
     arena: it is allocated for this capture, kept alive by it, and detached from the model, so that a later eager `render_rays` -

@@ -238,13 +238,14 @@ class DynamicModel(Model):
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         return self._ws
 
-    def _render_call(self, rays, n: int, cfg, out) -> None:
+    def _render_call(self, rays, n: int, cfg, out, lidar_only: bool = False) -> None:
         box, winners = self._dyn_call
         ws = self._workspace(n)
         wp = (_lib.c_fp * len(winners))(*[w.data_ptr() for w in winners]) if winners else None
-        rc = _lib.lib().nlr_render_rays_dynamic(self._handle, self._objects, C.byref(rays), _lib.ptr(box), int(box.shape[1]), n, C.byref(cfg),
-                                                C.byref(out), wp, _lib.ptr(ws), ws.numel(), _lib.current_stream())
-        _lib.check(rc, "nlr_render_rays_dynamic")
+        name = "nlr_render_lidar_dynamic" if lidar_only else "nlr_render_rays_dynamic"
+        rc = getattr(_lib.lib(), name)(self._handle, self._objects, C.byref(rays), _lib.ptr(box), int(box.shape[1]), n, C.byref(cfg),
+                                       C.byref(out), wp, _lib.ptr(ws), ws.numel(), _lib.current_stream())
+        _lib.check(rc, name)
 
     def box_params(self, timestamp: torch.Tensor, curr_track=None) -> torch.Tensor:
         """[N, n_obj, 8] world -> box constants of every ray and track at the ray's timestamp (`nlr_track_box_params`:
@@ -262,11 +263,12 @@ class DynamicModel(Model):
 
     @torch.no_grad()
     def render_rays(self, batch, train_frac: float = 1.0, compute_extras: bool = True, sample_n: int = 7, sample_m: int = 3,
-                    want_history: bool = False, scale_factor: float = 0.0, rand_jitter=None, rand_deg=None, packed=None, curr_track=None):
+                    want_history: bool = False, scale_factor: float = 0.0, rand_jitter=None, rand_deg=None, packed=None, curr_track=None,
+                    lidar_only: bool = False):
         """`Model.render_rays` with the object merge of ZI/models.py:401-477 inside every level, all on the device
         (`nlr_render_rays_dynamic`): pose blend, owner map, per-class compaction and the object networks run as kernels on
         the render stream; nothing is read back.  History entries carry `obj_mask` (winner >= 0) as the reference's
-        ray_results do."""
+        ray_results do.  lidar_only: `nlr_render_lidar_dynamic` - no colour from either the scene's or the objects' view MLPs."""
         if "timestamp" not in batch:
             raise RuntimeError("batch['timestamp'] is missing (ZI/models.py:315)")
         n = batch["origins"].shape[0]
@@ -276,7 +278,7 @@ class DynamicModel(Model):
         self._dyn_call = (box, winners)
         try:
             r, hist = Model.render_rays(self, batch, train_frac, compute_extras, sample_n, sample_m, want_history, scale_factor, rand_jitter,
-                                        rand_deg, packed)
+                                        rand_deg, packed, lidar_only)
         finally:
             self._dyn_call = None
         for h, w in zip(hist, winners):

@@ -69,11 +69,22 @@ def drop_rays(res: Dict[str, torch.Tensor], points_lidar: torch.Tensor, unet, ma
     return raydrop.apply_ray_drop(proj, logits[0], mask_thre=mask_thre, place_car=place_car), proj
 
 
-def render_sweep_device(model: Model, batch: Dict[str, torch.Tensor], scale_factor: float) -> Dict[str, torch.Tensor]:
+def render_sweep_device(model: Model, batch: Dict[str, torch.Tensor], scale_factor: float, lidar_only: bool = False) -> Dict[str, torch.Tensor]:
     """One sweep through ONE `nlr_render_rays` call (no chunk loop, nothing leaves the device): the LiDAR post-step outputs `points`
-    (metres), `labels`, `rgb`, `depth`, `intensity` of render_lidar.py:142-161, written by the compositing kernel itself."""
-    r, _ = model.render_rays(batch, compute_extras=False, scale_factor=scale_factor)
+    (metres), `labels`, `rgb`, `depth`, `intensity` of render_lidar.py:142-161, written by the compositing kernel itself.
+    lidar_only: ONE `nlr_render_lidar` call - the same outputs without `rgb`, and the view MLP is not run."""
+    r, _ = model.render_rays(batch, compute_extras=False, scale_factor=scale_factor, lidar_only=lidar_only)
     return r
+
+
+def save_sweep_lidar(out_dir: str, idx: int, res: Dict[str, torch.Tensor]) -> None:
+    """`save_sweep` for a LiDAR-only sweep: points and labels (+ intensity when the model has the head), no `points_rgb`."""
+    os.makedirs(out_dir, exist_ok=True)
+    npy = lambda t: t.detach().cpu().numpy()
+    np.save(os.path.join(out_dir, "points_{:04d}.npy".format(idx)), npy(res["points"]))
+    np.save(os.path.join(out_dir, "points_semantic_{:04d}.npy".format(idx)), npy(res["labels"]).astype(np.int64))
+    if "intensity" in res:
+        np.save(os.path.join(out_dir, "points_intensity_{:04d}.npy".format(idx)), npy(res["intensity"]))
 
 
 def sweep_unet_input(res: Dict[str, torch.Tensor], origin_m: torch.Tensor, lidar2world: torch.Tensor, var: bool = True, width: int = 1024):
@@ -131,7 +142,7 @@ def raydrop_batch(model: Model, sweep_ids, scale_factor: float = 1.0 / 250.0, se
     return torch.stack(imgs), gt_mask, gt_range, projs
 
 
-def main(argv=None) -> int:
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     src = ap.add_mutually_exclusive_group()
     src.add_argument("--ckpt", help="reference checkpoint directory or file (checkpoint_<step>.ckpt)")
@@ -151,7 +162,22 @@ def main(argv=None) -> int:
                     "the dynamic-object branch (Config.instance_obj=True); needs --track-classes")
     ap.add_argument("--track-classes", default=None, help="comma-separated nuScenes category per track, e.g. vehicle.car,vehicle.truck")
     ap.add_argument("--synthetic-tracks", type=int, default=0, help="N seeded boxes placed on rays of the sweep (no dataset in this image)")
+    ap.add_argument("--lidar-only", action="store_true", help="render without colour (one nlr_render_lidar call per sweep, no view MLP): "
+                    "writes points, points_semantic and points_intensity, no points_rgb; not with --raydrop-unet")
+    return ap
+
+
+def parse_args(argv=None) -> argparse.Namespace:
+    ap = build_parser()
     a = ap.parse_args(argv)
+    if a.lidar_only and a.raydrop_unet:
+        ap.error("--lidar-only renders no colour, and the ray-drop UNet's feature stack (raydrop.unet_features) takes the rgb channels: "
+                 "drop one of --lidar-only / --raydrop-unet")
+    return a
+
+
+def main(argv=None) -> int:
+    a = parse_args(argv)
     if not torch.cuda.is_available():
         raise RuntimeError("render_lidar needs a GPU: the fused path has no CPU fallback")
     dynamic = bool(a.tracks or a.synthetic_tracks)
@@ -209,10 +235,14 @@ def main(argv=None) -> int:
         if dynamic:  # one sweep = one instant (ZI/datasets.py: per-ray timestamps of a sweep are its capture time)
             batch["timestamp"] = np.full((batch["origins"].shape[0], 1), idx / max(a.sweeps - 1, 1), np.float32)
         t0 = time.time()
-        res = render_sweep(model, batch, a.scale_factor)
+        if a.lidar_only:
+            res = render_sweep_device(model, {k: torch.from_numpy(np.ascontiguousarray(v)).to(model.device) for k, v in batch.items()},
+                                      a.scale_factor, lidar_only=True)
+        else:
+            res = render_sweep(model, batch, a.scale_factor)
         torch.cuda.synchronize()
         dt = time.time() - t0
-        save_sweep(out_dir, idx, res)
+        (save_sweep_lidar if a.lidar_only else save_sweep)(out_dir, idx, res)
         n = res["points"].shape[0]
         print(f"sweep {idx + 1}/{a.sweeps}: {n} rays in {dt:0.3f}s ({n / dt:,.0f} rays/s), {int(res['labels'].unique().numel())} labels")
         if unet is not None:

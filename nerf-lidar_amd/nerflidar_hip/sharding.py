@@ -124,6 +124,13 @@ def render_sweep_sharded(render_fn: Callable[..., Dict[str, torch.Tensor]], batc
     `viewdirs` keep the full-sweep Frobenius normalisation (ZI/lidar_utils.py:12) and a sector renders exactly what the
     same rays render inside a one-GPU sweep.  `render_fn(batch, packed=tile)` may fill the azimuth-major tile itself
     (the HIP renderer does) and return None / a dict with "packed"; if it returns per-ray outputs they are packed here.
+
+    A sweep server that reads no colour passes a LiDAR-only render,
+
+        render_fn = lambda batch, packed: model.render_rays(batch, compute_extras=False, scale_factor=sf, packed=packed,
+                                                            lidar_only=True)[0]
+
+    and gets the same [W, H, 7] image with 0 in the rgb slots (3..5): `unpack_image` needs no change.
     """
     g = gatherer or SweepGatherer(height, width, device, group)
     sec, wp = lidar.azimuth_sector(batch_np, height, width, g.rank, g.world)
