@@ -276,6 +276,13 @@ const char *nlr_build_sha(void);
  *     1 full render, per-sample heads + nlr_composite_kernel; 2 full render, compositing-mode MLP kernel; 3 LiDAR-only render through
  *     the kernels of nlr_mlp_level(rgb = NULL); 4 LiDAR-only render through the LiDAR-only compositing instance.  0 = none yet. */
 #define NLR_DBG_LAST_ROUTE 7
+/*   NLR_DBG_TRAIN_ROUTE (key 8), NLR_DBG_TRAIN_TRUNK_ROW0 (key 9), NLR_DBG_TRAIN_TRUNK_ROWS (key 10): read-backs of the most recent
+ *     nlr_mlp_train_forward / _backward (or _split) call of this process.  Route = 1 (the full instance was launched) + 2 (the
+ *     trunk-and-heads instance was launched) + 4 (the call was a backward); the other two are the first row and the row count the
+ *     trunk-and-heads instance ran on (M_color and M - M_color). */
+#define NLR_DBG_TRAIN_ROUTE 8
+#define NLR_DBG_TRAIN_TRUNK_ROW0 9
+#define NLR_DBG_TRAIN_TRUNK_ROWS 10
 int nlr_debug_set(uint32_t key, int value);
 int nlr_debug_get(uint32_t key);
 /* 1 when the fused kernels' fast level body covers this grid (see csrc/nlr_level_fast.h:nlr_level_fast_ok), 0 when the generic body
@@ -387,6 +394,20 @@ int nlr_hash_decay_backward(const float *embeddings, const int32_t *offsets_host
  *       go to f32 slabs in the workspace and are summed in slice order: no atomics, the same inputs give the same bits.
  *       nlr_mlp_train_wgrad_workspace_bytes = 8 * n_params * 4 bytes, independent of M (largest plan: 32 MiB).
  *       Refused with nothing launched: NULL argument, M == 0, M % S != 0, workspace_bytes below that size.
+ *     _split: rows without colour supervision.  The three _split entry points take rows ordered colour rays first: rows [0, M_color)
+ *       are treated exactly as by their unsplit twins (same kernel instance, same bits), rows [M_color, M) run the density trunk and the
+ *       semantic / intensity heads only, as a second launch of a trunk-and-heads instance on the same stream (LiDAR rays of a mixed
+ *       batch carry a depth and an intensity loss and nothing else, ZI/train.py:316-320).  For those rows
+ *         forward:  rgb is WRITTEN AS 0; density, semantic, intensity and the acts columns [hid | bottleneck | head hidden] are the bits
+ *                   the unsplit call gives; the view columns x_0 .. x_{D-1} of acts are NOT written.
+ *         backward: g_rgb is not read; the bottleneck gradient collects the heads and the raw density only; the gacts columns of the
+ *                   view layers and of rgb_layer are NOT written; d_features is written for every row.
+ *         wgrad:    lin_second_stage_* and rgb_layer reduce over rows [0, M_color) and never read a later row of acts / gacts; the
+ *                   other Linears reduce over all M rows.  Same slabs, same fixed order, same workspace size; with M_color == 0 those
+ *                   parts of d_params are zeros.
+ *       M_color == M gives the bits of the unsplit call; M_color == 0 is valid (no view MLP at all, g_rgb may be NULL).  Refused with
+ *       nothing launched and a message naming the argument: M_color > M, M_color % S != 0, M % S != 0, M == 0, a NULL pointer among
+ *       those the unsplit call requires.
  * ------------------------------------------------------------------------------------------ */
 typedef struct NlrTrainPlan NlrTrainPlan;
 int nlr_train_plan_create(uint32_t F, uint32_t W, uint32_t WB, uint32_t D, uint32_t deg_view, uint32_t class_num,
@@ -404,6 +425,15 @@ int nlr_mlp_train_backward(const NlrTrainPlan *p, uint32_t M, uint32_t S, const 
 size_t nlr_mlp_train_wgrad_workspace_bytes(const NlrTrainPlan *p, uint32_t M);
 int nlr_mlp_train_wgrad(const NlrTrainPlan *p, uint32_t M, uint32_t S, const float *features, const float *enc, const void *acts,
                         const void *gacts, float *d_params, void *workspace, size_t workspace_bytes, void *stream);
+int nlr_mlp_train_forward_split(const NlrTrainPlan *p, const float *features, const float *enc, uint32_t M, uint32_t M_color,
+                                uint32_t S, float *density, float *rgb, float *semantic, float *intensity, void *acts, void *stream);
+int nlr_mlp_train_backward_split(const NlrTrainPlan *p, uint32_t M, uint32_t M_color, uint32_t S, const float *density,
+                                 const float *rgb, const float *semantic, const void *acts, const float *g_density,
+                                 const float *g_rgb, const float *g_semantic, const float *g_intensity, void *gacts,
+                                 float *d_features, void *stream);
+int nlr_mlp_train_wgrad_split(const NlrTrainPlan *p, uint32_t M, uint32_t M_color, uint32_t S, const float *features,
+                              const float *enc, const void *acts, const void *gacts, float *d_params, void *workspace,
+                              size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * (7) Dynamic-object branch: owner of every sample.  winner [N,S] int32 = index of the LAST

@@ -750,13 +750,15 @@ int nlr_fill_cast_params(CastParams *cp, const NlrRays *rays, const float *tdist
 // environment variable.  [0] force the generic level body, [1] cap of the persistent MLP grid for models created afterwards.
 #include <atomic>
 // [7] is a read-back, not a switch: the route of the last render call (NLR_DBG_LAST_ROUTE), stored by render_impl.
-static std::atomic<int> nlr_debug_switch[8] = {{0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}};
+// [8..10] likewise for the fused training NerfMLP (NLR_DBG_TRAIN_*), stored by nlr_mlp_train_forward / _backward (and _split).
+#define NLR_DBG_KEYS 11
+static std::atomic<int> nlr_debug_switch[NLR_DBG_KEYS] = {{0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}};
 extern "C" int nlr_debug_set(uint32_t key, int value) {
-    NLR_CHECK_ARG(key < 8, "debug_set: unknown key %u", key);
+    NLR_CHECK_ARG(key < NLR_DBG_KEYS, "debug_set: unknown key %u", key);
     nlr_debug_switch[key].store(value);
     return NLR_OK;
 }
-extern "C" int nlr_debug_get(uint32_t key) { return key < 8 ? nlr_debug_switch[key].load() : 0; }
+extern "C" int nlr_debug_get(uint32_t key) { return key < NLR_DBG_KEYS ? nlr_debug_switch[key].load() : 0; }
 static bool nlr_force_generic() { return nlr_debug_switch[NLR_DBG_FORCE_GENERIC].load() != 0; }
 
 extern "C" int nlr_grid_fast_path(const int32_t *offsets_host, uint32_t L, uint32_t C, float S, uint32_t H, int table_dtype, uint32_t gridtype,

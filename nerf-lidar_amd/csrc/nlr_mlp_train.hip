@@ -22,7 +22,8 @@
 #include "nlr_train_plan.h"
 
 struct TrainParams {
-    uint32_t M, S, F, depth, K, int_row, act_w;
+    uint32_t M, S, F, depth, K, int_row, act_w;  // M: one past the last row of this launch
+    uint32_t row0, ldm;                          // first row of this launch; samples of the channel-major tensors (rgb [3, ldm], ..)
     const float *feat;   // [M, F] f32
     const float *enc;    // [N, 32]
     const uint4 *tape;
@@ -78,7 +79,10 @@ __device__ __forceinline__ void nlr_pack_masked(BT<2> &dst, const Unit<2> &src, 
 }
 
 // WT = view width / 32, BW = bottleneck / 32, FT = ceil(F / 32), HT = head hidden units of 32 (0, 2, 4)
-template <int WT, int BW, int FT, int HT, bool BWD>
+// VIEW = false: rows without colour supervision (nlr_mlp_train_*_split): density trunk and heads only, on the tapes
+//   forward D0 D2 [H1 H2], backward H2^T [H1^T | e_0] D2^T D0^T; rgb is written as 0, the view columns of acts / gacts and the
+//   rgb_layer columns of gacts are neither read nor written.  WT does not enter these instances.
+template <int WT, int BW, int FT, int HT, bool BWD, bool VIEW = true>
 __global__ void __launch_bounds__(256, 1) nlr_mlp_train_kernel(TrainParams P) {
     __shared__ __align__(16) uint4 lds_tape[NLR_NBUF * NLR_CHUNK_SLOTS];
     __shared__ __align__(16) float lds_bias[NLR_BIAS_MAX];
@@ -98,12 +102,14 @@ __global__ void __launch_bounds__(256, 1) nlr_mlp_train_kernel(TrainParams P) {
     static_assert(FR_HL % NLR_CHUNK_FRAGS == 0, "hidden view layers must cover whole chunks");
     constexpr int FF_HID = FR_T + FR_V0 + FR_V1, FF_END = FF_HID + FR_RGB;
     // backward program: RGB^T (WT units x 1 k-block), hidden^T, V1a^T (WT x WT), H2^T (HT x 1), BIG (BW x (2 WT + HT + 1)), D2^T (2 x BW), D0^T (FT x 2)
-    constexpr int BR_RGB = WT * 1 * 2, BR_V1A = WT * WT * 2, BR_H2 = HT * 1 * 2, BR_BIG = BW * (2 * WT + HT + 1) * 2, BR_D2 = 2 * BW * 2,
+    // (VW = 0 without the view MLP: the program starts at H2^T and BIG shrinks to [H1^T | e_0])
+    constexpr int VW = VIEW ? WT : 0;
+    constexpr int BR_RGB = VW * 1 * 2, BR_V1A = VW * VW * 2, BR_H2 = HT * 1 * 2, BR_BIG = BW * (2 * VW + HT + 1) * 2, BR_D2 = 2 * BW * 2,
                   BR_D0 = FT * 2 * 2;
     constexpr int BF_V1A = BR_RGB, BF_H2 = BF_V1A + BR_V1A, BF_BIG = BF_H2 + BR_H2, BF_D2 = BF_BIG + BR_BIG, BF_D0 = BF_D2 + BR_D2,
                   BF_END = BF_D0 + BR_D0;  // (+ hidden layers between RGB^T and V1a^T: whole chunks)
 
-    const uint32_t ntiles = (P.M + 127) / 128;
+    const uint32_t ntiles = (P.M - P.row0 + 127) / 128;
     if (!BWD)
         for (uint32_t i = threadIdx.x * 4; i < P.bias_count; i += 1024)
             *reinterpret_cast<f32x4 *>(lds_bias + i) = *reinterpret_cast<const f32x4 *>(P.bias_all + i);
@@ -125,7 +131,7 @@ __global__ void __launch_bounds__(256, 1) nlr_mlp_train_kernel(TrainParams P) {
     auto no_bias = [&](auto, f32x4 (&out)[2]) { out[0] = out[1] = zero4; };
 
     for (uint32_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const uint32_t s0 = tile * 128 + wave * 32;
+        const uint32_t s0 = P.row0 + tile * 128 + wave * 32;
         if constexpr (!BWD) {
             // ======================================================= forward =======================================================
             BT<2> fb[FT], hbe[BW + 1];
@@ -144,13 +150,15 @@ __global__ void __launch_bounds__(256, 1) nlr_mlp_train_kernel(TrainParams P) {
                     }
                     nlr_pack_all<false, 0>(fb[t], fin);
                 }
+                if constexpr (VIEW) {
 #pragma unroll
-                for (int n = 0; n < 2; ++n) {
-                    const uint32_t smp = s0 + 16 * n + col, sc = smp < P.M ? smp : P.M - 1;
+                    for (int n = 0; n < 2; ++n) {
+                        const uint32_t smp = s0 + 16 * n + col, sc = smp < P.M ? smp : P.M - 1;
 #pragma unroll
-                    for (int jb = 0; jb < 2; ++jb) eu.a[jb][n] = *reinterpret_cast<const f32x4 *>(P.enc + (size_t)(sc / P.S) * 32 + 16 * jb + 4 * q);
+                        for (int jb = 0; jb < 2; ++jb) eu.a[jb][n] = *reinterpret_cast<const f32x4 *>(P.enc + (size_t)(sc / P.S) * 32 + 16 * jb + 4 * q);
+                    }
+                    nlr_pack_all<false, 0>(hbe[BW], eu);
                 }
-                nlr_pack_all<false, 0>(hbe[BW], eu);
             }
             BT<2> hidb[2];
             nlr_gemm<2, FT, 2, 2, 1, 0, 9>(
@@ -239,7 +247,7 @@ __global__ void __launch_bounds__(256, 1) nlr_mlp_train_kernel(TrainParams P) {
 #pragma unroll
                             for (int r = 0; r < 4; ++r) {
                                 const int row = 16 * jb + 4 * q + r;
-                                if (valid && row < (int)P.K) P.sem[(size_t)row * P.M + smp] = e[jb][r] / s;
+                                if (valid && row < (int)P.K) P.sem[(size_t)row * P.ldm + smp] = e[jb][r] / s;
                             }
                     }
                     if (P.inten && valid) {
@@ -251,115 +259,147 @@ __global__ void __launch_bounds__(256, 1) nlr_mlp_train_kernel(TrainParams P) {
                     }
                 }
             }
-            // view MLP
-            BT<2> x[WT], y[WT];
-            nlr_gemm<WT, BW + 1, 2, 2, 1, FR_T, 9>(
-                tp, [&](auto o, f32x4(&b)[2]) { bias_rows(lds_bias + OB_V0 + 32 * decltype(o)::value, b); },
-                [&](Unit<2> &u, auto g, auto j, const uint4 &f0, const uint4 &, const f32x4 &bj) {
-                    constexpr int G = decltype(g)::value, J = decltype(j)::value;
-                    nlr_mma_bf16<G == 0, 0>(u.a[J], bj, f0, hbe[G]);
-                },
-                [&](auto o, auto p, const Unit<2> &u) {
-                    constexpr int O = decltype(o)::value, Pc = decltype(p)::value;
-                    if constexpr (Pc < 8) nlr_pack_piece<true, Pc, 0>(x[O], u);
-                    else nlr_store_bt(P.acts, ld, s0, P.M, col, q, C_X + 32 * O, x[O]);
-                });
-            nlr_gemm<WT, WT + BW + 1, 2, 2, 1, FR_T + FR_V0, 9>(
-                tp, [&](auto o, f32x4(&b)[2]) { bias_rows(lds_bias + OB_V1 + 32 * decltype(o)::value, b); },
-                [&](Unit<2> &u, auto g, auto j, const uint4 &f0, const uint4 &, const f32x4 &bj) {
-                    constexpr int G = decltype(g)::value, J = decltype(j)::value;
-                    if constexpr (G < WT) nlr_mma_bf16<G == 0, 0>(u.a[J], bj, f0, x[G]);
-                    else nlr_mma_bf16<false, 0>(u.a[J], bj, f0, hbe[G - WT]);
-                },
-                [&](auto o, auto p, const Unit<2> &u) {
-                    constexpr int O = decltype(o)::value, Pc = decltype(p)::value;
-                    if constexpr (Pc < 8) nlr_pack_piece<true, Pc, 0>(y[O], u);
-                    else nlr_store_bt(P.acts, ld, s0, P.M, col, q, C_X + W + 32 * O, y[O]);
-                });
-            for (uint32_t l = 2; l < P.depth; ++l) {
-                const float *bl = lds_bias + OB_VL + (l - 2) * (WT * 32);
-                const uint32_t cl = C_X + l * W;
-                nlr_gemm<WT, WT, 2, 2, 1, FF_HID, 9>(
-                    tp, [&](auto o, f32x4(&b)[2]) { bias_rows(bl + 32 * decltype(o)::value, b); },
+            if constexpr (!VIEW) {
+                // no colour supervision: rgb = 0 (the compositing operator reads it), the view columns of acts stay unwritten
+                if (q == 0) {
+#pragma unroll
+                    for (int n = 0; n < 2; ++n) {
+                        const uint32_t smp = s0 + 16 * n + col;
+                        if (smp < P.M) {
+#pragma unroll
+                            for (int c = 0; c < 3; ++c) P.rgb[(size_t)c * P.ldm + smp] = 0.0f;
+                        }
+                    }
+                }
+                nlr_pad<FR_T % NLR_CHUNK_FRAGS>(tp);
+            } else {
+                // view MLP
+                BT<2> x[WT], y[WT];
+                nlr_gemm<WT, BW + 1, 2, 2, 1, FR_T, 9>(
+                    tp, [&](auto o, f32x4(&b)[2]) { bias_rows(lds_bias + OB_V0 + 32 * decltype(o)::value, b); },
                     [&](Unit<2> &u, auto g, auto j, const uint4 &f0, const uint4 &, const f32x4 &bj) {
                         constexpr int G = decltype(g)::value, J = decltype(j)::value;
-                        nlr_mma_bf16<G == 0, 0>(u.a[J], bj, f0, y[G]);
+                        nlr_mma_bf16<G == 0, 0>(u.a[J], bj, f0, hbe[G]);
                     },
                     [&](auto o, auto p, const Unit<2> &u) {
                         constexpr int O = decltype(o)::value, Pc = decltype(p)::value;
                         if constexpr (Pc < 8) nlr_pack_piece<true, Pc, 0>(x[O], u);
-                        else nlr_store_bt(P.acts, ld, s0, P.M, col, q, cl + 32 * O, x[O]);
+                        else nlr_store_bt(P.acts, ld, s0, P.M, col, q, C_X + 32 * O, x[O]);
                     });
+                nlr_gemm<WT, WT + BW + 1, 2, 2, 1, FR_T + FR_V0, 9>(
+                    tp, [&](auto o, f32x4(&b)[2]) { bias_rows(lds_bias + OB_V1 + 32 * decltype(o)::value, b); },
+                    [&](Unit<2> &u, auto g, auto j, const uint4 &f0, const uint4 &, const f32x4 &bj) {
+                        constexpr int G = decltype(g)::value, J = decltype(j)::value;
+                        if constexpr (G < WT) nlr_mma_bf16<G == 0, 0>(u.a[J], bj, f0, x[G]);
+                        else nlr_mma_bf16<false, 0>(u.a[J], bj, f0, hbe[G - WT]);
+                    },
+                    [&](auto o, auto p, const Unit<2> &u) {
+                        constexpr int O = decltype(o)::value, Pc = decltype(p)::value;
+                        if constexpr (Pc < 8) nlr_pack_piece<true, Pc, 0>(y[O], u);
+                        else nlr_store_bt(P.acts, ld, s0, P.M, col, q, C_X + W + 32 * O, y[O]);
+                    });
+                for (uint32_t l = 2; l < P.depth; ++l) {
+                    const float *bl = lds_bias + OB_VL + (l - 2) * (WT * 32);
+                    const uint32_t cl = C_X + l * W;
+                    nlr_gemm<WT, WT, 2, 2, 1, FF_HID, 9>(
+                        tp, [&](auto o, f32x4(&b)[2]) { bias_rows(bl + 32 * decltype(o)::value, b); },
+                        [&](Unit<2> &u, auto g, auto j, const uint4 &f0, const uint4 &, const f32x4 &bj) {
+                            constexpr int G = decltype(g)::value, J = decltype(j)::value;
+                            nlr_mma_bf16<G == 0, 0>(u.a[J], bj, f0, y[G]);
+                        },
+                        [&](auto o, auto p, const Unit<2> &u) {
+                            constexpr int O = decltype(o)::value, Pc = decltype(p)::value;
+                            if constexpr (Pc < 8) nlr_pack_piece<true, Pc, 0>(x[O], u);
+                            else nlr_store_bt(P.acts, ld, s0, P.M, col, q, cl + 32 * O, x[O]);
+                        });
 #pragma unroll
-                for (int t = 0; t < WT; ++t) y[t] = x[t];
-            }
-            Unit<2> out1;
-            nlr_gemm<1, WT, 1, 2, 1, FF_HID, 1>(
-                tp, [&](auto, f32x4(&b)[2]) { bias_rows(lds_bias + OB_VL + (P.depth - 2) * (WT * 32), b); },
-                [&](Unit<2> &u, auto g, auto j, const uint4 &f0, const uint4 &, const f32x4 &bj) {
-                    constexpr int G = decltype(g)::value, J = decltype(j)::value;
-                    nlr_mma_bf16<G == 0, 0>(u.a[J], bj, f0, y[G]);
-                },
-                [&](auto, auto, const Unit<2> &u) { out1 = u; });
-            if (q == 0) {
-#pragma unroll
-                for (int n = 0; n < 2; ++n) {
-                    const uint32_t smp = s0 + 16 * n + col;
-                    if (smp < P.M) {
-#pragma unroll
-                        for (int c = 0; c < 3; ++c) {
-                            const float z = P.rgb_premul * out1.a[0][n][c] + P.rgb_bias;
-                            const float sg = 1.0f / (1.0f + expf(-z));
-                            P.rgb[(size_t)c * P.M + smp] = sg * (1.0f + 2.0f * P.rgb_padding) - P.rgb_padding;
-                        }
-                    }
+                    for (int t = 0; t < WT; ++t) y[t] = x[t];
                 }
-            }
-            nlr_pad<FF_END % NLR_CHUNK_FRAGS>(tp);
-        } else {
-            // ======================================================= backward ======================================================
-            // d loss / d (rgb_layer output): rgb = s (1 + 2p) - p, s = sigmoid(premul o + bias)
-            BT<2> gin;  // one 32-feature k-block of upstream gradient
-            {
-                Unit<2> du;
-#pragma unroll
-                for (int jb = 0; jb < 2; ++jb)
-#pragma unroll
-                    for (int n = 0; n < 2; ++n) du.a[jb][n] = zero4;
-                if (q == 0 && P.g_rgb) {
+                Unit<2> out1;
+                nlr_gemm<1, WT, 1, 2, 1, FF_HID, 1>(
+                    tp, [&](auto, f32x4(&b)[2]) { bias_rows(lds_bias + OB_VL + (P.depth - 2) * (WT * 32), b); },
+                    [&](Unit<2> &u, auto g, auto j, const uint4 &f0, const uint4 &, const f32x4 &bj) {
+                        constexpr int G = decltype(g)::value, J = decltype(j)::value;
+                        nlr_mma_bf16<G == 0, 0>(u.a[J], bj, f0, y[G]);
+                    },
+                    [&](auto, auto, const Unit<2> &u) { out1 = u; });
+                if (q == 0) {
 #pragma unroll
                     for (int n = 0; n < 2; ++n) {
                         const uint32_t smp = s0 + 16 * n + col;
                         if (smp < P.M) {
 #pragma unroll
                             for (int c = 0; c < 3; ++c) {
-                                const float s = (P.rgb[(size_t)c * P.M + smp] + P.rgb_padding) / (1.0f + 2.0f * P.rgb_padding);
-                                du.a[0][n][c] = P.g_rgb[(size_t)c * P.M + smp] * (1.0f + 2.0f * P.rgb_padding) * (s * (1.0f - s)) * P.rgb_premul;
+                                const float z = P.rgb_premul * out1.a[0][n][c] + P.rgb_bias;
+                                const float sg = 1.0f / (1.0f + expf(-z));
+                                P.rgb[(size_t)c * P.ldm + smp] = sg * (1.0f + 2.0f * P.rgb_padding) - P.rgb_padding;
                             }
                         }
                     }
                 }
-                nlr_pack_all<false, 0>(gin, du);
-                nlr_store_bt(P.gacts, gld, s0, P.M, col, q, C_O, gin);
+                nlr_pad<FF_END % NLR_CHUNK_FRAGS>(tp);
             }
+        } else {
+            // ======================================================= backward ======================================================
+            // d loss / d (rgb_layer output): rgb = s (1 + 2p) - p, s = sigmoid(premul o + bias)
+            BT<2> gin;  // one 32-feature k-block of upstream gradient
             BT<2> g[WT], h[WT], mk;
-            {  // RGB^T: gradient of the last view layer's pre-activation
-                const uint32_t cl = C_X + (P.depth - 1) * W;
-                nlr_gemm<WT, 1, 2, 2, 1, 0, 9>(
-                    tp, no_bias,
-                    [&](Unit<2> &u, auto, auto j, const uint4 &f0, const uint4 &, const f32x4 &bj) {
-                        nlr_mma_bf16<true, 0>(u.a[decltype(j)::value], bj, f0, gin);
-                    },
-                    [&](auto o, auto p, const Unit<2> &u) {
-                        constexpr int O = decltype(o)::value, Pc = decltype(p)::value;
-                        if constexpr (Pc == 0) nlr_load_bt(P.acts, ld, s0, P.M, col, q, cl + 32 * O, mk);
-                        if constexpr (Pc < 8) nlr_pack_masked<Pc>(g[O], u, mk);
-                        else nlr_store_bt(P.gacts, gld, s0, P.M, col, q, cl + 32 * O, g[O]);
-                    });
-            }
-            for (uint32_t l = P.depth - 1; l >= 2; --l) {  // hidden layers, transposed: d z_{l-1} = mask(x_{l-1}) W_l^T d z_l
-                const uint32_t cl = C_X + (l - 1) * W;
-                nlr_gemm<WT, WT, 2, 2, 1, BR_RGB, 9>(
+            if constexpr (VIEW) {
+                {
+                    Unit<2> du;
+#pragma unroll
+                    for (int jb = 0; jb < 2; ++jb)
+#pragma unroll
+                        for (int n = 0; n < 2; ++n) du.a[jb][n] = zero4;
+                    if (q == 0 && P.g_rgb) {
+#pragma unroll
+                        for (int n = 0; n < 2; ++n) {
+                            const uint32_t smp = s0 + 16 * n + col;
+                            if (smp < P.M) {
+#pragma unroll
+                                for (int c = 0; c < 3; ++c) {
+                                    const float s = (P.rgb[(size_t)c * P.ldm + smp] + P.rgb_padding) / (1.0f + 2.0f * P.rgb_padding);
+                                    du.a[0][n][c] = P.g_rgb[(size_t)c * P.ldm + smp] * (1.0f + 2.0f * P.rgb_padding) * (s * (1.0f - s)) * P.rgb_premul;
+                                }
+                            }
+                        }
+                    }
+                    nlr_pack_all<false, 0>(gin, du);
+                    nlr_store_bt(P.gacts, gld, s0, P.M, col, q, C_O, gin);
+                }
+                {  // RGB^T: gradient of the last view layer's pre-activation
+                    const uint32_t cl = C_X + (P.depth - 1) * W;
+                    nlr_gemm<WT, 1, 2, 2, 1, 0, 9>(
+                        tp, no_bias,
+                        [&](Unit<2> &u, auto, auto j, const uint4 &f0, const uint4 &, const f32x4 &bj) {
+                            nlr_mma_bf16<true, 0>(u.a[decltype(j)::value], bj, f0, gin);
+                        },
+                        [&](auto o, auto p, const Unit<2> &u) {
+                            constexpr int O = decltype(o)::value, Pc = decltype(p)::value;
+                            if constexpr (Pc == 0) nlr_load_bt(P.acts, ld, s0, P.M, col, q, cl + 32 * O, mk);
+                            if constexpr (Pc < 8) nlr_pack_masked<Pc>(g[O], u, mk);
+                            else nlr_store_bt(P.gacts, gld, s0, P.M, col, q, cl + 32 * O, g[O]);
+                        });
+                }
+                for (uint32_t l = P.depth - 1; l >= 2; --l) {  // hidden layers, transposed: d z_{l-1} = mask(x_{l-1}) W_l^T d z_l
+                    const uint32_t cl = C_X + (l - 1) * W;
+                    nlr_gemm<WT, WT, 2, 2, 1, BR_RGB, 9>(
+                        tp, no_bias,
+                        [&](Unit<2> &u, auto gg, auto j, const uint4 &f0, const uint4 &, const f32x4 &bj) {
+                            constexpr int G = decltype(gg)::value, J = decltype(j)::value;
+                            nlr_mma_bf16<G == 0, 0>(u.a[J], bj, f0, g[G]);
+                        },
+                        [&](auto o, auto p, const Unit<2> &u) {
+                            constexpr int O = decltype(o)::value, Pc = decltype(p)::value;
+                            if constexpr (Pc == 0) nlr_load_bt(P.acts, ld, s0, P.M, col, q, cl + 32 * O, mk);
+                            if constexpr (Pc < 8) nlr_pack_masked<Pc>(h[O], u, mk);
+                            else nlr_store_bt(P.gacts, gld, s0, P.M, col, q, cl + 32 * O, h[O]);
+                        });
+#pragma unroll
+                    for (int t = 0; t < WT; ++t) g[t] = h[t];
+                }
+                // g = d z_1.  V1a^T: d z_0 = mask(x_0) W1[:, :W]^T d z_1
+                nlr_gemm<WT, WT, 2, 2, 1, BF_V1A, 9>(
                     tp, no_bias,
                     [&](Unit<2> &u, auto gg, auto j, const uint4 &f0, const uint4 &, const f32x4 &bj) {
                         constexpr int G = decltype(gg)::value, J = decltype(j)::value;
@@ -367,26 +407,11 @@ __global__ void __launch_bounds__(256, 1) nlr_mlp_train_kernel(TrainParams P) {
                     },
                     [&](auto o, auto p, const Unit<2> &u) {
                         constexpr int O = decltype(o)::value, Pc = decltype(p)::value;
-                        if constexpr (Pc == 0) nlr_load_bt(P.acts, ld, s0, P.M, col, q, cl + 32 * O, mk);
+                        if constexpr (Pc == 0) nlr_load_bt(P.acts, ld, s0, P.M, col, q, C_X + 32 * O, mk);
                         if constexpr (Pc < 8) nlr_pack_masked<Pc>(h[O], u, mk);
-                        else nlr_store_bt(P.gacts, gld, s0, P.M, col, q, cl + 32 * O, h[O]);
+                        else nlr_store_bt(P.gacts, gld, s0, P.M, col, q, C_X + 32 * O, h[O]);
                     });
-#pragma unroll
-                for (int t = 0; t < WT; ++t) g[t] = h[t];
             }
-            // g = d z_1.  V1a^T: d z_0 = mask(x_0) W1[:, :W]^T d z_1
-            nlr_gemm<WT, WT, 2, 2, 1, BF_V1A, 9>(
-                tp, no_bias,
-                [&](Unit<2> &u, auto gg, auto j, const uint4 &f0, const uint4 &, const f32x4 &bj) {
-                    constexpr int G = decltype(gg)::value, J = decltype(j)::value;
-                    nlr_mma_bf16<G == 0, 0>(u.a[J], bj, f0, g[G]);
-                },
-                [&](auto o, auto p, const Unit<2> &u) {
-                    constexpr int O = decltype(o)::value, Pc = decltype(p)::value;
-                    if constexpr (Pc == 0) nlr_load_bt(P.acts, ld, s0, P.M, col, q, C_X + 32 * O, mk);
-                    if constexpr (Pc < 8) nlr_pack_masked<Pc>(h[O], u, mk);
-                    else nlr_store_bt(P.gacts, gld, s0, P.M, col, q, C_X + 32 * O, h[O]);
-                });
             // heads: softmax backward d l_c = p_c (g_c - sum_k g_k p_k), intensity row: its upstream gradient
             BT<2> gq[HTA], aux;
             {
@@ -408,8 +433,8 @@ __global__ void __launch_bounds__(256, 1) nlr_mlp_train_kernel(TrainParams P) {
                                 for (int r = 0; r < 4; ++r) {
                                     const int row = 16 * jb + 4 * q + r;
                                     const bool on = valid && row < (int)P.K;
-                                    pr[jb][r] = on ? P.sem[(size_t)row * P.M + smp] : 0.0f;
-                                    gr[jb][r] = on ? P.g_sem[(size_t)row * P.M + smp] : 0.0f;
+                                    pr[jb][r] = on ? P.sem[(size_t)row * P.ldm + smp] : 0.0f;
+                                    gr[jb][r] = on ? P.g_sem[(size_t)row * P.ldm + smp] : 0.0f;
                                     dot += pr[jb][r] * gr[jb][r];
                                 }
                             dot = nlr_q_sum(dot);
@@ -452,16 +477,16 @@ __global__ void __launch_bounds__(256, 1) nlr_mlp_train_kernel(TrainParams P) {
                         else nlr_store_bt(P.gacts, gld, s0, P.M, col, q, C_Q + 32 * O, gq[O]);
                     });
             }
-            // BIG: d bottleneck = W1[:, W:W+WB]^T d z_1 + W0[:, :WB]^T d z_0 + H1^T d q + e_0 d raw
+            // BIG: d bottleneck = W1[:, W:W+WB]^T d z_1 + W0[:, :WB]^T d z_0 + H1^T d q + e_0 d raw (without the view MLP: the last two)
             BT<2> gb[BW];
-            nlr_gemm<BW, 2 * WT + HT + 1, 2, 2, 1, BF_BIG, 9>(
+            nlr_gemm<BW, 2 * VW + HT + 1, 2, 2, 1, BF_BIG, 9>(
                 tp, no_bias,
                 [&](Unit<2> &u, auto gg, auto j, const uint4 &f0, const uint4 &, const f32x4 &bj) {
                     constexpr int G = decltype(gg)::value, J = decltype(j)::value;
-                    if constexpr (G < WT) nlr_mma_bf16<G == 0, 0>(u.a[J], bj, f0, g[G]);
-                    else if constexpr (G < 2 * WT) nlr_mma_bf16<false, 0>(u.a[J], bj, f0, h[G - WT]);
-                    else if constexpr (G < 2 * WT + HT) nlr_mma_bf16<false, 0>(u.a[J], bj, f0, gq[G - 2 * WT]);
-                    else nlr_mma_bf16<false, 0>(u.a[J], bj, f0, aux);
+                    if constexpr (G < VW) nlr_mma_bf16<G == 0, 0>(u.a[J], bj, f0, g[G]);
+                    else if constexpr (G < 2 * VW) nlr_mma_bf16<false, 0>(u.a[J], bj, f0, h[G - VW]);
+                    else if constexpr (G < 2 * VW + HT) nlr_mma_bf16<G == 0, 0>(u.a[J], bj, f0, gq[G - 2 * VW]);
+                    else nlr_mma_bf16<G == 0, 0>(u.a[J], bj, f0, aux);
                 },
                 [&](auto o, auto p, const Unit<2> &u) {
                     constexpr int O = decltype(o)::value, Pc = decltype(p)::value;
@@ -690,6 +715,34 @@ extern "C" int nlr_train_plan_create(uint32_t F, uint32_t W, uint32_t WB, uint32
         tape_add(bt, d0t, 64, 64);
     }
     tape_pad(bt);
+    // ---- the tapes of rows without colour supervision (nlr_mlp_train_*_split), behind the full ones so that one gather packs both:
+    //      forward D0 D2 [H1 H2], backward H2^T [H1^T | e_0] D2^T D0^T
+    p->f0n = (uint32_t)ft.size(), p->b0n = (uint32_t)bt.size();
+    tape_add(ft, d0, 64, 64);
+    tape_add(ft, d2, WB, 64);
+    if (HH) {
+        tape_add(ft, h1, HH, WB);
+        tape_add(ft, h2, 32, HH);
+    }
+    tape_pad(ft);
+    if (HH) tape_add(bt, transpose(h2), HH, 32);
+    {
+        IMat big(WB, HH + 32);
+        for (uint32_t r = 0; r < WB; ++r)
+            for (uint32_t c = 0; c < HH; ++c) big.at(r, c) = h1.a[(size_t)c * WB + r];
+        big.at(0, HH + 0) = -2;
+        big.at(0, HH + 1) = -2;
+        tape_add(bt, big, WB, HH + 32);
+    }
+    tape_add(bt, transpose(d2), 64, WB);
+    {
+        IMat d0t(64, 64);
+        for (uint32_t r = 0; r < F; ++r)
+            for (uint32_t c = 0; c < 64; ++c) d0t.at(r, c) = d0.a[(size_t)c * F + r];
+        tape_add(bt, d0t, 64, 64);
+    }
+    tape_pad(bt);
+    p->f1 = p->f0n, p->f1n = (uint32_t)ft.size() - p->f0n, p->b1 = p->b0n, p->b1n = (uint32_t)bt.size() - p->b0n;
     p->fn = (uint32_t)ft.size(), p->bn = (uint32_t)bt.size(), p->biasn = (uint32_t)bb.size();
     NLR_CHECK_ARG(p->biasn <= NLR_BIAS_MAX && p->biasn % 4 == 0, "train_plan_create: bias block of %u floats does not fit", p->biasn);
     auto up = [&](const std::vector<int32_t> &h, int32_t **d) -> int {
@@ -738,7 +791,7 @@ extern "C" int nlr_train_pack(NlrTrainPlan *p, const float *params_dev, void *st
 
 template <bool BWD>
 static int launch_train(const NlrTrainPlan *p, TrainParams &P, hipStream_t st) {
-    const uint32_t ntiles = (P.M + 127) / 128;
+    const uint32_t ntiles = (P.M - P.row0 + 127) / 128;
     dim3 grid(ntiles < p->cus ? ntiles : p->cus);
 #define NLR_TR(wt, ht)                                                                                              \
     if (p->W == wt * 32 && p->HT == ht) {                                                                           \
@@ -750,40 +803,128 @@ static int launch_train(const NlrTrainPlan *p, TrainParams &P, hipStream_t st) {
 #undef NLR_TR
     NLR_FAIL(NLR_ERR_UNSUPPORTED, "mlp_train: no kernel instance for view width %u with %u head units", p->W, p->HT);
 }
+// the trunk-and-heads instances (VIEW = false): one per head count, whatever the view width
+template <bool BWD>
+static int launch_train_trunk(const NlrTrainPlan *p, TrainParams &P, hipStream_t st) {
+    const uint32_t ntiles = (P.M - P.row0 + 127) / 128;
+    dim3 grid(ntiles < p->cus ? ntiles : p->cus);
+#define NLR_TR(ht)                                                                                                  \
+    if (p->HT == ht) {                                                                                              \
+        hipLaunchKernelGGL((nlr_mlp_train_kernel<4, 8, 2, ht, BWD, false>), grid, dim3(256), 0, st, P);              \
+        NLR_LAUNCH_CHECK("nlr_mlp_train_kernel (trunk and heads)");                                                  \
+        return NLR_OK;                                                                                              \
+    }
+    NLR_TR(4) NLR_TR(2) NLR_TR(0)
+#undef NLR_TR
+    NLR_FAIL(NLR_ERR_UNSUPPORTED, "mlp_train: no trunk-and-heads kernel instance for %u head units", p->HT);
+}
 
 static void fill_common(const NlrTrainPlan *p, TrainParams &P, uint32_t M, uint32_t S) {
     memset(&P, 0, sizeof(P));
-    P.M = M, P.S = S, P.F = p->F, P.depth = p->D, P.K = p->K, P.int_row = p->int_row, P.act_w = p->act_w;
+    P.M = M, P.ldm = M, P.row0 = 0, P.S = S, P.F = p->F, P.depth = p->D, P.K = p->K, P.int_row = p->int_row, P.act_w = p->act_w;
     P.density_bias = p->density_bias, P.rgb_premul = p->rgb_premul, P.rgb_bias = p->rgb_bias, P.rgb_padding = p->rgb_padding;
 }
 
-// features [M, F] f32 row-major, enc [M / S, 32]; outputs as nlr_mlp_level; acts [M, act_w] bf16
+// NLR_DBG_TRAIN_ROUTE / _TRUNK_ROW0 / _TRUNK_ROWS: which instances the last forward / backward call launched, and on which rows
+static void note_route(bool bwd, uint32_t M, uint32_t M_color) {
+    (void)nlr_debug_set(NLR_DBG_TRAIN_ROUTE, (M_color > 0 ? 1 : 0) | (M_color < M ? 2 : 0) | (bwd ? 4 : 0));
+    (void)nlr_debug_set(NLR_DBG_TRAIN_TRUNK_ROW0, (int)M_color);
+    (void)nlr_debug_set(NLR_DBG_TRAIN_TRUNK_ROWS, (int)(M - M_color));
+}
+#define NLR_CHECK_SPLIT(what)                                                                                                             \
+    NLR_CHECK_ARG(M > 0, what ": M is 0");                                                                                                \
+    NLR_CHECK_ARG(S > 0 && M % S == 0, what ": M = %u is not a multiple of S = %u (M %% S != 0)", M, S);                                  \
+    NLR_CHECK_ARG(M_color <= M, what ": M_color = %u exceeds M = %u (M_color > M)", M_color, M);                                          \
+    NLR_CHECK_ARG(M_color % S == 0, what ": M_color = %u is not a multiple of S = %u (M_color %% S != 0)", M_color, S)
+
+// features [M, F] f32 row-major, enc [M / S, 32]; outputs as nlr_mlp_level; acts [M, act_w] bf16.
+// Rows [0, M_color) through the full instance, rows [M_color, M) through the trunk-and-heads instance: two launches on one stream.
+static int train_forward(const NlrTrainPlan *p, const float *features, const float *enc, uint32_t M, uint32_t M_color, uint32_t S,
+                         float *density, float *rgb, float *semantic, float *intensity, void *acts, void *stream) {
+    TrainParams P;
+    fill_common(p, P, M, S);
+    P.feat = features, P.enc = enc;
+    P.bias_all = p->bias, P.bias_count = p->biasn;
+    P.density = density, P.rgb = rgb, P.sem = semantic, P.inten = p->inten ? intensity : nullptr;
+    P.acts = (__bf16 *)acts;
+    note_route(false, M, M_color);
+    if (M_color > 0) {
+        P.row0 = 0, P.M = M_color;
+        P.tape = (const uint4 *)p->ftape, P.tape_chunks = p->f0n / 16384;
+        if (const int rc = launch_train<false>(p, P, (hipStream_t)stream)) return rc;
+    }
+    if (M_color < M) {
+        P.row0 = M_color, P.M = M;
+        P.tape = (const uint4 *)(p->ftape + p->f1), P.tape_chunks = p->f1n / 16384;
+        if (const int rc = launch_train_trunk<false>(p, P, (hipStream_t)stream)) return rc;
+    }
+    return NLR_OK;
+}
+
 extern "C" int nlr_mlp_train_forward(const NlrTrainPlan *p, const float *features, const float *enc, uint32_t M, uint32_t S, float *density,
                                      float *rgb, float *semantic, float *intensity, void *acts, void *stream) {
     NLR_CHECK_ARG(p && features && enc && density && rgb && acts && M > 0 && S > 0, "mlp_train_forward: bad argument");
     NLR_CHECK_ARG((!p->sem || semantic) && (!p->inten || intensity), "mlp_train_forward: head output missing");
-    TrainParams P;
-    fill_common(p, P, M, S);
-    P.feat = features, P.enc = enc;
-    P.tape = (const uint4 *)p->ftape, P.tape_chunks = p->fn / 16384;
-    P.bias_all = p->bias, P.bias_count = p->biasn;
-    P.density = density, P.rgb = rgb, P.sem = semantic, P.inten = p->inten ? intensity : nullptr;
-    P.acts = (__bf16 *)acts;
-    return launch_train<false>(p, P, (hipStream_t)stream);
+    return train_forward(p, features, enc, M, M, S, density, rgb, semantic, intensity, acts, stream);
+}
+
+extern "C" int nlr_mlp_train_forward_split(const NlrTrainPlan *p, const float *features, const float *enc, uint32_t M, uint32_t M_color,
+                                           uint32_t S, float *density, float *rgb, float *semantic, float *intensity, void *acts,
+                                           void *stream) {
+    NLR_CHECK_ARG(p, "mlp_train_forward_split: plan is NULL");
+    NLR_CHECK_ARG(features, "mlp_train_forward_split: features is NULL");
+    NLR_CHECK_ARG(enc, "mlp_train_forward_split: enc is NULL");
+    NLR_CHECK_ARG(density, "mlp_train_forward_split: density is NULL");
+    NLR_CHECK_ARG(rgb, "mlp_train_forward_split: rgb is NULL");
+    NLR_CHECK_ARG(acts, "mlp_train_forward_split: acts is NULL");
+    NLR_CHECK_ARG(!p->sem || semantic, "mlp_train_forward_split: semantic is NULL");
+    NLR_CHECK_ARG(!p->inten || intensity, "mlp_train_forward_split: intensity is NULL");
+    NLR_CHECK_SPLIT("mlp_train_forward_split");
+    return train_forward(p, features, enc, M, M_color, S, density, rgb, semantic, intensity, acts, stream);
 }
 
 // upstream gradients in the layouts of the outputs (any may be NULL); gacts [M, act_w + 64] bf16, d_features [M, F] f32
-extern "C" int nlr_mlp_train_backward(const NlrTrainPlan *p, uint32_t M, uint32_t S, const float *density, const float *rgb, const float *semantic,
-                                      const void *acts, const float *g_density, const float *g_rgb, const float *g_semantic,
-                                      const float *g_intensity, void *gacts, float *d_features, void *stream) {
-    NLR_CHECK_ARG(p && density && rgb && acts && gacts && d_features && M > 0 && S > 0, "mlp_train_backward: bad argument");
+static int train_backward(const NlrTrainPlan *p, uint32_t M, uint32_t M_color, uint32_t S, const float *density, const float *rgb,
+                          const float *semantic, const void *acts, const float *g_density, const float *g_rgb, const float *g_semantic,
+                          const float *g_intensity, void *gacts, float *d_features, void *stream) {
     TrainParams P;
     fill_common(p, P, M, S);
-    P.tape = (const uint4 *)p->btape, P.tape_chunks = p->bn / 16384;
     P.density = const_cast<float *>(density), P.rgb = const_cast<float *>(rgb), P.sem = const_cast<float *>(semantic);
     P.acts = (__bf16 *)const_cast<void *>(acts);
     P.g_density = g_density, P.g_rgb = g_rgb, P.g_sem = (p->sem && semantic) ? g_semantic : nullptr, P.g_inten = p->inten ? g_intensity : nullptr;
     P.gacts = (__bf16 *)gacts;
     P.d_feat = d_features;
-    return launch_train<true>(p, P, (hipStream_t)stream);
+    note_route(true, M, M_color);
+    if (M_color > 0) {
+        P.row0 = 0, P.M = M_color;
+        P.tape = (const uint4 *)p->btape, P.tape_chunks = p->b0n / 16384;
+        if (const int rc = launch_train<true>(p, P, (hipStream_t)stream)) return rc;
+    }
+    if (M_color < M) {
+        P.row0 = M_color, P.M = M;
+        P.tape = (const uint4 *)(p->btape + p->b1), P.tape_chunks = p->b1n / 16384;
+        if (const int rc = launch_train_trunk<true>(p, P, (hipStream_t)stream)) return rc;
+    }
+    return NLR_OK;
+}
+
+extern "C" int nlr_mlp_train_backward(const NlrTrainPlan *p, uint32_t M, uint32_t S, const float *density, const float *rgb, const float *semantic,
+                                      const void *acts, const float *g_density, const float *g_rgb, const float *g_semantic,
+                                      const float *g_intensity, void *gacts, float *d_features, void *stream) {
+    NLR_CHECK_ARG(p && density && rgb && acts && gacts && d_features && M > 0 && S > 0, "mlp_train_backward: bad argument");
+    return train_backward(p, M, M, S, density, rgb, semantic, acts, g_density, g_rgb, g_semantic, g_intensity, gacts, d_features, stream);
+}
+
+extern "C" int nlr_mlp_train_backward_split(const NlrTrainPlan *p, uint32_t M, uint32_t M_color, uint32_t S, const float *density,
+                                            const float *rgb, const float *semantic, const void *acts, const float *g_density,
+                                            const float *g_rgb, const float *g_semantic, const float *g_intensity, void *gacts,
+                                            float *d_features, void *stream) {
+    NLR_CHECK_ARG(p, "mlp_train_backward_split: plan is NULL");
+    NLR_CHECK_ARG(density, "mlp_train_backward_split: density is NULL");
+    NLR_CHECK_ARG(rgb, "mlp_train_backward_split: rgb is NULL");
+    NLR_CHECK_ARG(acts, "mlp_train_backward_split: acts is NULL");
+    NLR_CHECK_ARG(gacts, "mlp_train_backward_split: gacts is NULL");
+    NLR_CHECK_ARG(d_features, "mlp_train_backward_split: d_features is NULL");
+    NLR_CHECK_SPLIT("mlp_train_backward_split");
+    return train_backward(p, M, M_color, S, density, rgb, semantic, acts, g_density, g_rgb, g_semantic, g_intensity, gacts, d_features, stream);
 }

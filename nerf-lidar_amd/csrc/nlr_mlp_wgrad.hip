@@ -39,11 +39,12 @@ struct WgJob {
     uint16_t n_in;            // valid columns of the input block (<= 128)
     uint16_t dst_ld;          // `in` of the Linear
     uint16_t has_bias;
+    uint16_t color;           // 1: a view layer or rgb_layer, reduced over the rows with colour supervision [0, M_color) only
     uint32_t dst, bias;       // offsets into d_params of dW[first row][first column] and of db[first row]
 };
 
 struct WgParams {
-    uint32_t M, S, F, E, ld_a, ld_g, n_slices, chunks_per_slice, n_chunks, n_params;
+    uint32_t M, M_color, S, F, E, ld_a, ld_g, n_slices, n_params;
     const float *feat, *enc;
     const __bf16 *acts, *gacts;
     float *slab;
@@ -75,8 +76,12 @@ __global__ void __launch_bounds__(256, 2) nlr_mlp_wgrad_kernel(WgParams P) {
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // uniform
     const uint32_t x_src = J.x_src;
     const uint32_t oh = wave >> 1, ih = wave & 1;
-    const uint32_t c_begin = slice * P.chunks_per_slice;
-    const uint32_t c_end = min(c_begin + P.chunks_per_slice, P.n_chunks);
+    // this job's rows [0, Mj) in chunks, dealt to the n_slices slabs front to back; a slice (or a whole job: M_color = 0) without
+    // rows runs no chunk and writes its zero accumulators, so the reduce reads defined memory everywhere
+    const uint32_t Mj = J.color ? P.M_color : P.M;
+    const uint32_t n_chunks = (Mj + NLR_WG_CH - 1) / NLR_WG_CH, chunks_per_slice = (n_chunks + P.n_slices - 1) / P.n_slices;
+    const uint32_t c_begin = min(slice * chunks_per_slice, n_chunks);
+    const uint32_t c_end = min(c_begin + chunks_per_slice, n_chunks);
     const f32x4 zero4 = {0.0f, 0.0f, 0.0f, 0.0f};
     const u32x4 zero16 = {0u, 0u, 0u, 0u};
 
@@ -89,21 +94,21 @@ __global__ void __launch_bounds__(256, 2) nlr_mlp_wgrad_kernel(WgParams P) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const uint32_t m = m0 + 16 * k;
-            rg[k] = (m < P.M && g_on) ? *reinterpret_cast<const u32x4 *>(P.gacts + (size_t)m * P.ld_g + J.g_col + 8 * unit) : zero16;
+            rg[k] = (m < Mj && g_on) ? *reinterpret_cast<const u32x4 *>(P.gacts + (size_t)m * P.ld_g + J.g_col + 8 * unit) : zero16;
         }
         if (x_src == 0) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const uint32_t m = m0 + 16 * k;
-                rx[k] = (m < P.M && x_on) ? *reinterpret_cast<const u32x4 *>(P.acts + (size_t)m * P.ld_a + J.x_col + 8 * unit) : zero16;
+                rx[k] = (m < Mj && x_on) ? *reinterpret_cast<const u32x4 *>(P.acts + (size_t)m * P.ld_a + J.x_col + 8 * unit) : zero16;
             }
         } else if (x_src == 1) {  // grid features, f32: 8 unit < n_in = F and F % 4 == 0
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const uint32_t m = m0 + 16 * k;
                 const float *f = P.feat + (size_t)m * P.F + 8 * unit;
-                const f32x4 a = (m < P.M && x_on) ? *reinterpret_cast<const f32x4 *>(f) : zero4;
-                const f32x4 b = (m < P.M && 8 * unit + 4 < J.n_in) ? *reinterpret_cast<const f32x4 *>(f + 4) : zero4;
+                const f32x4 a = (m < Mj && x_on) ? *reinterpret_cast<const f32x4 *>(f) : zero4;
+                const f32x4 b = (m < Mj && 8 * unit + 4 < J.n_in) ? *reinterpret_cast<const f32x4 *>(f + 4) : zero4;
                 rx[k] = nlr_pack8(a, b);
             }
         } else {  // direction encoding of the sample's ray, f32 [M / S, 32]: 8 unit < E <= 32
@@ -112,7 +117,7 @@ __global__ void __launch_bounds__(256, 2) nlr_mlp_wgrad_kernel(WgParams P) {
                 const uint32_t m = m0 + 16 * k;
                 const float *e = P.enc + (size_t)(m / P.S) * 32 + 8 * unit;
                 f32x4 a = zero4, b = zero4;
-                if (m < P.M && x_on) a = *reinterpret_cast<const f32x4 *>(e), b = *reinterpret_cast<const f32x4 *>(e + 4);
+                if (m < Mj && x_on) a = *reinterpret_cast<const f32x4 *>(e), b = *reinterpret_cast<const f32x4 *>(e + 4);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     a[i] = 8 * unit + i < P.E ? a[i] : 0.0f;
@@ -222,25 +227,26 @@ static int build_jobs(const NlrTrainPlan *p, WgJob *jobs, uint32_t *n_jobs) {
         uint32_t g_col, o_off, n_out;
         WgBlock b[3];
         uint32_t nb;
+        uint32_t color;  // a view layer or rgb_layer
     };
     std::vector<L> ls;
     const WgBlock hbe = {0, c_hbe, WB}, encb = {2, 0, p->E};
-    ls.push_back({c_hid, 0, 64, {{1, 0, p->F}}, 1});
-    ls.push_back({c_hbe, 0, WB, {{0, c_hid, 64}}, 1});
+    ls.push_back({c_hid, 0, 64, {{1, 0, p->F}}, 1, 0});
+    ls.push_back({c_hbe, 0, WB, {{0, c_hid, 64}}, 1, 0});
     uint32_t r0 = 0;
     if (p->sem) {
-        ls.push_back({c_q, 0, 64, {hbe}, 1});
-        ls.push_back({aw, 0, K, {{0, c_q, 64}}, 1});
+        ls.push_back({c_q, 0, 64, {hbe}, 1, 0});
+        ls.push_back({aw, 0, K, {{0, c_q, 64}}, 1, 0});
         r0 = 64;
     }
     if (p->inten) {
-        ls.push_back({c_q + r0, 0, 64, {hbe}, 1});
-        ls.push_back({aw, K, 1, {{0, c_q + r0, 64}}, 1});
+        ls.push_back({c_q + r0, 0, 64, {hbe}, 1, 0});
+        ls.push_back({aw, K, 1, {{0, c_q + r0, 64}}, 1, 0});
     }
-    ls.push_back({c_x, 0, W, {hbe, encb}, 2});
-    ls.push_back({c_x + W, 0, W, {{0, c_x, W}, hbe, encb}, 3});
-    for (uint32_t l = 2; l < D; ++l) ls.push_back({c_x + l * W, 0, W, {{0, c_x + (l - 1) * W, W}}, 1});
-    ls.push_back({aw + 32, 0, 3, {{0, c_x + (D - 1) * W, W}}, 1});
+    ls.push_back({c_x, 0, W, {hbe, encb}, 2, 1});
+    ls.push_back({c_x + W, 0, W, {{0, c_x, W}, hbe, encb}, 3, 1});
+    for (uint32_t l = 2; l < D; ++l) ls.push_back({c_x + l * W, 0, W, {{0, c_x + (l - 1) * W, W}}, 1, 1});
+    ls.push_back({aw + 32, 0, 3, {{0, c_x + (D - 1) * W, W}}, 1, 1});
     if (2 * ls.size() != p->offs.size()) return NLR_ERR_INVALID;
     n = 0;
     for (size_t q = 0; q < ls.size(); ++q) {
@@ -261,6 +267,7 @@ static int build_jobs(const NlrTrainPlan *p, WgJob *jobs, uint32_t *n_jobs) {
                     j.x_src = (uint16_t)l.b[k].src, j.x_col = (uint16_t)(l.b[k].col + c), j.n_in = (uint16_t)cols;
                     j.dst_ld = (uint16_t)n_in_total;
                     j.has_bias = first ? 1 : 0;
+                    j.color = (uint16_t)l.color;
                     j.dst = w_off + o0 * n_in_total + i0 + c;
                     j.bias = b_off + o0;
                     first = false;
@@ -279,29 +286,16 @@ extern "C" size_t nlr_mlp_train_wgrad_workspace_bytes(const NlrTrainPlan *p, uin
     return p ? (size_t)NLR_WG_SLICES * p->n_params * sizeof(float) : 0;
 }
 
-extern "C" int nlr_mlp_train_wgrad(const NlrTrainPlan *p, uint32_t M, uint32_t S, const float *features, const float *enc, const void *acts,
-                                   const void *gacts, float *d_params, void *workspace, size_t workspace_bytes, void *stream) {
-    NLR_CHECK_ARG(p, "mlp_train_wgrad: plan is NULL");
-    NLR_CHECK_ARG(features, "mlp_train_wgrad: features is NULL");
-    NLR_CHECK_ARG(enc, "mlp_train_wgrad: enc is NULL");
-    NLR_CHECK_ARG(acts, "mlp_train_wgrad: acts is NULL");
-    NLR_CHECK_ARG(gacts, "mlp_train_wgrad: gacts is NULL");
-    NLR_CHECK_ARG(d_params, "mlp_train_wgrad: d_params is NULL");
-    NLR_CHECK_ARG(workspace, "mlp_train_wgrad: workspace is NULL");
-    NLR_CHECK_ARG(M > 0, "mlp_train_wgrad: M is 0");
-    NLR_CHECK_ARG(S > 0 && M % S == 0, "mlp_train_wgrad: M = %u is not a multiple of S = %u (M %% S != 0)", M, S);
-    const size_t need = nlr_mlp_train_wgrad_workspace_bytes(p, M);
-    if (workspace_bytes < need)
-        NLR_FAIL(NLR_ERR_WORKSPACE, "mlp_train_wgrad: workspace_bytes %zu B < nlr_mlp_train_wgrad_workspace_bytes() = %zu B", workspace_bytes, need);
+static int train_wgrad(const NlrTrainPlan *p, uint32_t M, uint32_t M_color, uint32_t S, const float *features, const float *enc,
+                       const void *acts, const void *gacts, float *d_params, void *workspace, void *stream) {
     WgParams P;
     memset(&P, 0, sizeof(P));
     uint32_t n_jobs = 0;
     const int rc = build_jobs(p, P.jobs, &n_jobs);
     if (rc != NLR_OK || n_jobs == 0) NLR_FAIL(rc ? rc : NLR_ERR_UNSUPPORTED, "mlp_train_wgrad: no job list for this plan");
-    P.M = M, P.S = S, P.F = p->F, P.E = p->E, P.ld_a = p->act_w, P.ld_g = p->act_w + 64, P.n_params = p->n_params;
-    P.n_chunks = (M + NLR_WG_CH - 1) / NLR_WG_CH;
-    P.n_slices = P.n_chunks < NLR_WG_SLICES ? P.n_chunks : NLR_WG_SLICES;
-    P.chunks_per_slice = (P.n_chunks + P.n_slices - 1) / P.n_slices;
+    P.M = M, P.M_color = M_color, P.S = S, P.F = p->F, P.E = p->E, P.ld_a = p->act_w, P.ld_g = p->act_w + 64, P.n_params = p->n_params;
+    const uint32_t n_chunks = (M + NLR_WG_CH - 1) / NLR_WG_CH;
+    P.n_slices = n_chunks < NLR_WG_SLICES ? n_chunks : NLR_WG_SLICES;  // by M: the slab layout is the same for every job
     P.feat = features, P.enc = enc, P.acts = (const __bf16 *)acts, P.gacts = (const __bf16 *)gacts;
     P.slab = (float *)workspace;
     hipStream_t st = (hipStream_t)stream;
@@ -311,4 +305,37 @@ extern "C" int nlr_mlp_train_wgrad(const NlrTrainPlan *p, uint32_t M, uint32_t S
                        p->n_params, d_params);
     NLR_LAUNCH_CHECK("nlr_mlp_wgrad_reduce_kernel");
     return NLR_OK;
+}
+
+#define NLR_WGRAD_ARGS(what)                                                                                                               \
+    NLR_CHECK_ARG(p, what ": plan is NULL");                                                                                               \
+    NLR_CHECK_ARG(features, what ": features is NULL");                                                                                    \
+    NLR_CHECK_ARG(enc, what ": enc is NULL");                                                                                              \
+    NLR_CHECK_ARG(acts, what ": acts is NULL");                                                                                            \
+    NLR_CHECK_ARG(gacts, what ": gacts is NULL");                                                                                          \
+    NLR_CHECK_ARG(d_params, what ": d_params is NULL");                                                                                    \
+    NLR_CHECK_ARG(workspace, what ": workspace is NULL");                                                                                  \
+    NLR_CHECK_ARG(M > 0, what ": M is 0");                                                                                                 \
+    NLR_CHECK_ARG(S > 0 && M % S == 0, what ": M = %u is not a multiple of S = %u (M %% S != 0)", M, S)
+#define NLR_WGRAD_WORKSPACE(what)                                                                                                          \
+    const size_t need = nlr_mlp_train_wgrad_workspace_bytes(p, M);                                                                         \
+    if (workspace_bytes < need)                                                                                                            \
+        NLR_FAIL(NLR_ERR_WORKSPACE, what ": workspace_bytes %zu B < nlr_mlp_train_wgrad_workspace_bytes() = %zu B", workspace_bytes, need)
+
+extern "C" int nlr_mlp_train_wgrad(const NlrTrainPlan *p, uint32_t M, uint32_t S, const float *features, const float *enc, const void *acts,
+                                   const void *gacts, float *d_params, void *workspace, size_t workspace_bytes, void *stream) {
+    NLR_WGRAD_ARGS("mlp_train_wgrad");
+    NLR_WGRAD_WORKSPACE("mlp_train_wgrad");
+    return train_wgrad(p, M, M, S, features, enc, acts, gacts, d_params, workspace, stream);
+}
+
+// view-layer and rgb_layer jobs reduce over rows [0, M_color) and never read a later row of acts / gacts; the others over all M
+extern "C" int nlr_mlp_train_wgrad_split(const NlrTrainPlan *p, uint32_t M, uint32_t M_color, uint32_t S, const float *features,
+                                         const float *enc, const void *acts, const void *gacts, float *d_params, void *workspace,
+                                         size_t workspace_bytes, void *stream) {
+    NLR_WGRAD_ARGS("mlp_train_wgrad_split");
+    NLR_CHECK_ARG(M_color <= M, "mlp_train_wgrad_split: M_color = %u exceeds M = %u (M_color > M)", M_color, M);
+    NLR_CHECK_ARG(M_color % S == 0, "mlp_train_wgrad_split: M_color = %u is not a multiple of S = %u (M_color %% S != 0)", M_color, S);
+    NLR_WGRAD_WORKSPACE("mlp_train_wgrad_split");
+    return train_wgrad(p, M, M_color, S, features, enc, acts, gacts, d_params, workspace, stream);
 }

@@ -88,11 +88,16 @@ EXPORTS = ["nlr_last_error", "nlr_version", "nlr_build_sha", "nlr_debug_set", "n
            "nlr_encode_features_backward", "nlr_encode_features_backward_ws", "nlr_grid_encode_backward_ws", "nlr_grid_backward_workspace_bytes",
            "nlr_train_plan_create", "nlr_train_plan_destroy", "nlr_train_act_width", "nlr_train_param_layout", "nlr_train_pack",
            "nlr_mlp_train_forward", "nlr_mlp_train_backward", "nlr_mlp_train_wgrad_workspace_bytes", "nlr_mlp_train_wgrad",
+           "nlr_mlp_train_forward_split", "nlr_mlp_train_backward_split", "nlr_mlp_train_wgrad_split",
            "nlr_render_lidar", "nlr_render_lidar_dynamic"]
 NLR_K_COUNT = 6
 DBG_FORCE_GENERIC, DBG_MLP_WORKGROUPS, DBG_BINNED_C4, DBG_NO_XPAIR_SCATTER, DBG_SCATTER_LEVELS, DBG_NO_SCATTER_CACHE, DBG_RAY_GROUPS = 0, 1, 2, 3, 4, 5, 6
 DBG_LAST_ROUTE = 7  # read-back (nlr_debug_get): how the last level of the most recent render ran
 ROUTE_FULL, ROUTE_FULL_FUSED, ROUTE_LIDAR, ROUTE_LIDAR_FUSED = 1, 2, 3, 4
+# read-backs of the most recent nlr_mlp_train_forward / _backward (or _split) call: route = TRAIN_FULL | TRAIN_TRUNK | TRAIN_BWD, and
+# the first row / row count the trunk-and-heads instance ran on
+DBG_TRAIN_ROUTE, DBG_TRAIN_TRUNK_ROW0, DBG_TRAIN_TRUNK_ROWS = 8, 9, 10
+TRAIN_FULL, TRAIN_TRUNK, TRAIN_BWD = 1, 2, 4
 
 
 def lib():
@@ -181,6 +186,9 @@ def lib():
         L.nlr_mlp_train_wgrad_workspace_bytes.restype = C.c_size_t
         L.nlr_mlp_train_wgrad_workspace_bytes.argtypes = [c_fp, C.c_uint32]
         L.nlr_mlp_train_wgrad.argtypes = [c_fp, C.c_uint32, C.c_uint32] + [c_fp] * 6 + [C.c_size_t, c_fp]
+        L.nlr_mlp_train_forward_split.argtypes = [c_fp, c_fp, c_fp, C.c_uint32, C.c_uint32, C.c_uint32, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]
+        L.nlr_mlp_train_backward_split.argtypes = [c_fp, C.c_uint32, C.c_uint32, C.c_uint32] + [c_fp] * 11
+        L.nlr_mlp_train_wgrad_split.argtypes = [c_fp, C.c_uint32, C.c_uint32, C.c_uint32] + [c_fp] * 6 + [C.c_size_t, c_fp]
         L.nlr_profile_begin.argtypes = [c_fp]
         L.nlr_profile_begin_kinds.argtypes = [c_fp, C.c_uint32]
         L.nlr_profile_end.argtypes = [c_fp, c_fp, c_fp, c_fp]

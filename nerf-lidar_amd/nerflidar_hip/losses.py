@@ -186,6 +186,22 @@ def nusc_masks(batch: Dict[str, torch.Tensor], lidar_supervision: bool = False, 
     return dict(mask_rgb=rgb, depth_mask=depth, sem_mask=sem, lidar_mask=lidar)
 
 
+def colourless_count(n_rays: int, fraction: float) -> int:
+    """Number of trailing rays without colour supervision for a `--colourless-fraction`: round(fraction * n_rays), fraction in [0, 1]."""
+    if not 0.0 <= fraction <= 1.0:
+        raise ValueError(f"colourless fraction must lie in [0, 1], got {fraction}")
+    return int(round(fraction * n_rays))
+
+
+def check_colourless(batch: Dict[str, torch.Tensor], color_rays: int) -> None:
+    """Debug check of the caller's promise behind `color_rays`: `mask_rgb` is zero on the rays [color_rays, N).  Reads the mask back
+    (a host synchronisation), so `training_step` calls it only on request."""
+    m = batch.get("mask_rgb")
+    if m is None or bool(m.reshape(-1)[color_rays:].to(torch.bool).any()):
+        raise ValueError(f"color_rays = {color_rays}: batch['mask_rgb'] must be zero on the rays from {color_rays} on "
+                         "(their colour would be supervised but is not computed)")
+
+
 def total_loss(renderings: List[Dict[str, torch.Tensor]], ray_history: List[Dict[str, torch.Tensor]], batch: Dict[str, torch.Tensor], *,
                data_kind: str = "charb", charb_padding: float = 1e-3, data_coarse_mult: float = 0.0, data_mult: float = 1.0,
                interlevel_mult: float = 0.0, anti_interlevel_mult: float = 0.01, pulse_width: Sequence[float] = (0.03, 0.003),

@@ -150,13 +150,20 @@ def random_lidar_rays(n: int, seed: int, step: int, device, rot_seed: int = 0, s
                 semantic=torch.full((n,), 255.0, device=dev), mask=torch.ones(n, device=dev))
 
 
-def supervise(batch: Dict[str, torch.Tensor], rot_seed: int = 0, scale_factor: float = 1.0 / 250.0) -> Dict[str, torch.Tensor]:
+def supervise(batch: Dict[str, torch.Tensor], rot_seed: int = 0, scale_factor: float = 1.0 / 250.0, colourless: int = 0) -> Dict[str, torch.Tensor]:
     """Adds the supervision keys train.py:283-424 reads for LiDAR rays (`rgb`, `depth`, `semantic`, `intensity`, and the masks
-    `losses.total_loss` takes) to a ray batch, from the analytic scene."""
+    `losses.total_loss` takes) to a ray batch, from the analytic scene.  colourless: the last that many rays get `mask_rgb` =
+    `sem_mask` = False, as train.py:316-320 sets them for the LiDAR rays at the end of a mixed batch (depth and intensity stay
+    supervised); pass `color_rays = N - colourless` to `training.training_step` with such a batch."""
     n = batch["origins"].shape[0]
     gt = cast(batch["origins"].reshape(n, 3), batch["directions"].reshape(n, 3), nlidar.seeded_rotation(rot_seed), scale_factor)
     out = dict(batch)
     ones = torch.ones(n, dtype=torch.bool, device=gt["depth"].device)
     out.update(rgb=gt["rgb"], depth=gt["depth"], semantic=gt["semantic"], intensity=gt["intensity"], mask_rgb=ones, depth_mask=ones,
                sem_mask=ones, lidar_mask=ones)
+    if colourless:
+        if not 0 <= colourless <= n:
+            raise ValueError(f"colourless must lie in [0, {n}], got {colourless}")
+        keep = torch.arange(n, device=ones.device) < n - colourless
+        out.update(mask_rgb=keep, sem_mask=keep)
     return out

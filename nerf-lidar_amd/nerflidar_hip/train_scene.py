@@ -43,7 +43,7 @@ def evaluate(model, scale_factor: float, sweep_idx: int = 100, width: int = 1024
     return out
 
 
-def main(argv=None) -> int:
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--workload", default="REFI", help="architecture (nerflidar_hip.config.workload): REF, REFI, C2, ...")
     ap.add_argument("--log2-hashmap", type=int, default=None, help="hash-map size of all three grids (default: the gin value 21)")
@@ -63,9 +63,22 @@ def main(argv=None) -> int:
     ap.add_argument("--out", required=True, help="checkpoint directory")
     ap.add_argument("--log-every", type=int, default=200)
     ap.add_argument("--eval-every", type=int, default=0, help="also render the held-out sweep on the fused inference path every this many steps")
+    ap.add_argument("--colourless-fraction", type=float, default=0.0,
+                    help="the last round(F * rays) rays of every batch carry no colour or semantic supervision (mask_rgb = sem_mask = 0, as "
+                         "train.py:316-320 sets them for LiDAR rays) and skip the view MLP (training_step(color_rays=..)); 0: off")
+    return ap
+
+
+def main(argv=None) -> int:
+    from .losses import colourless_count
+    ap = build_parser()
     a = ap.parse_args(argv)
     if a.fused_wgrad and not a.fused:
         ap.error("--fused-wgrad requires --fused 1")
+    if not 0.0 <= a.colourless_fraction <= 1.0:
+        ap.error("--colourless-fraction must lie in [0, 1]")
+    colourless = colourless_count(a.rays, a.colourless_fraction)
+    color_rays = a.rays - colourless if colourless else None
     if not torch.cuda.is_available():
         raise RuntimeError("train_scene needs a GPU: the training operators have no CPU fallback")
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -79,10 +92,11 @@ def main(argv=None) -> int:
     for step in range(1, a.steps + 1):                                     # train.py:180: steps count from 1
         for g in opt.param_groups:
             g["lr"] = lr_fn(step)                                          # train.py:187-190
-        batch = nscene.supervise(nscene.random_lidar_rays(a.rays, a.seed, step, dev, a.seed, a.scale_factor), a.seed, a.scale_factor)
+        batch = nscene.supervise(nscene.random_lidar_rays(a.rays, a.seed, step, dev, a.seed, a.scale_factor), a.seed, a.scale_factor,
+                                 colourless=colourless)
         train_frac = float(np.clip((step - 1) / max(a.steps - 1, 1), 0, 1))  # train.py:184
         terms = ntrain.training_step(tm, opt, batch, train_frac=train_frac, randomized=True, hash_decay_mult=a.hash_decay,
-                                     depth_lam=a.depth_lam, sem_lam=a.sem_lam, as_tensors=True)
+                                     depth_lam=a.depth_lam, sem_lam=a.sem_lam, as_tensors=True, color_rays=color_rays)
         if step % a.log_every == 0 or step == 1 or step == a.steps:          # the only host read of the loop
             torch.cuda.synchronize()
             rec = dict(step=step, lr=lr_fn(step), elapsed_s=round(time.time() - t0, 1), **{k: round(float(v), 6) for k, v in terms.items()})
@@ -99,7 +113,7 @@ def main(argv=None) -> int:
     model, step, ignored = nckpt.model_from_checkpoint(a.out, base=mc)
     ev = evaluate(model, a.scale_factor, seed=a.seed)
     summary = dict(workload=a.workload, log2_hashmap=a.log2_hashmap, steps=a.steps, rays_per_step=a.rays, fused=bool(a.fused), fused_wgrad=a.fused_wgrad,
-                   train_seconds=round(train_s, 1), train_rays_per_s=round(a.steps * a.rays / train_s), checkpoint=path,
+                   colourless_fraction=a.colourless_fraction, train_seconds=round(train_s, 1), train_rays_per_s=round(a.steps * a.rays / train_s), checkpoint=path,
                    checkpoint_bytes=os.path.getsize(path), restored_step=step, held_out_sweep=ev, final_terms=log[-1])
     print(json.dumps(summary), flush=True)
     with open(os.path.join(a.out, "train_summary.json"), "w") as f:

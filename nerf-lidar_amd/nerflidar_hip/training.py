@@ -244,10 +244,21 @@ def encode_features_fused(encoder, batch, tdist, sample_n: int = 7, sample_m: in
 
 
 # ---- fused NerfMLP for training: nlr_mlp_train_forward / nlr_mlp_train_backward (csrc/nlr_mlp_train.hip) ---------------------------
-def _wgrad_bmm(level, M, f, e, acts, gacts):
+def _check_color_rays(color_rays, n: int) -> Optional[int]:
+    """`color_rays` of `TrainableNerfLevel.forward`: None, or an integer 0 <= color_rays <= n (the number of rays)."""
+    if color_rays is None:
+        return None
+    if isinstance(color_rays, bool) or not isinstance(color_rays, (int, np.integer)) or not 0 <= int(color_rays) <= n:
+        raise ValueError(f"color_rays must be None or an integer in [0, {n}] (the rays [color_rays, {n}) carry no colour supervision), "
+                         f"got {color_rays!r}")
+    return int(color_rays)
+
+
+def _wgrad_bmm(level, M, f, e, acts, gacts, M_color=None):
     """The weight and bias gradients of the fused NerfMLP as split-K library GEMMs over the tensors the kernels saved: the list
     [dW, db, dW, db, ..] in the order of `TrainableNerfLevel._mlp_params`.  `_FusedMLP.backward` without `fused_wgrad` and
-    `scripts/wgrad_bench.py` call this same code."""
+    `scripts/wgrad_bench.py` call this same code.  M_color (rows, None = M): the view layers and rgb_layer reduce over the first
+    M_color rows only - the split kernels leave their columns of the later rows unwritten."""
     plan, cfg = level._plan, level.cfg
     dev = f.device
     K = cfg.class_num if cfg.use_semantic else 0
@@ -263,24 +274,33 @@ def _wgrad_bmm(level, M, f, e, acts, gacts):
     # [M, out]^T . [M, in_0 | in_1 | ..]: bf16 operands, f32 accumulation.  The reduction runs over M (10^5..10^6) into a
     # 256 x 256 result: as ONE library GEMM that is 16 output tiles = 16 busy CUs, so M is cut into `ck` batches (split-K as a
     # batched GEMM over strided views, no copies) whose partial results are summed in f32.
-    ck = 1
-    while ck < 128 and M % (2 * ck) == 0 and M // (2 * ck) >= 2048:
-        ck *= 2
-
-    def wgrad(gy, *xs):
-        gb = gy.reshape(ck, M // ck, gy.shape[1]).transpose(1, 2)
-        return torch.cat([torch.bmm(gb, x.reshape(ck, M // ck, x.shape[1])).float().sum(0) for x in xs], 1)
-
     grads = []
 
-    ones = torch.ones(ck, 1, M // ck, device=dev, dtype=torch.bfloat16)
+    def linear_over(Mr):
+        """`lin` over the first Mr rows, with the split-K factor chosen from that row count."""
+        ck = 1
+        while ck < 128 and Mr % (2 * ck) == 0 and Mr // (2 * ck) >= 2048:
+            ck *= 2
 
-    def lin(gy, *xs):
-        grads.append(wgrad(gy, *xs))
-        # bias gradient = 1^T gy, through the same split-K batched GEMM (a column reduction of a strided [M, out] view runs at
-        # a tenth of the memory bandwidth as an elementwise reduce kernel)
-        grads.append(torch.bmm(ones, gy.reshape(ck, M // ck, gy.shape[1])).float().sum(0)[0])
+        def wgrad(gy, *xs):
+            gb = gy[:Mr].reshape(ck, Mr // ck, gy.shape[1]).transpose(1, 2)
+            return torch.cat([torch.bmm(gb, x[:Mr].reshape(ck, Mr // ck, x.shape[1])).float().sum(0) for x in xs], 1)
 
+        ones = torch.ones(ck, 1, Mr // ck, device=dev, dtype=torch.bfloat16) if Mr else None
+
+        def lin(gy, *xs):
+            if Mr == 0:  # no row: zeros, as the kernel's rule for a NULL upstream gradient
+                grads.append(torch.zeros(gy.shape[1], sum(x.shape[1] for x in xs), device=dev))
+                grads.append(torch.zeros(gy.shape[1], device=dev))
+                return
+            grads.append(wgrad(gy, *xs))
+            # bias gradient = 1^T gy, through the same split-K batched GEMM (a column reduction of a strided [M, out] view runs at
+            # a tenth of the memory bandwidth as an elementwise reduce kernel)
+            grads.append(torch.bmm(ones, gy[:Mr].reshape(ck, Mr // ck, gy.shape[1])).float().sum(0)[0])
+
+        return lin
+
+    lin = linear_over(M)
     lin(g(c_hid, 64), f.to(torch.bfloat16))
     lin(g(c_hbe, WB), a(c_hid, 64))
     r0 = 0
@@ -291,6 +311,8 @@ def _wgrad_bmm(level, M, f, e, acts, gacts):
     if cfg.use_intensity:
         lin(g(c_q + r0, 64), a(c_hbe, WB))
         lin(g(plan.act_w + K, 1), a(c_q + r0, 64))
+    if M_color is not None and M_color != M:
+        lin = linear_over(M_color)
     lin(g(c_x, W), a(c_hbe, WB), enc_s)
     if D > 1:
         lin(g(c_x + W, W), a(c_x, W), a(c_hbe, WB), enc_s)
@@ -303,12 +325,15 @@ def _wgrad_bmm(level, M, f, e, acts, gacts):
 class _FusedMLP(torch.autograd.Function):
     """The Linear stack of ZI/models.py:1116-1251 (density trunk, heads, view MLP, rgb) as two MFMA-chain kernels.  The weight
     gradients are GEMMs over the tensors those kernels save: dW_l = (d pre-activation_l)^T . (input_l), M-long reductions: library
-    GEMMs (`_wgrad_bmm`) or, with `fused_wgrad`, `nlr_mlp_train_wgrad` (csrc/nlr_mlp_wgrad.hip)."""
+    GEMMs (`_wgrad_bmm`) or, with `fused_wgrad`, `nlr_mlp_train_wgrad` (csrc/nlr_mlp_wgrad.hip).  With `level._color_rays` (an
+    integer, `TrainableNerfLevel.forward(color_rays=..)`) the three `_split` entry points: the rows of the later rays run the trunk
+    and the heads only."""
 
     @staticmethod
     def forward(ctx, feats, enc, level, *params):
         plan = level._plan
         M, S = feats.shape[0], level._S
+        Mc = None if level._color_rays is None else level._color_rays * S
         dev = feats.device
         flat = torch.cat([p.detach().reshape(-1).float() for p in params])
         new = lambda *s, dtype=torch.float32: torch.empty(*s, device=dev, dtype=dtype)
@@ -323,9 +348,13 @@ class _FusedMLP(torch.autograd.Function):
         with torch.cuda.device(dev):
             st = _lib.current_stream()
             _lib.check(L.nlr_train_pack(plan.handle, _lib.ptr(flat), st), "nlr_train_pack")
-            _lib.check(L.nlr_mlp_train_forward(plan.handle, _lib.ptr(f), _lib.ptr(e), M, S, _lib.ptr(density), _lib.ptr(rgb), _lib.ptr(sem),
-                                               _lib.ptr(inten), _lib.ptr(acts), st), "nlr_mlp_train_forward")
-        ctx.level, ctx.M = level, M
+            if Mc is None:
+                _lib.check(L.nlr_mlp_train_forward(plan.handle, _lib.ptr(f), _lib.ptr(e), M, S, _lib.ptr(density), _lib.ptr(rgb), _lib.ptr(sem),
+                                                   _lib.ptr(inten), _lib.ptr(acts), st), "nlr_mlp_train_forward")
+            else:
+                _lib.check(L.nlr_mlp_train_forward_split(plan.handle, _lib.ptr(f), _lib.ptr(e), M, Mc, S, _lib.ptr(density), _lib.ptr(rgb),
+                                                         _lib.ptr(sem), _lib.ptr(inten), _lib.ptr(acts), st), "nlr_mlp_train_forward_split")
+        ctx.level, ctx.M, ctx.Mc = level, M, Mc
         ctx.save_for_backward(f, e, density, rgb, sem if sem is not None else density.new_empty(0),
                               inten if inten is not None else density.new_empty(0), acts)
         outs = [density, rgb]
@@ -335,7 +364,7 @@ class _FusedMLP(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_density, g_rgb, g_sem, g_inten):
-        level, M = ctx.level, ctx.M
+        level, M, Mc = ctx.level, ctx.M, ctx.Mc
         plan, cfg = level._plan, level.cfg
         f, e, density, rgb, sem, inten, acts = ctx.saved_tensors
         dev = f.device
@@ -345,10 +374,12 @@ class _FusedMLP(torch.autograd.Function):
         gacts = torch.empty(M, plan.act_w + 64, device=dev, dtype=torch.bfloat16)
         d_feat = torch.empty_like(f)
         with torch.cuda.device(dev):
-            _lib.check(_lib.lib().nlr_mlp_train_backward(plan.handle, M, level._S, _lib.ptr(density), _lib.ptr(rgb),
-                                                         _lib.ptr(sem) if sem.numel() else None, _lib.ptr(acts), _lib.ptr(gd), _lib.ptr(gr),
-                                                         _lib.ptr(gs), _lib.ptr(gi), _lib.ptr(gacts), _lib.ptr(d_feat), _lib.current_stream()),
-                       "nlr_mlp_train_backward")
+            tail = (_lib.ptr(density), _lib.ptr(rgb), _lib.ptr(sem) if sem.numel() else None, _lib.ptr(acts), _lib.ptr(gd), _lib.ptr(gr),
+                    _lib.ptr(gs), _lib.ptr(gi), _lib.ptr(gacts), _lib.ptr(d_feat), _lib.current_stream())
+            if Mc is None:
+                _lib.check(_lib.lib().nlr_mlp_train_backward(plan.handle, M, level._S, *tail), "nlr_mlp_train_backward")
+            else:
+                _lib.check(_lib.lib().nlr_mlp_train_backward_split(plan.handle, M, Mc, level._S, *tail), "nlr_mlp_train_backward_split")
         if getattr(level, "_keep_debug", False):  # tests look at the kernels' raw results
             level._dbg = {k: v.detach() for k, v in dict(acts=acts, gacts=gacts, d_feat=d_feat, feats=f, enc=e, density=density, rgb=rgb,
                                                         sem=sem, inten=inten).items()}
@@ -357,9 +388,12 @@ class _FusedMLP(torch.autograd.Function):
             d_params = torch.empty(plan.n_params, device=dev, dtype=torch.float32)
             ws = level._wgrad_workspace(dev)
             with torch.cuda.device(dev):
-                _lib.check(_lib.lib().nlr_mlp_train_wgrad(plan.handle, M, level._S, _lib.ptr(f), _lib.ptr(e), _lib.ptr(acts), _lib.ptr(gacts),
-                                                          _lib.ptr(d_params), _lib.ptr(ws), ws.numel(), _lib.current_stream()),
-                           "nlr_mlp_train_wgrad")
+                tail = (_lib.ptr(f), _lib.ptr(e), _lib.ptr(acts), _lib.ptr(gacts), _lib.ptr(d_params), _lib.ptr(ws), ws.numel(),
+                        _lib.current_stream())
+                if Mc is None:
+                    _lib.check(_lib.lib().nlr_mlp_train_wgrad(plan.handle, M, level._S, *tail), "nlr_mlp_train_wgrad")
+                else:
+                    _lib.check(_lib.lib().nlr_mlp_train_wgrad_split(plan.handle, M, Mc, level._S, *tail), "nlr_mlp_train_wgrad_split")
             if getattr(level, "_keep_debug", False):
                 level._dbg["d_params"] = d_params.detach()
             grads, off = [], 0
@@ -367,7 +401,7 @@ class _FusedMLP(torch.autograd.Function):
                 grads.append(d_params[off:off + p.numel()].view(p.shape))
                 off += p.numel()
         else:
-            grads = _wgrad_bmm(level, M, f, e, acts, gacts)
+            grads = _wgrad_bmm(level, M, f, e, acts, gacts, Mc)
         return (d_feat, None, None) + tuple(grads)
 
 
@@ -412,6 +446,7 @@ class TrainableNerfLevel(torch.nn.Module):
         self._wgrad_ws = {}  # device -> workspace of nlr_mlp_train_wgrad, allocated once
         self.fused_encode = bool(fused_mlp)  # cast + encode + re-weight + mean as one operator (encode_features_fused)
         self._plan = None
+        self._color_rays = None  # set by forward(color_rays=..) for _FusedMLP, like _S
         if self.fused_mlp and cfg.use_semantic and cfg.no_sem_layer:
             raise NotImplementedError("fused training MLP: no_sem_layer=True is not wired (use fused_mlp=False)")
         if self.fused_mlp and cfg.skip_layer_dir != 0:
@@ -446,17 +481,23 @@ class TrainableNerfLevel(torch.nn.Module):
         return self
 
     def forward(self, batch: Dict[str, torch.Tensor], tdist: torch.Tensor, sample_n: int = 7, sample_m: int = 3,
-                rand_deg: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+                rand_deg: Optional[torch.Tensor] = None, color_rays: Optional[int] = None) -> Dict[str, torch.Tensor]:
+        """color_rays: None, or the number n of leading rays that carry colour supervision (0 <= n <= N; anything else raises
+        ValueError).  The rays [n, N) - the LiDAR rays the reference appends to every batch, ZI/datasets.py:352-390 - then skip the
+        view MLP (`lin_second_stage_*`, `rgb_layer`) forward and backward and come back with rgb = 0.  THE CALLER PROMISES that the
+        loss ignores their colour: `batch['mask_rgb']` is zero on rays [n, N) (train.py:316-320).  Under that promise every gradient
+        is the one the masked loss gives without `color_rays`; nothing here reads the mask (a step stays free of host reads)."""
         from .objects import _pos_enc
         F = torch.nn.functional
         cfg = self.cfg
+        nc = _check_color_rays(color_rays, tdist.shape[0])
         if self.fused_encode:
             feats = encode_features_fused(self.encoder, batch, tdist, sample_n, sample_m, rand_deg=rand_deg, re_weights=cfg.re_weights)
         else:
             means, stds = cast_contract(batch, tdist, sample_n, sample_m, rand_deg=rand_deg)
             feats = encode_features(self.encoder, means, stds, cfg.re_weights)
         if self.fused_mlp:
-            return self._forward_fused(batch, feats)
+            return self._forward_fused(batch, feats, nc)
         x = self.density_layer(feats)
         out = {"density": F.softplus(x[..., 0] + cfg.density_bias)}
         if cfg.use_semantic:
@@ -464,6 +505,9 @@ class TrainableNerfLevel(torch.nn.Module):
         if cfg.use_intensity:
             out["intensity"] = self.intensity_layer(x)[..., 0]
         enc = _pos_enc(batch["viewdirs"].reshape(x.shape[0], 3).float(), cfg.deg_view)
+        n_all = x.shape[0]
+        if nc is not None:  # the view MLP on the rays with colour supervision only
+            x, enc = x[:nc], enc[:nc]
         h = torch.cat([x, enc[:, None, :].expand(-1, x.shape[1], -1)], dim=-1)
         inputs = h
         for i in range(cfg.net_depth_viewdirs):
@@ -471,7 +515,10 @@ class TrainableNerfLevel(torch.nn.Module):
             if i == cfg.skip_layer_dir:
                 h = torch.cat([h, inputs], dim=-1)
         rgb = torch.sigmoid(cfg.rgb_premultiplier * self.rgb_layer(h) + cfg.rgb_bias)
-        out["rgb"] = rgb * (1 + 2 * cfg.rgb_padding) - cfg.rgb_padding
+        rgb = rgb * (1 + 2 * cfg.rgb_padding) - cfg.rgb_padding
+        if nc is not None:  # rgb = 0 for the rest (a zeros block carries no gradient)
+            rgb = torch.cat([rgb, rgb.new_zeros(n_all - nc, *rgb.shape[1:])], dim=0)
+        out["rgb"] = rgb
         return out
 
     def _mlp_params(self):
@@ -496,10 +543,11 @@ class TrainableNerfLevel(torch.nn.Module):
             ws = self._wgrad_ws[dev] = torch.empty(n, device=dev, dtype=torch.uint8)
         return ws
 
-    def _forward_fused(self, batch, feats):
+    def _forward_fused(self, batch, feats, color_rays=None):
         from .objects import _pos_enc
         cfg = self.cfg
         n, S = feats.shape[0], feats.shape[1]
+        self._color_rays = color_rays
         if self._plan is None:
             with torch.cuda.device(feats.device):  # nlr_train_plan_create allocates on the current device
                 self._plan = _TrainPlan(cfg)
@@ -517,6 +565,7 @@ class TrainableNerfLevel(torch.nn.Module):
         return out
 
     def render(self, batch, tdist, opaque_background: bool = True, bg: float = 1.0, **kw):
+        """forward + compositing; keywords (`color_rays` among them, see `forward`) go to `forward`."""
         o = self.forward(batch, tdist, **kw)
         r = volumetric_render(o["density"], tdist, batch["directions"].reshape(tdist.shape[0], 3), o["rgb"], o.get("semantic"),
                               o.get("intensity"), opaque_background, bg)
@@ -769,11 +818,16 @@ class TrainableModel(torch.nn.Module):
         return density, rgbs, sem, mask
 
     def forward(self, batch: Dict[str, torch.Tensor], train_frac: float = 1.0, rand: Optional[torch.Generator] = None, randomized: bool = False,
-                sample_n: int = 7, sample_m: int = 3, curr_track=None):
+                sample_n: int = 7, sample_m: int = 3, curr_track=None, color_rays: Optional[int] = None):
         """-> (renderings, ray_history), one entry per level, like `Model.forward`.  randomized (or a generator in `rand`): per-ray
         jitter of the sample positions (stepfun.py:216) and per-multisample rotation (render.py:150), as `model(True, ...)` draws
-        them in train.py:272."""
+        them in train.py:272.
+        color_rays: None, or the number n of leading rays with colour supervision; the NerfMLP level skips its view MLP for the
+        rays [n, N) and renders them black (`TrainableNerfLevel.forward`).  The caller promises `batch['mask_rgb']` = 0 on those
+        rays.  With `instance_obj` the object networks still write their own rgb into the samples they own on such rays: harmless,
+        the loss masks those rays."""
         mc = self.mc
+        color_rays = _check_color_rays(color_rays, batch["origins"].shape[0])
         L = _lib.lib()
         n = batch["origins"].shape[0]
         dev = batch["origins"].device
@@ -807,7 +861,7 @@ class TrainableModel(torch.nn.Module):
                                                 _lib.ptr(jit), _lib.ptr(near), _lib.ptr(far), float(mc.power_lambda), n, _lib.ptr(sdist), _lib.ptr(tdist),
                                                 _lib.current_stream()), "nlr_resample_level")
             rd = torch.rand(n, S, sample_n, device=dev, generator=rand) if randomized else None
-            o = level(batch, tdist, sample_n, sample_m, rand_deg=rd)
+            o = level(batch, tdist, sample_n, sample_m, rand_deg=rd, **({"color_rays": color_rays} if last else {}))
             rgbs = o["rgb"] if last else torch.zeros(n, S, 3, device=dev)   # a PropMLP renders black (models.py:1119-1122)
             obj_mask = None
             if box is not None:
@@ -869,15 +923,22 @@ def create_optimizer(model: torch.nn.Module, lr_init: float = 0.01, lr_final: fl
 
 def training_step(model: TrainableModel, optimizer: torch.optim.Optimizer, batch: Dict[str, torch.Tensor], train_frac: float = 1.0,
                   randomized: bool = True, hash_decay_mult: float = 0.1, tv_weight: float = 0.0, grad_max_norm: float = 0.0,
-                  grad_max_val: float = 0.0, latent_reg: float = 0.001, as_tensors: bool = False, **loss_kw):
+                  grad_max_val: float = 0.0, latent_reg: float = 0.001, as_tensors: bool = False, color_rays: Optional[int] = None,
+                  check_color_rays: bool = False, **loss_kw):
     """One optimiser step as train.py:272-459 takes it: forward with random jitter, the loss dictionary (`losses.total_loss` +
     hash decay), backward through the HIP backward kernels, optional total-variation gradient on the tables (grid.py:176-198),
     gradient clipping incl. the unconditional nan_to_num_ (train_utils.clip_gradients), step.  Returns the loss terms as floats, or
     with `as_tensors` as detached device scalars: reading them is the only host synchronisation of a step (without object tracks), so a
-    loop that logs every n-th step keeps the next step's launches ahead of the GPU in between."""
+    loop that logs every n-th step keeps the next step's launches ahead of the GPU in between.
+    color_rays: None, or the number n of leading rays with colour supervision (`TrainableModel.forward`): the caller promises
+    `batch['mask_rgb']` = 0 on the rays [n, N), as train.py:316-320 sets it for the LiDAR rays at the end of a batch
+    (`losses.nusc_masks(lidar_supervision=True)` and `scene.supervise(colourless=..)` build such masks).  check_color_rays (off by default: it reads the mask back, one host
+    synchronisation) verifies the promise and raises ValueError when it is broken."""
     from . import losses as nlosses
+    if check_color_rays and color_rays is not None:
+        nlosses.check_colourless(batch, color_rays)
     optimizer.zero_grad(set_to_none=True)
-    renderings, history = model(batch, train_frac=train_frac, randomized=randomized)
+    renderings, history = model(batch, train_frac=train_frac, randomized=randomized, color_rays=color_rays)
     terms = nlosses.total_loss(renderings, history, batch, **loss_kw)
     if hash_decay_mult > 0:  # (Config.obj_nodecay, nuscenes_single.gin:24: the object grids stay out)
         terms["hash_decay"] = hash_decay_loss([lv.encoder for lv in model.levels()], hash_decay_mult)
