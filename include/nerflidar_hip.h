@@ -382,6 +382,19 @@ int nlr_hash_decay_backward(const float *embeddings, const int32_t *offsets_host
  *     density_layer.2, [sem_layer.0, sem_layer.2], [intensity_layer.0, intensity_layer.2], lin_second_stage_0..D-1, rgb_layer its
  *     weight (row-major [out, in]) then its bias; nlr_train_param_layout returns the offsets (2 per Linear).  nlr_train_pack
  *     re-packs the weight tapes on the device from that buffer (call it after every optimizer step).
+ *     The plan's layer table is the single description of the training MLP: the tapes, the bias block, the weight-gradient jobs and
+ *     the host-side GEMMs are all derived from it.  nlr_train_linear_table returns it, one row of 16 uint32 per Linear in the
+ *     order above (returns the row count; `capacity` in uint32): g_col, o_off, n_out, color, n_blocks, 3 x (src, col, n), w_off,
+ *     b_off.  The Linear's pre-activation gradient is gacts[:, g_col : g_col + n_out]; o_off counts the columns in front of
+ *     g_col that another Linear of the same 32-column unit owns (the intensity row behind the K semantic rows; else 0); its
+ *     input is the concatenation of n_blocks blocks, columns [col, col + n) of src 0 = acts, 1 = features, 2 = enc (unused
+ *     blocks are 0); color = 1 for lin_second_stage_* and rgb_layer, which see rows [0, M_color) only; w_off / b_off as
+ *     nlr_train_param_layout.  E.g. W = 128, D = 2, F = 40, deg_view = 4, no heads (act_w = 576):
+ *       density_layer.0     g_col   0, n_out  64 <- features[0:40]
+ *       density_layer.2     g_col  64, n_out 256 <- acts[0:64]
+ *       lin_second_stage_0  g_col 320, n_out 128 <- acts[64:320] | enc[0:27]                  (color)
+ *       lin_second_stage_1  g_col 448, n_out 128 <- acts[320:448] | acts[64:320] | enc[0:27]  (color)
+ *       rgb_layer           g_col 608, n_out   3 <- acts[448:576]                             (color)
  *     forward: features [M, F] f32 row-major, enc [M / S, 32] (pos_enc of the ray's viewdirs, zero padded); outputs in the
  *       layouts of nlr_mlp_level; acts [M, nlr_train_act_width()] bf16 = [hid 64 | bottleneck | head hidden | x_0 .. x_{D-1}].
  *     backward: upstream gradients in the layouts of the outputs (NULL = zero); gacts [M, act_width + 64] bf16 = the gradient of
@@ -416,6 +429,7 @@ int nlr_train_plan_create(uint32_t F, uint32_t W, uint32_t WB, uint32_t D, uint3
 void nlr_train_plan_destroy(NlrTrainPlan *p);
 uint32_t nlr_train_act_width(const NlrTrainPlan *p);
 int nlr_train_param_layout(const NlrTrainPlan *p, uint32_t *offsets, uint32_t capacity);
+int nlr_train_linear_table(const NlrTrainPlan *p, uint32_t *rows, uint32_t capacity);
 int nlr_train_pack(NlrTrainPlan *p, const float *params_dev, void *stream);
 int nlr_mlp_train_forward(const NlrTrainPlan *p, const float *features, const float *enc, uint32_t M, uint32_t S, float *density,
                           float *rgb, float *semantic, float *intensity, void *acts, void *stream);

@@ -14,8 +14,12 @@
 //            Every layer's pre-activation gradient is stored row-major in `gacts`; the gradient of the features goes out in f32.
 // Weight gradients are GEMMs over the saved tensors (dW_l = gacts_l^T . acts_{l-1}, M-long reductions), as are the bias sums:
 // nlr_mlp_train_wgrad (nlr_mlp_wgrad.hip) computes all of them in one MFMA kernel plus a slab reduce; nerflidar_hip/training.py
-// also keeps the older form, library GEMMs on the host side, as its default.  The tapes are re-packed on the device from the flat
-// parameter buffer before every step (nlr_train_pack: one gather through an index map built once).
+// also keeps the older form, library GEMMs on the host side, as its default.
+// The plan (nlr_train_plan.h) holds ONE table of the Linear layers: flat-parameter offsets, the columns of acts / gacts each reads and
+// writes, which ones see the colour rows only.  plan_build derives from it the index maps of both tapes (with and without the view MLP)
+// and of the bias block, without touching a device; nlr_mlp_wgrad.hip derives its job list from it, the host side its GEMMs
+// (nlr_train_linear_table).  The tapes are re-packed on the device from the flat parameter buffer before every step (nlr_train_pack:
+// one gather through those index maps).
 #include <vector>
 
 #include "nlr_mlp_kernel.h"
@@ -78,6 +82,13 @@ __device__ __forceinline__ void nlr_pack_masked(BT<2> &dst, const Unit<2> &src, 
     dst.n[n][4 * jb + 2 * pr + 1] = o[1];
 }
 
+__device__ __forceinline__ void nlr_zero(Unit<2> &u) {
+#pragma unroll
+    for (int jb = 0; jb < 2; ++jb)
+#pragma unroll
+        for (int n = 0; n < 2; ++n) u.a[jb][n] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+}
+
 // WT = view width / 32, BW = bottleneck / 32, FT = ceil(F / 32), HT = head hidden units of 32 (0, 2, 4)
 // VIEW = false: rows without colour supervision (nlr_mlp_train_*_split): density trunk and heads only, on the tapes
 //   forward D0 D2 [H1 H2], backward H2^T [H1^T | e_0] D2^T D0^T; rgb is written as 0, the view columns of acts / gacts and the
@@ -92,8 +103,9 @@ __global__ void __launch_bounds__(256, 1) nlr_mlp_train_kernel(TrainParams P) {
     constexpr int HTA = HT > 0 ? HT : 1;
     constexpr int OB_D0 = 0, OB_D2 = 64, OB_H1 = OB_D2 + BW * 32, OB_H2 = OB_H1 + HT * 32, OB_V0 = OB_H2 + 32;
     constexpr int OB_V1 = OB_V0 + WT * 32, OB_VL = OB_V1 + WT * 32;
-    // columns of acts / gacts
-    constexpr uint32_t C_HID = 0, C_HBE = 64, C_Q = C_HBE + BW * 32, C_X = C_Q + HT * 32;
+    // columns of acts / gacts (the depth is a run-time value: the two blocks behind the view layers are placed from P.act_w)
+    constexpr TrainCols CC = nlr_train_cols(WT * 32, BW * 32, HT, 0);
+    constexpr uint32_t C_HID = CC.c_hid, C_HBE = CC.c_hbe, C_Q = CC.c_q, C_X = CC.c_x;
     const uint32_t W = WT * 32, ld = P.act_w, gld = P.act_w + 64, C_LO = P.act_w, C_O = P.act_w + 32;
     // forward program (fragments)
     constexpr int FR_D0 = 2 * FT * 2, FR_D2 = BW * 2 * 2, FR_H1 = HT * BW * 2, FR_H2 = HT > 0 ? HT * 2 : 0;
@@ -129,6 +141,18 @@ __global__ void __launch_bounds__(256, 1) nlr_mlp_train_kernel(TrainParams P) {
         out[1] = *reinterpret_cast<const f32x4 *>(b + 16 + 4 * q);
     };
     auto no_bias = [&](auto, f32x4 (&out)[2]) { out[0] = out[1] = zero4; };
+    // ---- the recurring callbacks of nlr_gemm
+    // bias: the rows of output unit O from the block at lds_bias + OB (OB: a constant as ic<>)
+    auto bias_at = [&](auto ob) {
+        return [&](auto o, f32x4(&out)[2]) { bias_rows(lds_bias + decltype(ob)::value + 32 * decltype(o)::value, out); };
+    };
+    // mma: one accumulator chain over the B tiles t[0 .. KG)
+    auto chain = [](const BT<2> *t) {
+        return [t](Unit<2> &u, auto g, auto j, const uint4 &f0, const uint4 &, const f32x4 &bj) {
+            constexpr int G = decltype(g)::value, J = decltype(j)::value;
+            nlr_mma_bf16<G == 0, 0>(u.a[J], bj, f0, t[G]);
+        };
+    };
 
     for (uint32_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const uint32_t s0 = P.row0 + tile * 128 + wave * 32;
@@ -162,11 +186,8 @@ __global__ void __launch_bounds__(256, 1) nlr_mlp_train_kernel(TrainParams P) {
             }
             BT<2> hidb[2];
             nlr_gemm<2, FT, 2, 2, 1, 0, 9>(
-                tp, [&](auto o, f32x4(&b)[2]) { bias_rows(lds_bias + OB_D0 + 32 * decltype(o)::value, b); },
-                [&](Unit<2> &u, auto g, auto j, const uint4 &f0, const uint4 &, const f32x4 &bj) {
-                    constexpr int G = decltype(g)::value, J = decltype(j)::value;
-                    nlr_mma_bf16<G == 0, 0>(u.a[J], bj, f0, fb[G]);
-                },
+                tp, bias_at(ic<OB_D0>{}),
+                chain(fb),
                 [&](auto o, auto p, const Unit<2> &u) {
                     constexpr int O = decltype(o)::value, Pc = decltype(p)::value;
                     if constexpr (Pc < 8) nlr_pack_piece<true, Pc, 0>(hidb[O], u);
@@ -174,11 +195,8 @@ __global__ void __launch_bounds__(256, 1) nlr_mlp_train_kernel(TrainParams P) {
                 });
             float raw[2] = {0.0f, 0.0f};
             nlr_gemm<BW, 2, 2, 2, 1, FR_D0, 9>(
-                tp, [&](auto o, f32x4(&b)[2]) { bias_rows(lds_bias + OB_D2 + 32 * decltype(o)::value, b); },
-                [&](Unit<2> &u, auto g, auto j, const uint4 &f0, const uint4 &, const f32x4 &bj) {
-                    constexpr int G = decltype(g)::value, J = decltype(j)::value;
-                    nlr_mma_bf16<G == 0, 0>(u.a[J], bj, f0, hidb[G]);
-                },
+                tp, bias_at(ic<OB_D2>{}),
+                chain(hidb),
                 [&](auto o, auto p, const Unit<2> &u) {
                     constexpr int O = decltype(o)::value, Pc = decltype(p)::value;
                     if constexpr (O == 0 && Pc == 0) {
@@ -189,29 +207,20 @@ __global__ void __launch_bounds__(256, 1) nlr_mlp_train_kernel(TrainParams P) {
                     else nlr_store_bt(P.acts, ld, s0, P.M, col, q, C_HBE + 32 * O, hbe[O]);
                 });
             Unit<2> lo;
-#pragma unroll
-            for (int jb = 0; jb < 2; ++jb)
-#pragma unroll
-                for (int n = 0; n < 2; ++n) lo.a[jb][n] = zero4;
+            nlr_zero(lo);
             if constexpr (HT > 0) {
                 BT<2> qb[HTA];
                 nlr_gemm<HT, BW, 2, 2, 1, FR_D0 + FR_D2, 9>(
-                    tp, [&](auto o, f32x4(&b)[2]) { bias_rows(lds_bias + OB_H1 + 32 * decltype(o)::value, b); },
-                    [&](Unit<2> &u, auto g, auto j, const uint4 &f0, const uint4 &, const f32x4 &bj) {
-                        constexpr int G = decltype(g)::value, J = decltype(j)::value;
-                        nlr_mma_bf16<G == 0, 0>(u.a[J], bj, f0, hbe[G]);
-                    },
+                    tp, bias_at(ic<OB_H1>{}),
+                    chain(hbe),
                     [&](auto o, auto p, const Unit<2> &u) {
                         constexpr int O = decltype(o)::value, Pc = decltype(p)::value;
                         if constexpr (Pc < 8) nlr_pack_piece<true, Pc, 0>(qb[O], u);
                         else nlr_store_bt(P.acts, ld, s0, P.M, col, q, C_Q + 32 * O, qb[O]);
                     });
                 nlr_gemm<1, HT, 2, 2, 1, FR_D0 + FR_D2 + FR_H1, 1>(
-                    tp, [&](auto, f32x4(&b)[2]) { bias_rows(lds_bias + OB_H2, b); },
-                    [&](Unit<2> &u, auto g, auto j, const uint4 &f0, const uint4 &, const f32x4 &bj) {
-                        constexpr int G = decltype(g)::value, J = decltype(j)::value;
-                        nlr_mma_bf16<G == 0, 0>(u.a[J], bj, f0, qb[G]);
-                    },
+                    tp, bias_at(ic<OB_H2>{}),
+                    chain(qb),
                     [&](auto, auto, const Unit<2> &u) { lo = u; });
             }
             // per-sample heads (layouts of the inference kernel)
@@ -276,18 +285,15 @@ __global__ void __launch_bounds__(256, 1) nlr_mlp_train_kernel(TrainParams P) {
                 // view MLP
                 BT<2> x[WT], y[WT];
                 nlr_gemm<WT, BW + 1, 2, 2, 1, FR_T, 9>(
-                    tp, [&](auto o, f32x4(&b)[2]) { bias_rows(lds_bias + OB_V0 + 32 * decltype(o)::value, b); },
-                    [&](Unit<2> &u, auto g, auto j, const uint4 &f0, const uint4 &, const f32x4 &bj) {
-                        constexpr int G = decltype(g)::value, J = decltype(j)::value;
-                        nlr_mma_bf16<G == 0, 0>(u.a[J], bj, f0, hbe[G]);
-                    },
+                    tp, bias_at(ic<OB_V0>{}),
+                    chain(hbe),
                     [&](auto o, auto p, const Unit<2> &u) {
                         constexpr int O = decltype(o)::value, Pc = decltype(p)::value;
                         if constexpr (Pc < 8) nlr_pack_piece<true, Pc, 0>(x[O], u);
                         else nlr_store_bt(P.acts, ld, s0, P.M, col, q, C_X + 32 * O, x[O]);
                     });
                 nlr_gemm<WT, WT + BW + 1, 2, 2, 1, FR_T + FR_V0, 9>(
-                    tp, [&](auto o, f32x4(&b)[2]) { bias_rows(lds_bias + OB_V1 + 32 * decltype(o)::value, b); },
+                    tp, bias_at(ic<OB_V1>{}),
                     [&](Unit<2> &u, auto g, auto j, const uint4 &f0, const uint4 &, const f32x4 &bj) {
                         constexpr int G = decltype(g)::value, J = decltype(j)::value;
                         if constexpr (G < WT) nlr_mma_bf16<G == 0, 0>(u.a[J], bj, f0, x[G]);
@@ -303,10 +309,7 @@ __global__ void __launch_bounds__(256, 1) nlr_mlp_train_kernel(TrainParams P) {
                     const uint32_t cl = C_X + l * W;
                     nlr_gemm<WT, WT, 2, 2, 1, FF_HID, 9>(
                         tp, [&](auto o, f32x4(&b)[2]) { bias_rows(bl + 32 * decltype(o)::value, b); },
-                        [&](Unit<2> &u, auto g, auto j, const uint4 &f0, const uint4 &, const f32x4 &bj) {
-                            constexpr int G = decltype(g)::value, J = decltype(j)::value;
-                            nlr_mma_bf16<G == 0, 0>(u.a[J], bj, f0, y[G]);
-                        },
+                        chain(y),
                         [&](auto o, auto p, const Unit<2> &u) {
                             constexpr int O = decltype(o)::value, Pc = decltype(p)::value;
                             if constexpr (Pc < 8) nlr_pack_piece<true, Pc, 0>(x[O], u);
@@ -318,10 +321,7 @@ __global__ void __launch_bounds__(256, 1) nlr_mlp_train_kernel(TrainParams P) {
                 Unit<2> out1;
                 nlr_gemm<1, WT, 1, 2, 1, FF_HID, 1>(
                     tp, [&](auto, f32x4(&b)[2]) { bias_rows(lds_bias + OB_VL + (P.depth - 2) * (WT * 32), b); },
-                    [&](Unit<2> &u, auto g, auto j, const uint4 &f0, const uint4 &, const f32x4 &bj) {
-                        constexpr int G = decltype(g)::value, J = decltype(j)::value;
-                        nlr_mma_bf16<G == 0, 0>(u.a[J], bj, f0, y[G]);
-                    },
+                    chain(y),
                     [&](auto, auto, const Unit<2> &u) { out1 = u; });
                 if (q == 0) {
 #pragma unroll
@@ -344,13 +344,20 @@ __global__ void __launch_bounds__(256, 1) nlr_mlp_train_kernel(TrainParams P) {
             // d loss / d (rgb_layer output): rgb = s (1 + 2p) - p, s = sigmoid(premul o + bias)
             BT<2> gin;  // one 32-feature k-block of upstream gradient
             BT<2> g[WT], h[WT], mk;
+            // epi: the gradient of a ReLU layer's pre-activation: unit O masked by the saved activation at columns c0 + 32 O of acts,
+            // packed into dst[O] and stored at the same columns of gacts
+            auto mask_store = [&](BT<2> *dst, uint32_t c0) {
+                return [&, dst, c0](auto o, auto p, const Unit<2> &u) {
+                    constexpr int O = decltype(o)::value, Pc = decltype(p)::value;
+                    if constexpr (Pc == 0) nlr_load_bt(P.acts, ld, s0, P.M, col, q, c0 + 32 * O, mk);
+                    if constexpr (Pc < 8) nlr_pack_masked<Pc>(dst[O], u, mk);
+                    else nlr_store_bt(P.gacts, gld, s0, P.M, col, q, c0 + 32 * O, dst[O]);
+                };
+            };
             if constexpr (VIEW) {
                 {
                     Unit<2> du;
-#pragma unroll
-                    for (int jb = 0; jb < 2; ++jb)
-#pragma unroll
-                        for (int n = 0; n < 2; ++n) du.a[jb][n] = zero4;
+                    nlr_zero(du);
                     if (q == 0 && P.g_rgb) {
 #pragma unroll
                         for (int n = 0; n < 2; ++n) {
@@ -371,46 +378,23 @@ __global__ void __launch_bounds__(256, 1) nlr_mlp_train_kernel(TrainParams P) {
                     const uint32_t cl = C_X + (P.depth - 1) * W;
                     nlr_gemm<WT, 1, 2, 2, 1, 0, 9>(
                         tp, no_bias,
-                        [&](Unit<2> &u, auto, auto j, const uint4 &f0, const uint4 &, const f32x4 &bj) {
-                            nlr_mma_bf16<true, 0>(u.a[decltype(j)::value], bj, f0, gin);
-                        },
-                        [&](auto o, auto p, const Unit<2> &u) {
-                            constexpr int O = decltype(o)::value, Pc = decltype(p)::value;
-                            if constexpr (Pc == 0) nlr_load_bt(P.acts, ld, s0, P.M, col, q, cl + 32 * O, mk);
-                            if constexpr (Pc < 8) nlr_pack_masked<Pc>(g[O], u, mk);
-                            else nlr_store_bt(P.gacts, gld, s0, P.M, col, q, cl + 32 * O, g[O]);
-                        });
+                        chain(&gin),
+                        mask_store(g, cl));
                 }
                 for (uint32_t l = P.depth - 1; l >= 2; --l) {  // hidden layers, transposed: d z_{l-1} = mask(x_{l-1}) W_l^T d z_l
                     const uint32_t cl = C_X + (l - 1) * W;
                     nlr_gemm<WT, WT, 2, 2, 1, BR_RGB, 9>(
                         tp, no_bias,
-                        [&](Unit<2> &u, auto gg, auto j, const uint4 &f0, const uint4 &, const f32x4 &bj) {
-                            constexpr int G = decltype(gg)::value, J = decltype(j)::value;
-                            nlr_mma_bf16<G == 0, 0>(u.a[J], bj, f0, g[G]);
-                        },
-                        [&](auto o, auto p, const Unit<2> &u) {
-                            constexpr int O = decltype(o)::value, Pc = decltype(p)::value;
-                            if constexpr (Pc == 0) nlr_load_bt(P.acts, ld, s0, P.M, col, q, cl + 32 * O, mk);
-                            if constexpr (Pc < 8) nlr_pack_masked<Pc>(h[O], u, mk);
-                            else nlr_store_bt(P.gacts, gld, s0, P.M, col, q, cl + 32 * O, h[O]);
-                        });
+                        chain(g),
+                        mask_store(h, cl));
 #pragma unroll
                     for (int t = 0; t < WT; ++t) g[t] = h[t];
                 }
                 // g = d z_1.  V1a^T: d z_0 = mask(x_0) W1[:, :W]^T d z_1
                 nlr_gemm<WT, WT, 2, 2, 1, BF_V1A, 9>(
                     tp, no_bias,
-                    [&](Unit<2> &u, auto gg, auto j, const uint4 &f0, const uint4 &, const f32x4 &bj) {
-                        constexpr int G = decltype(gg)::value, J = decltype(j)::value;
-                        nlr_mma_bf16<G == 0, 0>(u.a[J], bj, f0, g[G]);
-                    },
-                    [&](auto o, auto p, const Unit<2> &u) {
-                        constexpr int O = decltype(o)::value, Pc = decltype(p)::value;
-                        if constexpr (Pc == 0) nlr_load_bt(P.acts, ld, s0, P.M, col, q, C_X + 32 * O, mk);
-                        if constexpr (Pc < 8) nlr_pack_masked<Pc>(h[O], u, mk);
-                        else nlr_store_bt(P.gacts, gld, s0, P.M, col, q, C_X + 32 * O, h[O]);
-                    });
+                    chain(g),
+                    mask_store(h, C_X));
             }
             // heads: softmax backward d l_c = p_c (g_c - sum_k g_k p_k), intensity row: its upstream gradient
             BT<2> gq[HTA], aux;
@@ -467,15 +451,8 @@ __global__ void __launch_bounds__(256, 1) nlr_mlp_train_kernel(TrainParams P) {
             if constexpr (HT > 0) {  // H2^T: d (head hidden pre-activation)
                 nlr_gemm<HT, 1, 2, 2, 1, BF_H2, 9>(
                     tp, no_bias,
-                    [&](Unit<2> &u, auto, auto j, const uint4 &f0, const uint4 &, const f32x4 &bj) {
-                        nlr_mma_bf16<true, 0>(u.a[decltype(j)::value], bj, f0, gin);
-                    },
-                    [&](auto o, auto p, const Unit<2> &u) {
-                        constexpr int O = decltype(o)::value, Pc = decltype(p)::value;
-                        if constexpr (Pc == 0) nlr_load_bt(P.acts, ld, s0, P.M, col, q, C_Q + 32 * O, mk);
-                        if constexpr (Pc < 8) nlr_pack_masked<Pc>(gq[O], u, mk);
-                        else nlr_store_bt(P.gacts, gld, s0, P.M, col, q, C_Q + 32 * O, gq[O]);
-                    });
+                    chain(&gin),
+                    mask_store(gq, C_Q));
             }
             // BIG: d bottleneck = W1[:, W:W+WB]^T d z_1 + W0[:, :WB]^T d z_0 + H1^T d q + e_0 d raw (without the view MLP: the last two)
             BT<2> gb[BW];
@@ -497,23 +474,12 @@ __global__ void __launch_bounds__(256, 1) nlr_mlp_train_kernel(TrainParams P) {
             BT<2> gh[2];
             nlr_gemm<2, BW, 2, 2, 1, BF_D2, 9>(
                 tp, no_bias,
-                [&](Unit<2> &u, auto gg, auto j, const uint4 &f0, const uint4 &, const f32x4 &bj) {
-                    constexpr int G = decltype(gg)::value, J = decltype(j)::value;
-                    nlr_mma_bf16<G == 0, 0>(u.a[J], bj, f0, gb[G]);
-                },
-                [&](auto o, auto p, const Unit<2> &u) {
-                    constexpr int O = decltype(o)::value, Pc = decltype(p)::value;
-                    if constexpr (Pc == 0) nlr_load_bt(P.acts, ld, s0, P.M, col, q, C_HID + 32 * O, mk);
-                    if constexpr (Pc < 8) nlr_pack_masked<Pc>(gh[O], u, mk);
-                    else nlr_store_bt(P.gacts, gld, s0, P.M, col, q, C_HID + 32 * O, gh[O]);
-                });
+                chain(gb),
+                mask_store(gh, C_HID));
             // D0^T: gradient of the grid features, f32 out
             nlr_gemm<FT, 2, 2, 2, 1, BF_D0, 1>(
                 tp, no_bias,
-                [&](Unit<2> &u, auto gg, auto j, const uint4 &f0, const uint4 &, const f32x4 &bj) {
-                    constexpr int G = decltype(gg)::value, J = decltype(j)::value;
-                    nlr_mma_bf16<G == 0, 0>(u.a[J], bj, f0, gh[G]);
-                },
+                chain(gh),
                 [&](auto o, auto, const Unit<2> &u) {
                     constexpr int O = decltype(o)::value;
 #pragma unroll
@@ -581,80 +547,74 @@ static IMat transpose(const IMat &w) {
     return t;
 }
 
-// Flat parameter order (weights row-major [out, in], then bias), `n_entries` pairs:
+// Everything of a plan that needs no device: the scalars, the layer table and the index maps of the two tapes and of the bias block.
+// Flat parameter order (weights row-major [out, in], then bias), one TrainLinear each:
 //   density_layer.0, density_layer.2, [sem_layer.0, sem_layer.2], [intensity_layer.0, intensity_layer.2], lin_second_stage_0..D-1, rgb_layer
-extern "C" int nlr_train_plan_create(uint32_t F, uint32_t W, uint32_t WB, uint32_t D, uint32_t deg_view, uint32_t class_num, int use_semantic,
-                                     int use_intensity, float density_bias, float rgb_premultiplier, float rgb_bias, float rgb_padding,
-                                     NlrTrainPlan **out, uint32_t *n_params) {
-    NLR_CHECK_ARG(out && n_params, "train_plan_create: NULL argument");
+static void plan_build(NlrTrainPlan *p, uint32_t F, uint32_t W, uint32_t WB, uint32_t D, uint32_t deg_view, uint32_t class_num,
+                       int use_semantic, int use_intensity, std::vector<int32_t> &ft, std::vector<int32_t> &bt, std::vector<int32_t> &bb) {
     const uint32_t E = 3 + 6 * deg_view;
-    NLR_CHECK_ARG(WB == 256 && (W == 128 || W == 256) && F % 4 == 0 && F > 32 && F <= 64 && D >= 2 && D <= 10 && E <= 32 && class_num <= 31,
-                  "train_plan_create: unsupported NerfMLP shape (bottleneck 256, view width 128/256, 33..64 grid features, depth 2..10)");
-    NlrTrainPlan *p = new NlrTrainPlan();
     p->F = F, p->W = W, p->WB = WB, p->D = D, p->E = E, p->sem = use_semantic != 0, p->inten = use_intensity != 0;
-    p->K = p->sem ? class_num : 0;
-    p->int_row = p->inten ? p->K : 0xffffffffu;
+    const uint32_t K = p->K = p->sem ? class_num : 0;
+    p->int_row = p->inten ? K : 0xffffffffu;
     p->HT = (p->sem ? 2 : 0) + (p->inten ? 2 : 0);
-    p->density_bias = density_bias, p->rgb_premul = rgb_premultiplier, p->rgb_bias = rgb_bias, p->rgb_padding = rgb_padding;
-    p->act_w = 64 + WB + p->HT * 32 + D * W;
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) {
-        delete p;
-        NLR_FAIL(NLR_ERR_HIP, "train_plan_create: cannot query the current device");
-    }
-    p->cus = (uint32_t)cus;
+    const TrainCols c = nlr_train_cols(W, WB, p->HT, D);
+    p->act_w = c.c_lo;
+    // ---- the layer table; each entry takes its weight and bias from the flat buffer
     uint32_t off = 0;
-    auto take = [&](uint32_t rows, uint32_t cols, IMat &w, uint32_t &b) {
-        w = lin(off, rows, cols);
-        off += rows * cols;
-        b = off;
-        off += rows;
-        p->offs.push_back(b - rows * cols);
-        p->offs.push_back(b);
+    auto add = [&](uint32_t g_col, uint32_t o_off, uint32_t n_out, uint32_t color, std::initializer_list<TrainBlock> in, uint32_t &b) {
+        TrainLinear l = {};
+        l.g_col = g_col, l.o_off = o_off, l.n_out = n_out, l.color = color;
+        uint32_t cols = 0;
+        for (const TrainBlock &k : in) l.in[l.n_in++] = k, cols += k.n;
+        l.w_off = off, l.b_off = b = off + n_out * cols;
+        off = l.b_off + n_out;
+        p->linears.push_back(l);
+        return lin(l.w_off, n_out, cols);
     };
-    IMat d0, d2, s0, s2, i0, i2, rgbw;
+    const TrainBlock hbe = {NLR_TRAIN_SRC_ACTS, c.c_hbe, WB}, encb = {NLR_TRAIN_SRC_ENC, 0, E};
+    auto acts = [](uint32_t col, uint32_t n) { return TrainBlock{NLR_TRAIN_SRC_ACTS, col, n}; };
+    IMat s0, s2, i0, i2;
     std::vector<IMat> v(D);
     uint32_t bd0, bd2, bs0 = 0, bs2 = 0, bi0 = 0, bi2 = 0, brgb;
     std::vector<uint32_t> bv(D);
-    take(64, F, d0, bd0);
-    take(WB, 64, d2, bd2);
+    const IMat d0 = add(c.c_hid, 0, 64, 0, {{NLR_TRAIN_SRC_FEATURES, 0, F}}, bd0);
+    const IMat d2 = add(c.c_hbe, 0, WB, 0, {acts(c.c_hid, 64)}, bd2);
+    uint32_t r0 = 0;  // head hidden units: [sem 64][intensity 64]
     if (p->sem) {
-        take(64, WB, s0, bs0);
-        take(class_num, 64, s2, bs2);
+        s0 = add(c.c_q, 0, 64, 0, {hbe}, bs0);
+        s2 = add(c.c_lo, 0, K, 0, {acts(c.c_q, 64)}, bs2);
+        r0 = 64;
     }
     if (p->inten) {
-        take(64, WB, i0, bi0);
-        take(1, 64, i2, bi2);
+        i0 = add(c.c_q + r0, 0, 64, 0, {hbe}, bi0);
+        i2 = add(c.c_lo + K, K, 1, 0, {acts(c.c_q + r0, 64)}, bi2);
     }
-    const uint32_t in0 = WB + E, in1 = W + in0;
-    for (uint32_t l = 0; l < D; ++l) take(W, l == 0 ? in0 : (l == 1 ? in1 : W), v[l], bv[l]);
-    take(3, W, rgbw, brgb);
+    v[0] = add(c.c_x, 0, W, 1, {hbe, encb}, bv[0]);
+    v[1] = add(c.c_x + W, 0, W, 1, {acts(c.c_x, W), hbe, encb}, bv[1]);  // the skip concatenation
+    for (uint32_t l = 2; l < D; ++l) v[l] = add(c.c_x + l * W, 0, W, 1, {acts(c.c_x + (l - 1) * W, W)}, bv[l]);
+    const IMat rgbw = add(c.c_o, 0, 3, 1, {acts(c.c_x + (D - 1) * W, W)}, brgb);
     p->n_params = off;
     // heads as two stacked GEMMs (as the inference path): h1 = [sem0 ; int0], h2 block-diagonal into one 32-row unit
     const uint32_t HH = p->HT * 32;
     IMat h1(HH ? HH : 1, WB), h2(32, HH ? HH : 1);
     std::vector<int32_t> b1(HH, -1), b2(32, -1);
-    {
-        uint32_t r0 = 0;
-        if (p->sem) {
-            for (uint32_t r = 0; r < 64; ++r) {
-                for (uint32_t c = 0; c < WB; ++c) h1.at(r0 + r, c) = s0.a[(size_t)r * WB + c];
-                b1[r0 + r] = (int32_t)(bs0 + r);
-            }
-            for (uint32_t r = 0; r < class_num; ++r) {
-                for (uint32_t c = 0; c < 64; ++c) h2.at(r, r0 + c) = s2.a[(size_t)r * 64 + c];
-                b2[r] = (int32_t)(bs2 + r);
-            }
-            r0 += 64;
+    if (p->sem) {
+        for (uint32_t r = 0; r < 64; ++r) {
+            for (uint32_t c = 0; c < WB; ++c) h1.at(r, c) = s0.a[(size_t)r * WB + c];
+            b1[r] = (int32_t)(bs0 + r);
         }
-        if (p->inten) {
-            for (uint32_t r = 0; r < 64; ++r) {
-                for (uint32_t c = 0; c < WB; ++c) h1.at(r0 + r, c) = i0.a[(size_t)r * WB + c];
-                b1[r0 + r] = (int32_t)(bi0 + r);
-            }
-            for (uint32_t c = 0; c < 64; ++c) h2.at(p->int_row, r0 + c) = i2.a[c];
-            b2[p->int_row] = (int32_t)bi2;
+        for (uint32_t r = 0; r < K; ++r) {
+            for (uint32_t c = 0; c < 64; ++c) h2.at(r, c) = s2.a[(size_t)r * 64 + c];
+            b2[r] = (int32_t)(bs2 + r);
         }
+    }
+    if (p->inten) {
+        for (uint32_t r = 0; r < 64; ++r) {
+            for (uint32_t c = 0; c < WB; ++c) h1.at(r0 + r, c) = i0.a[(size_t)r * WB + c];
+            b1[r0 + r] = (int32_t)(bi0 + r);
+        }
+        for (uint32_t c = 0; c < 64; ++c) h2.at(p->int_row, r0 + c) = i2.a[c];
+        b2[p->int_row] = (int32_t)bi2;
     }
     // view layers with the direction-encoding columns padded to one 32-feature k-block
     auto pad_enc = [&](const IMat &w, uint32_t lead) {  // [.., lead + E] -> [.., lead + 32]
@@ -664,86 +624,73 @@ extern "C" int nlr_train_plan_create(uint32_t F, uint32_t W, uint32_t WB, uint32
         return m;
     };
     const IMat v0p = pad_enc(v[0], WB), v1p = pad_enc(v[1], W + WB);
-    // ---- forward tape + bias block
-    std::vector<int32_t> ft, bt, bb;
-    tape_add(ft, d0, 64, 64);
-    tape_add(ft, d2, WB, 64);
-    if (HH) {
-        tape_add(ft, h1, HH, WB);
-        tape_add(ft, h2, 32, HH);
-    }
-    tape_add(ft, v0p, W, WB + 32);
-    tape_add(ft, v1p, W, W + WB + 32);
-    for (uint32_t l = 2; l < D; ++l) tape_add(ft, v[l], W, W);
-    tape_add(ft, rgbw, 16, W, 1);
-    tape_pad(ft);
+    IMat d0t(64, 64);
+    for (uint32_t r = 0; r < F; ++r)
+        for (uint32_t c = 0; c < 64; ++c) d0t.at(r, c) = d0.a[(size_t)c * F + r];
+    // ---- the tapes: forward D0 D2 [H1 H2] (V0 V1 L2.. RGB), backward (RGB^T L^T.. V1a^T) H2^T BIG D2^T D0^T; the parts in brackets
+    //      with the view MLP only
+    auto build_tapes = [&](bool view) {
+        tape_add(ft, d0, 64, 64);
+        tape_add(ft, d2, WB, 64);
+        if (HH) {
+            tape_add(ft, h1, HH, WB);
+            tape_add(ft, h2, 32, HH);
+        }
+        if (view) {
+            tape_add(ft, v0p, W, WB + 32);
+            tape_add(ft, v1p, W, W + WB + 32);
+            for (uint32_t l = 2; l < D; ++l) tape_add(ft, v[l], W, W);
+            tape_add(ft, rgbw, 16, W, 1);
+        }
+        tape_pad(ft);
+        const uint32_t VW = view ? W : 0;
+        if (view) {
+            tape_add(bt, transpose(rgbw), W, 32);  // rows = view features, k = the 3 (of 32) rgb rows
+            for (uint32_t l = D - 1; l >= 2; --l) tape_add(bt, transpose(v[l]), W, W);
+            IMat v1a(W, W);  // d z_0 <- d z_1 through W1[:, :W]
+            for (uint32_t r = 0; r < W; ++r)
+                for (uint32_t c = 0; c < W; ++c) v1a.at(r, c) = v1p.a[(size_t)c * v1p.cols + r];
+            tape_add(bt, v1a, W, W);
+        }
+        if (HH) tape_add(bt, transpose(h2), HH, 32);
+        IMat big(WB, 2 * VW + HH + 32);
+        for (uint32_t r = 0; r < WB; ++r) {
+            for (uint32_t c = 0; c < VW; ++c) big.at(r, c) = v1p.a[(size_t)c * v1p.cols + W + r];   // skip concat of layer 1
+            for (uint32_t c = 0; c < VW; ++c) big.at(r, VW + c) = v0p.a[(size_t)c * v0p.cols + r];  // layer 0
+            for (uint32_t c = 0; c < HH; ++c) big.at(r, 2 * VW + c) = h1.a[(size_t)c * WB + r];     // heads
+        }
+        big.at(0, 2 * VW + HH + 0) = -2;  // unit weights: raw-density gradient (hi, lo) onto bottleneck row 0
+        big.at(0, 2 * VW + HH + 1) = -2;
+        tape_add(bt, big, WB, 2 * VW + HH + 32);
+        tape_add(bt, transpose(d2), 64, WB);
+        tape_add(bt, d0t, 64, 64);
+        tape_pad(bt);
+    };
+    build_tapes(true);
+    // the tapes of rows without colour supervision (nlr_mlp_train_*_split) behind the full ones, so that one gather packs both
+    p->f0n = p->f1 = (uint32_t)ft.size(), p->b0n = p->b1 = (uint32_t)bt.size();
+    build_tapes(false);
+    p->fn = (uint32_t)ft.size(), p->bn = (uint32_t)bt.size();
+    p->f1n = p->fn - p->f1, p->b1n = p->bn - p->b1;
+    // ---- bias block of the forward kernel
     auto pushb = [&](uint32_t b, uint32_t n, uint32_t pad) {
         for (uint32_t i = 0; i < pad; ++i) bb.push_back(i < n ? (int32_t)(b + i) : -1);
     };
     pushb(bd0, 64, 64);
     pushb(bd2, WB, WB);
-    for (uint32_t i = 0; i < HH; ++i) bb.push_back(b1[i]);
-    for (uint32_t i = 0; i < 32; ++i) bb.push_back(HH ? b2[i] : -1);
+    bb.insert(bb.end(), b1.begin(), b1.end());
+    bb.insert(bb.end(), b2.begin(), b2.end());
     for (uint32_t l = 0; l < D; ++l) pushb(bv[l], W, W);
     pushb(brgb, 3, 32);
-    // ---- backward tape
-    tape_add(bt, transpose(rgbw), W, 32);  // rows = view features, k = the 3 (of 32) rgb rows
-    for (uint32_t l = D - 1; l >= 2; --l) tape_add(bt, transpose(v[l]), W, W);
-    {
-        IMat v1a(W, W);  // d z_0 <- d z_1 through W1[:, :W]
-        for (uint32_t r = 0; r < W; ++r)
-            for (uint32_t c = 0; c < W; ++c) v1a.at(r, c) = v1p.a[(size_t)c * v1p.cols + r];
-        tape_add(bt, v1a, W, W);
-    }
-    if (HH) tape_add(bt, transpose(h2), HH, 32);
-    {
-        IMat big(WB, 2 * W + HH + 32);
-        for (uint32_t r = 0; r < WB; ++r) {
-            for (uint32_t c = 0; c < W; ++c) big.at(r, c) = v1p.a[(size_t)c * v1p.cols + W + r];       // skip concat of layer 1
-            for (uint32_t c = 0; c < W; ++c) big.at(r, W + c) = v0p.a[(size_t)c * v0p.cols + r];       // layer 0
-            for (uint32_t c = 0; c < HH; ++c) big.at(r, 2 * W + c) = h1.a[(size_t)c * WB + r];         // heads
-        }
-        big.at(0, 2 * W + HH + 0) = -2;  // unit weights: raw-density gradient (hi, lo) onto bottleneck row 0
-        big.at(0, 2 * W + HH + 1) = -2;
-        tape_add(bt, big, WB, 2 * W + HH + 32);
-    }
-    tape_add(bt, transpose(d2), 64, WB);
-    {
-        IMat d0t(64, 64);
-        for (uint32_t r = 0; r < F; ++r)
-            for (uint32_t c = 0; c < 64; ++c) d0t.at(r, c) = d0.a[(size_t)c * F + r];
-        tape_add(bt, d0t, 64, 64);
-    }
-    tape_pad(bt);
-    // ---- the tapes of rows without colour supervision (nlr_mlp_train_*_split), behind the full ones so that one gather packs both:
-    //      forward D0 D2 [H1 H2], backward H2^T [H1^T | e_0] D2^T D0^T
-    p->f0n = (uint32_t)ft.size(), p->b0n = (uint32_t)bt.size();
-    tape_add(ft, d0, 64, 64);
-    tape_add(ft, d2, WB, 64);
-    if (HH) {
-        tape_add(ft, h1, HH, WB);
-        tape_add(ft, h2, 32, HH);
-    }
-    tape_pad(ft);
-    if (HH) tape_add(bt, transpose(h2), HH, 32);
-    {
-        IMat big(WB, HH + 32);
-        for (uint32_t r = 0; r < WB; ++r)
-            for (uint32_t c = 0; c < HH; ++c) big.at(r, c) = h1.a[(size_t)c * WB + r];
-        big.at(0, HH + 0) = -2;
-        big.at(0, HH + 1) = -2;
-        tape_add(bt, big, WB, HH + 32);
-    }
-    tape_add(bt, transpose(d2), 64, WB);
-    {
-        IMat d0t(64, 64);
-        for (uint32_t r = 0; r < F; ++r)
-            for (uint32_t c = 0; c < 64; ++c) d0t.at(r, c) = d0.a[(size_t)c * F + r];
-        tape_add(bt, d0t, 64, 64);
-    }
-    tape_pad(bt);
-    p->f1 = p->f0n, p->f1n = (uint32_t)ft.size() - p->f0n, p->b1 = p->b0n, p->b1n = (uint32_t)bt.size() - p->b0n;
-    p->fn = (uint32_t)ft.size(), p->bn = (uint32_t)bt.size(), p->biasn = (uint32_t)bb.size();
+    p->biasn = (uint32_t)bb.size();
+}
+
+// the device side of a plan; on failure the caller destroys the plan with what it owns by then
+static int plan_upload(NlrTrainPlan *p, const std::vector<int32_t> &ft, const std::vector<int32_t> &bt, const std::vector<int32_t> &bb) {
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
+        NLR_FAIL(NLR_ERR_HIP, "train_plan_create: cannot query the current device");
+    p->cus = (uint32_t)cus;
     NLR_CHECK_ARG(p->biasn <= NLR_BIAS_MAX && p->biasn % 4 == 0, "train_plan_create: bias block of %u floats does not fit", p->biasn);
     auto up = [&](const std::vector<int32_t> &h, int32_t **d) -> int {
         NLR_HIP(hipMalloc((void **)d, h.size() * 4));
@@ -758,8 +705,6 @@ extern "C" int nlr_train_plan_create(uint32_t F, uint32_t W, uint32_t WB, uint32
     NLR_HIP(hipMemset(p->ftape, 0, (ft.size() + slack) * 2));
     NLR_HIP(hipMemset(p->btape, 0, (bt.size() + slack) * 2));
     NLR_HIP(hipMalloc((void **)&p->bias, bb.size() * 4));
-    *out = p;
-    *n_params = p->n_params;
     return NLR_OK;
 }
 
@@ -769,13 +714,46 @@ extern "C" void nlr_train_plan_destroy(NlrTrainPlan *p) {
     delete p;
 }
 
+extern "C" int nlr_train_plan_create(uint32_t F, uint32_t W, uint32_t WB, uint32_t D, uint32_t deg_view, uint32_t class_num, int use_semantic,
+                                     int use_intensity, float density_bias, float rgb_premultiplier, float rgb_bias, float rgb_padding,
+                                     NlrTrainPlan **out, uint32_t *n_params) {
+    NLR_CHECK_ARG(out && n_params, "train_plan_create: NULL argument");
+    NLR_CHECK_ARG(WB == 256 && (W == 128 || W == 256) && F % 4 == 0 && F > 32 && F <= 64 && D >= 2 && D <= 10 && 3 + 6 * deg_view <= 32 &&
+                      class_num <= 31,
+                  "train_plan_create: unsupported NerfMLP shape (bottleneck 256, view width 128/256, 33..64 grid features, depth 2..10)");
+    NlrTrainPlan *p = new NlrTrainPlan();
+    p->density_bias = density_bias, p->rgb_premul = rgb_premultiplier, p->rgb_bias = rgb_bias, p->rgb_padding = rgb_padding;
+    std::vector<int32_t> ft, bt, bb;
+    plan_build(p, F, W, WB, D, deg_view, class_num, use_semantic, use_intensity, ft, bt, bb);
+    if (const int rc = plan_upload(p, ft, bt, bb)) {
+        nlr_train_plan_destroy(p);
+        return rc;
+    }
+    *out = p;
+    *n_params = p->n_params;
+    return NLR_OK;
+}
+
 extern "C" uint32_t nlr_train_act_width(const NlrTrainPlan *p) { return p ? p->act_w : 0; }
 
 // offsets (in floats) of every (weight, bias) pair inside the flat parameter buffer, in the order documented above
 extern "C" int nlr_train_param_layout(const NlrTrainPlan *p, uint32_t *offsets, uint32_t capacity) {
-    NLR_CHECK_ARG(p && offsets && capacity >= p->offs.size(), "train_param_layout: buffer too small (%zu entries)", p ? p->offs.size() : 0);
-    for (size_t i = 0; i < p->offs.size(); ++i) offsets[i] = p->offs[i];
-    return (int)p->offs.size();
+    NLR_CHECK_ARG(p && offsets && capacity >= 2 * p->linears.size(), "train_param_layout: buffer too small (%zu entries)",
+                  p ? 2 * p->linears.size() : 0);
+    for (size_t i = 0; i < p->linears.size(); ++i) offsets[2 * i] = p->linears[i].w_off, offsets[2 * i + 1] = p->linears[i].b_off;
+    return (int)(2 * p->linears.size());
+}
+
+// the layer table, NLR_TRAIN_TABLE_ROW uint32 per Linear (header section 6b); returns the number of rows
+extern "C" int nlr_train_linear_table(const NlrTrainPlan *p, uint32_t *rows, uint32_t capacity) {
+    NLR_CHECK_ARG(p && rows && capacity >= NLR_TRAIN_TABLE_ROW * p->linears.size(), "train_linear_table: buffer too small (%zu entries)",
+                  p ? NLR_TRAIN_TABLE_ROW * p->linears.size() : 0);
+    for (const TrainLinear &l : p->linears) {
+        *rows++ = l.g_col, *rows++ = l.o_off, *rows++ = l.n_out, *rows++ = l.color, *rows++ = l.n_in;
+        for (const TrainBlock &k : l.in) *rows++ = k.src, *rows++ = k.col, *rows++ = k.n;
+        *rows++ = l.w_off, *rows++ = l.b_off;
+    }
+    return (int)p->linears.size();
 }
 
 extern "C" int nlr_train_pack(NlrTrainPlan *p, const float *params_dev, void *stream) {
@@ -789,34 +767,20 @@ extern "C" int nlr_train_pack(NlrTrainPlan *p, const float *params_dev, void *st
     return NLR_OK;
 }
 
-template <bool BWD>
+// VIEW = false: the trunk-and-heads instances, one per head count whatever the view width
+template <bool BWD, bool VIEW>
 static int launch_train(const NlrTrainPlan *p, TrainParams &P, hipStream_t st) {
     const uint32_t ntiles = (P.M - P.row0 + 127) / 128;
     dim3 grid(ntiles < p->cus ? ntiles : p->cus);
 #define NLR_TR(wt, ht)                                                                                              \
-    if (p->W == wt * 32 && p->HT == ht) {                                                                           \
-        hipLaunchKernelGGL((nlr_mlp_train_kernel<wt, 8, 2, ht, BWD>), grid, dim3(256), 0, st, P);                    \
-        NLR_LAUNCH_CHECK("nlr_mlp_train_kernel");                                                                    \
+    if ((!VIEW || p->W == wt * 32) && p->HT == ht) {                                                                \
+        hipLaunchKernelGGL((nlr_mlp_train_kernel<VIEW ? wt : 4, 8, 2, ht, BWD, VIEW>), grid, dim3(256), 0, st, P);   \
+        NLR_LAUNCH_CHECK(VIEW ? "nlr_mlp_train_kernel" : "nlr_mlp_train_kernel (trunk and heads)");                  \
         return NLR_OK;                                                                                              \
     }
     NLR_TR(8, 4) NLR_TR(8, 2) NLR_TR(8, 0) NLR_TR(4, 4) NLR_TR(4, 2) NLR_TR(4, 0)
 #undef NLR_TR
     NLR_FAIL(NLR_ERR_UNSUPPORTED, "mlp_train: no kernel instance for view width %u with %u head units", p->W, p->HT);
-}
-// the trunk-and-heads instances (VIEW = false): one per head count, whatever the view width
-template <bool BWD>
-static int launch_train_trunk(const NlrTrainPlan *p, TrainParams &P, hipStream_t st) {
-    const uint32_t ntiles = (P.M - P.row0 + 127) / 128;
-    dim3 grid(ntiles < p->cus ? ntiles : p->cus);
-#define NLR_TR(ht)                                                                                                  \
-    if (p->HT == ht) {                                                                                              \
-        hipLaunchKernelGGL((nlr_mlp_train_kernel<4, 8, 2, ht, BWD, false>), grid, dim3(256), 0, st, P);              \
-        NLR_LAUNCH_CHECK("nlr_mlp_train_kernel (trunk and heads)");                                                  \
-        return NLR_OK;                                                                                              \
-    }
-    NLR_TR(4) NLR_TR(2) NLR_TR(0)
-#undef NLR_TR
-    NLR_FAIL(NLR_ERR_UNSUPPORTED, "mlp_train: no trunk-and-heads kernel instance for %u head units", p->HT);
 }
 
 static void fill_common(const NlrTrainPlan *p, TrainParams &P, uint32_t M, uint32_t S) {
@@ -831,14 +795,31 @@ static void note_route(bool bwd, uint32_t M, uint32_t M_color) {
     (void)nlr_debug_set(NLR_DBG_TRAIN_TRUNK_ROW0, (int)M_color);
     (void)nlr_debug_set(NLR_DBG_TRAIN_TRUNK_ROWS, (int)(M - M_color));
 }
+// Rows [0, M_color) through the full instance, rows [M_color, M) through the trunk-and-heads instance: two launches on one stream.
+template <bool BWD>
+static int launch_rows(const NlrTrainPlan *p, TrainParams &P, uint32_t M, uint32_t M_color, hipStream_t st) {
+    const __bf16 *tape = BWD ? p->btape : p->ftape;
+    const uint32_t n0 = BWD ? p->b0n : p->f0n, t1 = BWD ? p->b1 : p->f1, n1 = BWD ? p->b1n : p->f1n;
+    note_route(BWD, M, M_color);
+    if (M_color > 0) {
+        P.row0 = 0, P.M = M_color;
+        P.tape = (const uint4 *)tape, P.tape_chunks = n0 / 16384;
+        if (const int rc = launch_train<BWD, true>(p, P, st)) return rc;
+    }
+    if (M_color < M) {
+        P.row0 = M_color, P.M = M;
+        P.tape = (const uint4 *)(tape + t1), P.tape_chunks = n1 / 16384;
+        if (const int rc = launch_train<BWD, false>(p, P, st)) return rc;
+    }
+    return NLR_OK;
+}
 #define NLR_CHECK_SPLIT(what)                                                                                                             \
     NLR_CHECK_ARG(M > 0, what ": M is 0");                                                                                                \
     NLR_CHECK_ARG(S > 0 && M % S == 0, what ": M = %u is not a multiple of S = %u (M %% S != 0)", M, S);                                  \
     NLR_CHECK_ARG(M_color <= M, what ": M_color = %u exceeds M = %u (M_color > M)", M_color, M);                                          \
     NLR_CHECK_ARG(M_color % S == 0, what ": M_color = %u is not a multiple of S = %u (M_color %% S != 0)", M_color, S)
 
-// features [M, F] f32 row-major, enc [M / S, 32]; outputs as nlr_mlp_level; acts [M, act_w] bf16.
-// Rows [0, M_color) through the full instance, rows [M_color, M) through the trunk-and-heads instance: two launches on one stream.
+// features [M, F] f32 row-major, enc [M / S, 32]; outputs as nlr_mlp_level; acts [M, act_w] bf16
 static int train_forward(const NlrTrainPlan *p, const float *features, const float *enc, uint32_t M, uint32_t M_color, uint32_t S,
                          float *density, float *rgb, float *semantic, float *intensity, void *acts, void *stream) {
     TrainParams P;
@@ -847,18 +828,7 @@ static int train_forward(const NlrTrainPlan *p, const float *features, const flo
     P.bias_all = p->bias, P.bias_count = p->biasn;
     P.density = density, P.rgb = rgb, P.sem = semantic, P.inten = p->inten ? intensity : nullptr;
     P.acts = (__bf16 *)acts;
-    note_route(false, M, M_color);
-    if (M_color > 0) {
-        P.row0 = 0, P.M = M_color;
-        P.tape = (const uint4 *)p->ftape, P.tape_chunks = p->f0n / 16384;
-        if (const int rc = launch_train<false>(p, P, (hipStream_t)stream)) return rc;
-    }
-    if (M_color < M) {
-        P.row0 = M_color, P.M = M;
-        P.tape = (const uint4 *)(p->ftape + p->f1), P.tape_chunks = p->f1n / 16384;
-        if (const int rc = launch_train_trunk<false>(p, P, (hipStream_t)stream)) return rc;
-    }
-    return NLR_OK;
+    return launch_rows<false>(p, P, M, M_color, (hipStream_t)stream);
 }
 
 extern "C" int nlr_mlp_train_forward(const NlrTrainPlan *p, const float *features, const float *enc, uint32_t M, uint32_t S, float *density,
@@ -894,18 +864,7 @@ static int train_backward(const NlrTrainPlan *p, uint32_t M, uint32_t M_color, u
     P.g_density = g_density, P.g_rgb = g_rgb, P.g_sem = (p->sem && semantic) ? g_semantic : nullptr, P.g_inten = p->inten ? g_intensity : nullptr;
     P.gacts = (__bf16 *)gacts;
     P.d_feat = d_features;
-    note_route(true, M, M_color);
-    if (M_color > 0) {
-        P.row0 = 0, P.M = M_color;
-        P.tape = (const uint4 *)p->btape, P.tape_chunks = p->b0n / 16384;
-        if (const int rc = launch_train<true>(p, P, (hipStream_t)stream)) return rc;
-    }
-    if (M_color < M) {
-        P.row0 = M_color, P.M = M;
-        P.tape = (const uint4 *)(p->btape + p->b1), P.tape_chunks = p->b1n / 16384;
-        if (const int rc = launch_train_trunk<true>(p, P, (hipStream_t)stream)) return rc;
-    }
-    return NLR_OK;
+    return launch_rows<true>(p, P, M, M_color, (hipStream_t)stream);
 }
 
 extern "C" int nlr_mlp_train_backward(const NlrTrainPlan *p, uint32_t M, uint32_t S, const float *density, const float *rgb, const float *semantic,

@@ -213,66 +213,32 @@ __global__ void __launch_bounds__(256) nlr_mlp_wgrad_reduce_kernel(const float *
     out[i] = s;
 }
 
-// ---- the job list of a plan: every (Linear, 128 output rows, 128 input columns) of the header's table ---------------------------
-struct WgBlock {
-    uint32_t src, col, n;
-};
+// ---- the job list of a plan: every (Linear, 128 output rows, 128 input columns) of the plan's layer table ---------------------------
 static int build_jobs(const NlrTrainPlan *p, WgJob *jobs, uint32_t *n_jobs) {
     uint32_t n = 0;
-    const uint32_t W = p->W, WB = p->WB, D = p->D, K = p->K, aw = p->act_w;
-    const uint32_t c_hid = 0, c_hbe = 64, c_q = 64 + WB, c_x = c_q + 32 * p->HT;
     *n_jobs = 0;
-    struct L {  // one Linear: rows = gacts columns [g_col + o_off, + n_out), columns = its input blocks in order
-
-        uint32_t g_col, o_off, n_out;
-        WgBlock b[3];
-        uint32_t nb;
-        uint32_t color;  // a view layer or rgb_layer
-    };
-    std::vector<L> ls;
-    const WgBlock hbe = {0, c_hbe, WB}, encb = {2, 0, p->E};
-    ls.push_back({c_hid, 0, 64, {{1, 0, p->F}}, 1, 0});
-    ls.push_back({c_hbe, 0, WB, {{0, c_hid, 64}}, 1, 0});
-    uint32_t r0 = 0;
-    if (p->sem) {
-        ls.push_back({c_q, 0, 64, {hbe}, 1, 0});
-        ls.push_back({aw, 0, K, {{0, c_q, 64}}, 1, 0});
-        r0 = 64;
-    }
-    if (p->inten) {
-        ls.push_back({c_q + r0, 0, 64, {hbe}, 1, 0});
-        ls.push_back({aw, K, 1, {{0, c_q + r0, 64}}, 1, 0});
-    }
-    ls.push_back({c_x, 0, W, {hbe, encb}, 2, 1});
-    ls.push_back({c_x + W, 0, W, {{0, c_x, W}, hbe, encb}, 3, 1});
-    for (uint32_t l = 2; l < D; ++l) ls.push_back({c_x + l * W, 0, W, {{0, c_x + (l - 1) * W, W}}, 1, 1});
-    ls.push_back({aw + 32, 0, 3, {{0, c_x + (D - 1) * W, W}}, 1, 1});
-    if (2 * ls.size() != p->offs.size()) return NLR_ERR_INVALID;
-    n = 0;
-    for (size_t q = 0; q < ls.size(); ++q) {
-        const L &l = ls[q];
-        const uint32_t w_off = p->offs[2 * q], b_off = p->offs[2 * q + 1];
+    for (const TrainLinear &l : p->linears) {
         uint32_t n_in_total = 0;
-        for (uint32_t k = 0; k < l.nb; ++k) n_in_total += l.b[k].n;
+        for (uint32_t k = 0; k < l.n_in; ++k) n_in_total += l.in[k].n;
         for (uint32_t o0 = 0; o0 < l.n_out; o0 += 128) {
             uint32_t i0 = 0;
             bool first = true;
-            for (uint32_t k = 0; k < l.nb; ++k) {
-                for (uint32_t c = 0; c < l.b[k].n; c += 128) {
+            for (uint32_t k = 0; k < l.n_in; ++k) {
+                for (uint32_t c = 0; c < l.in[k].n; c += 128) {
                     if (n >= NLR_WG_MAX_JOBS) return NLR_ERR_UNSUPPORTED;
                     WgJob &j = jobs[n++];
-                    const uint32_t rows = l.n_out - o0 < 128 ? l.n_out - o0 : 128, cols = l.b[k].n - c < 128 ? l.b[k].n - c : 128;
-                    j.g_col = (uint16_t)(l.g_col + o0);
+                    const uint32_t rows = l.n_out - o0 < 128 ? l.n_out - o0 : 128, cols = l.in[k].n - c < 128 ? l.in[k].n - c : 128;
+                    j.g_col = (uint16_t)(l.g_col - l.o_off + o0);
                     j.o_lo = (uint16_t)l.o_off, j.o_hi = (uint16_t)(l.o_off + rows);
-                    j.x_src = (uint16_t)l.b[k].src, j.x_col = (uint16_t)(l.b[k].col + c), j.n_in = (uint16_t)cols;
+                    j.x_src = (uint16_t)l.in[k].src, j.x_col = (uint16_t)(l.in[k].col + c), j.n_in = (uint16_t)cols;
                     j.dst_ld = (uint16_t)n_in_total;
                     j.has_bias = first ? 1 : 0;
                     j.color = (uint16_t)l.color;
-                    j.dst = w_off + o0 * n_in_total + i0 + c;
-                    j.bias = b_off + o0;
+                    j.dst = l.w_off + o0 * n_in_total + i0 + c;
+                    j.bias = l.b_off + o0;
                     first = false;
                 }
-                i0 += l.b[k].n;
+                i0 += l.in[k].n;
             }
         }
     }

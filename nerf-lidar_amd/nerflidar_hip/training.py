@@ -10,7 +10,7 @@
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, Optional
+from typing import Dict, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -259,21 +259,12 @@ def _wgrad_bmm(level, M, f, e, acts, gacts, M_color=None):
     [dW, db, dW, db, ..] in the order of `TrainableNerfLevel._mlp_params`.  `_FusedMLP.backward` without `fused_wgrad` and
     `scripts/wgrad_bench.py` call this same code.  M_color (rows, None = M): the view layers and rgb_layer reduce over the first
     M_color rows only - the split kernels leave their columns of the later rows unwritten."""
-    plan, cfg = level._plan, level.cfg
-    dev = f.device
-    K = cfg.class_num if cfg.use_semantic else 0
-    # ---- weight gradients: plain GEMMs over the saved tensors (f32 accumulate and result)
-    W, WB, D = cfg.net_width_viewdirs, cfg.bottleneck_width, cfg.net_depth_viewdirs
-    HH = (64 if K else 0) + (64 if cfg.use_intensity else 0)
-    c_hid, c_hbe, c_q, c_x = 0, 64, 64 + WB, 64 + WB + HH
-    a = lambda c0, n: acts[:, c0:c0 + n]
-    g = lambda c0, n: gacts[:, c0:c0 + n]
-    E = cfg.dim_dir_enc
-    enc_s = e[:, :E].to(torch.bfloat16).repeat_interleave(level._S, dim=0)  # the bf16 values the forward chain consumed
+    plan, dev = level._plan, f.device
+    # the input blocks of the plan's layer table: columns of acts, the grid features, the direction encoding of the sample's ray
+    # (first E columns) - the bf16 values the forward chain consumed
+    srcs = (acts, f.to(torch.bfloat16), e[:, :level.cfg.dim_dir_enc].to(torch.bfloat16).repeat_interleave(level._S, dim=0))
 
-    # [M, out]^T . [M, in_0 | in_1 | ..]: bf16 operands, f32 accumulation.  The reduction runs over M (10^5..10^6) into a
-    # 256 x 256 result: as ONE library GEMM that is 16 output tiles = 16 busy CUs, so M is cut into `ck` batches (split-K as a
-    # batched GEMM over strided views, no copies) whose partial results are summed in f32.
+    # ---- weight gradients: plain GEMMs over the saved tensors (f32 accumulate and result)
     grads = []
 
     def linear_over(Mr):
@@ -300,40 +291,26 @@ def _wgrad_bmm(level, M, f, e, acts, gacts, M_color=None):
 
         return lin
 
-    lin = linear_over(M)
-    lin(g(c_hid, 64), f.to(torch.bfloat16))
-    lin(g(c_hbe, WB), a(c_hid, 64))
-    r0 = 0
-    if K:
-        lin(g(c_q, 64), a(c_hbe, WB))
-        lin(g(plan.act_w, K), a(c_q, 64))
-        r0 = 64
-    if cfg.use_intensity:
-        lin(g(c_q + r0, 64), a(c_hbe, WB))
-        lin(g(plan.act_w + K, 1), a(c_q + r0, 64))
-    if M_color is not None and M_color != M:
-        lin = linear_over(M_color)
-    lin(g(c_x, W), a(c_hbe, WB), enc_s)
-    if D > 1:
-        lin(g(c_x + W, W), a(c_x, W), a(c_hbe, WB), enc_s)
-    for l in range(2, D):
-        lin(g(c_x + l * W, W), a(c_x + (l - 1) * W, W))
-    lin(g(plan.act_w + 32, 3), a(c_x + (D - 1) * W, W))
+    lin, rows = linear_over(M), M
+    for l in plan.linears:
+        if l.color and M_color not in (None, rows):
+            lin, rows = linear_over(M_color), M_color
+        lin(gacts[:, l.g_col:l.g_col + l.n_out], *(srcs[src][:, col:col + n] for src, col, n in l.blocks))
     return grads
 
 
 class _FusedMLP(torch.autograd.Function):
     """The Linear stack of ZI/models.py:1116-1251 (density trunk, heads, view MLP, rgb) as two MFMA-chain kernels.  The weight
     gradients are GEMMs over the tensors those kernels save: dW_l = (d pre-activation_l)^T . (input_l), M-long reductions: library
-    GEMMs (`_wgrad_bmm`) or, with `fused_wgrad`, `nlr_mlp_train_wgrad` (csrc/nlr_mlp_wgrad.hip).  With `level._color_rays` (an
-    integer, `TrainableNerfLevel.forward(color_rays=..)`) the three `_split` entry points: the rows of the later rays run the trunk
-    and the heads only."""
+    GEMMs (`_wgrad_bmm`) or, with `fused_wgrad`, `nlr_mlp_train_wgrad` (csrc/nlr_mlp_wgrad.hip).  Always through the three `_split`
+    entry points: with `level._color_rays` (an integer, `TrainableNerfLevel.forward(color_rays=..)`) the rows of the later rays run
+    the trunk and the heads only, without it M_color = M, which is the unsplit call (header section 6b)."""
 
     @staticmethod
     def forward(ctx, feats, enc, level, *params):
         plan = level._plan
         M, S = feats.shape[0], level._S
-        Mc = None if level._color_rays is None else level._color_rays * S
+        Mc = M if level._color_rays is None else level._color_rays * S
         dev = feats.device
         flat = torch.cat([p.detach().reshape(-1).float() for p in params])
         new = lambda *s, dtype=torch.float32: torch.empty(*s, device=dev, dtype=dtype)
@@ -348,12 +325,8 @@ class _FusedMLP(torch.autograd.Function):
         with torch.cuda.device(dev):
             st = _lib.current_stream()
             _lib.check(L.nlr_train_pack(plan.handle, _lib.ptr(flat), st), "nlr_train_pack")
-            if Mc is None:
-                _lib.check(L.nlr_mlp_train_forward(plan.handle, _lib.ptr(f), _lib.ptr(e), M, S, _lib.ptr(density), _lib.ptr(rgb), _lib.ptr(sem),
-                                                   _lib.ptr(inten), _lib.ptr(acts), st), "nlr_mlp_train_forward")
-            else:
-                _lib.check(L.nlr_mlp_train_forward_split(plan.handle, _lib.ptr(f), _lib.ptr(e), M, Mc, S, _lib.ptr(density), _lib.ptr(rgb),
-                                                         _lib.ptr(sem), _lib.ptr(inten), _lib.ptr(acts), st), "nlr_mlp_train_forward_split")
+            _lib.check(L.nlr_mlp_train_forward_split(plan.handle, _lib.ptr(f), _lib.ptr(e), M, Mc, S, _lib.ptr(density), _lib.ptr(rgb),
+                                                     _lib.ptr(sem), _lib.ptr(inten), _lib.ptr(acts), st), "nlr_mlp_train_forward_split")
         ctx.level, ctx.M, ctx.Mc = level, M, Mc
         ctx.save_for_backward(f, e, density, rgb, sem if sem is not None else density.new_empty(0),
                               inten if inten is not None else density.new_empty(0), acts)
@@ -376,10 +349,7 @@ class _FusedMLP(torch.autograd.Function):
         with torch.cuda.device(dev):
             tail = (_lib.ptr(density), _lib.ptr(rgb), _lib.ptr(sem) if sem.numel() else None, _lib.ptr(acts), _lib.ptr(gd), _lib.ptr(gr),
                     _lib.ptr(gs), _lib.ptr(gi), _lib.ptr(gacts), _lib.ptr(d_feat), _lib.current_stream())
-            if Mc is None:
-                _lib.check(_lib.lib().nlr_mlp_train_backward(plan.handle, M, level._S, *tail), "nlr_mlp_train_backward")
-            else:
-                _lib.check(_lib.lib().nlr_mlp_train_backward_split(plan.handle, M, Mc, level._S, *tail), "nlr_mlp_train_backward_split")
+            _lib.check(_lib.lib().nlr_mlp_train_backward_split(plan.handle, M, Mc, level._S, *tail), "nlr_mlp_train_backward_split")
         if getattr(level, "_keep_debug", False):  # tests look at the kernels' raw results
             level._dbg = {k: v.detach() for k, v in dict(acts=acts, gacts=gacts, d_feat=d_feat, feats=f, enc=e, density=density, rgb=rgb,
                                                         sem=sem, inten=inten).items()}
@@ -390,10 +360,7 @@ class _FusedMLP(torch.autograd.Function):
             with torch.cuda.device(dev):
                 tail = (_lib.ptr(f), _lib.ptr(e), _lib.ptr(acts), _lib.ptr(gacts), _lib.ptr(d_params), _lib.ptr(ws), ws.numel(),
                         _lib.current_stream())
-                if Mc is None:
-                    _lib.check(_lib.lib().nlr_mlp_train_wgrad(plan.handle, M, level._S, *tail), "nlr_mlp_train_wgrad")
-                else:
-                    _lib.check(_lib.lib().nlr_mlp_train_wgrad_split(plan.handle, M, Mc, level._S, *tail), "nlr_mlp_train_wgrad_split")
+                _lib.check(_lib.lib().nlr_mlp_train_wgrad_split(plan.handle, M, Mc, level._S, *tail), "nlr_mlp_train_wgrad_split")
             if getattr(level, "_keep_debug", False):
                 level._dbg["d_params"] = d_params.detach()
             grads, off = [], 0
@@ -405,7 +372,20 @@ class _FusedMLP(torch.autograd.Function):
         return (d_feat, None, None) + tuple(grads)
 
 
+class _Linear(NamedTuple):
+    """One row of `nlr_train_linear_table` (header section 6b); blocks: (src, col, n) with src 0 acts, 1 features, 2 enc."""
+    g_col: int
+    o_off: int
+    n_out: int
+    color: int
+    blocks: tuple
+    w_off: int
+    b_off: int
+
+
 class _TrainPlan:
+    TABLE_ROW = 16  # uint32 per Linear
+
     def __init__(self, cfg):
         h, n = C.c_void_p(None), C.c_uint32(0)
         F = cfg.grid_num_levels * cfg.grid_level_dim
@@ -415,6 +395,12 @@ class _TrainPlan:
                                                     C.byref(h), C.byref(n)), "nlr_train_plan_create")
         self.handle, self.n_params = h, int(n.value)
         self.act_w = int(_lib.lib().nlr_train_act_width(h))
+        rows = (C.c_uint32 * (self.TABLE_ROW * 32))()
+        n = _lib.lib().nlr_train_linear_table(h, rows, len(rows))
+        if n <= 0:
+            _lib.check(n or -1, "nlr_train_linear_table")
+        t = np.frombuffer(rows, dtype=np.uint32)[:n * self.TABLE_ROW].reshape(n, self.TABLE_ROW).tolist()
+        self.linears = [_Linear(*r[:4], tuple(tuple(r[5 + 3 * k:8 + 3 * k]) for k in range(r[4])), *r[14:]) for r in t]
 
     def __del__(self):
         try:
