@@ -39,7 +39,8 @@ enum {
 enum {
     NLR_PREC_F32 = 0,   /* every layer on exact-f32 MFMA (v_mfma_f32_16x16x4_f32): reference-grade */
     NLR_PREC_MIXED = 1, /* density/semantic/intensity layers f32 MFMA, view-MLP bf16 MFMA */
-    NLR_PREC_FAST = 2   /* density/semantic/intensity layers split-bf16 (hi+lo, 3 MFMAs), view bf16: the default of the Python host side, bench.py and smoke() */
+    NLR_PREC_FAST = 2   /* density/semantic/intensity layers split-bf16 (hi+lo, 3 MFMAs), view bf16: the default of the Python host side, bench.py and smoke().
+                         * density_layer.2 is multiplied into the layers that read the bottleneck when the model is created */
 };
 
 const char *nlr_last_error(void);

@@ -114,6 +114,25 @@ struct Mat {
     float get(uint32_t r, uint32_t c) const { return (r < rows && c < cols) ? a[(size_t)r * cols + c] : 0.0f; }
 };
 
+// The fold of density_layer.2 into a consumer of the bottleneck (NLR_PREC_FAST, nlr_mlp_kernel.h: FOLD): a layer that computes
+// A.b + c from the bottleneck b = W2.h + c2 computes (A.W2).h + (c + A.c2) from the trunk's hidden vector h.  `a` holds A in its
+// columns [col0, col0 + WB); the products are formed in double from the f32 checkpoint weights and rounded once.
+static Mat fold_w2(const Mat &a, uint32_t col0, const NlrLinear &w2, std::vector<float> &bias) {
+    const uint32_t WB = w2.out_features, H = w2.in_features;
+    Mat out(a.rows, H);
+    for (uint32_t r = 0; r < a.rows; ++r) {
+        for (uint32_t k = 0; k < H; ++k) {
+            double acc = 0.0;
+            for (uint32_t c = 0; c < WB; ++c) acc += (double)a.get(r, col0 + c) * (double)w2.weight[(size_t)c * H + k];
+            out.at(r, k) = (float)acc;
+        }
+        double acc = (double)bias[r];
+        for (uint32_t c = 0; c < WB; ++c) acc += (double)a.get(r, col0 + c) * (double)w2.bias[c];
+        bias[r] = (float)acc;
+    }
+    return out;
+}
+
 static Mat mat_from(const NlrLinear &l, uint32_t col0, uint32_t ncols) {
     Mat m(l.out_features, ncols);
     for (uint32_t r = 0; r < l.out_features; ++r)
@@ -247,9 +266,13 @@ static int build_level(NlrModel *m, LevelModel &lv, const NlrMlpDesc &d, uint32_
     lv.prec = prec;
     const int crit = (prec == NLR_PREC_FAST) ? TAPE_X3 : TAPE_F32;   // density trunk + heads
     const int view = (prec == NLR_PREC_F32) ? TAPE_F32 : TAPE_BF16;  // view MLP
+    // NLR_PREC_FAST: density_layer.2 is multiplied into the layers that read the bottleneck (fold_w2), which then read the 64-wide
+    // hidden vector of the trunk; D2 keeps its first unit (row 0 = the raw density).  The other two precisions are the exact-parity
+    // modes and keep the reference's layers as they are.
+    const bool fold = prec == NLR_PREC_FAST;
     // The tile's program (nlr_mlp_kernel.h): bf16 view MLP: [T V0 V1 | T V0 V1 | hidden.. | RGB] (the trunk + heads T and view
     // layers 0/1 run once per 32-sample half); exact-f32 chain: [T V0 V1 | hidden.. | RGB], consumed once per half.
-    std::vector<float> bias;  // b_d0 | b_d2 | b_h1 | b_h2 | view0 | view1 | view2.. | rgb, each padded to whole units of 32
+    std::vector<float> bias;  // b_d0 | b_d2 (fold: its first 32 rows) | b_h1 | b_h2 | view0 | view1 | view2.. | rgb, each padded to whole units of 32
     auto push_bias = [&](const float *b, uint32_t n, uint32_t pad) {
         for (uint32_t i = 0; i < pad; ++i) bias.push_back(i < n ? b[i] : 0.0f);
     };
@@ -260,8 +283,8 @@ static int build_level(NlrModel *m, LevelModel &lv, const NlrMlpDesc &d, uint32_
     // density trunk
     trunk.add(mat_from(d.density0, 0, lv.F), 64, Fp32, crit);
     push_bias(d.density0.bias, 64, 64);
-    trunk.add(mat_from(d.density2, 0, 64), lv.WB, 64, crit);
-    push_bias(d.density2.bias, lv.WB, lv.WB);
+    trunk.add(mat_from(d.density2, 0, 64), fold ? 32 : lv.WB, 64, crit);
+    push_bias(d.density2.bias, fold ? 32 : lv.WB, fold ? 32 : lv.WB);
     // heads: [sem0 ; int0] stacked, then a block-diagonal [sem2 | 0 ; 0 | int2] into one 32-row unit
     if (lv.HT) {
         const uint32_t HH = lv.HT * 32;
@@ -301,7 +324,8 @@ static int build_level(NlrModel *m, LevelModel &lv, const NlrMlpDesc &d, uint32_
             for (uint32_t c = 0; c < 64; ++c) h2.at(lv.int_row, r0 + c) = d.int2.weight[c];
             b2[lv.int_row] = d.int2.bias[0];
         }
-        trunk.add(h1, HH, lv.WB, crit);
+        if (fold) trunk.add(fold_w2(h1, 0, d.density2, b1), HH, 64, crit);
+        else trunk.add(h1, HH, lv.WB, crit);
         push_bias(b1.data(), HH, HH);
         trunk.add(h2, 32, HH, crit);
         push_bias(b2.data(), 32, 32);
@@ -315,10 +339,26 @@ static int build_level(NlrModel *m, LevelModel &lv, const NlrMlpDesc &d, uint32_
     if ((rc = check_linear(d.view[1], lv.W, in1, "lin_second_stage_1"))) return rc;
     NLR_CHECK_ARG(lv.E <= 32, "deg_view %u gives %u > 32 direction features -- no fused path", lv.deg, lv.E);
     TapeBuilder v01;
-    v01.add(mat_from(d.view[0], 0, in0), lv.W, lv.WB + 32, view);
-    push_bias(d.view[0].bias, lv.W, lv.W);
-    v01.add(mat_from(d.view[1], 0, in1), lv.W, lv.W + lv.WB + 32, view);
-    push_bias(d.view[1].bias, lv.W, lv.W);
+    if (fold) {  // layer 0 over [h | dir_enc], layer 1 over [x | h | dir_enc]
+        const Mat v0 = mat_from(d.view[0], 0, in0), v1 = mat_from(d.view[1], 0, in1);
+        std::vector<float> c0(d.view[0].bias, d.view[0].bias + lv.W), c1(d.view[1].bias, d.view[1].bias + lv.W);
+        const Mat a0 = fold_w2(v0, 0, d.density2, c0), a1 = fold_w2(v1, lv.W, d.density2, c1);
+        Mat f0(lv.W, 64 + lv.E), f1(lv.W, lv.W + 64 + lv.E);
+        for (uint32_t r = 0; r < lv.W; ++r) {
+            for (uint32_t c = 0; c < 64; ++c) f0.at(r, c) = a0.get(r, c), f1.at(r, lv.W + c) = a1.get(r, c);
+            for (uint32_t c = 0; c < lv.E; ++c) f0.at(r, 64 + c) = v0.get(r, lv.WB + c), f1.at(r, lv.W + 64 + c) = v1.get(r, lv.W + lv.WB + c);
+            for (uint32_t c = 0; c < lv.W; ++c) f1.at(r, c) = v1.get(r, c);
+        }
+        v01.add(f0, lv.W, 64 + 32, view);
+        push_bias(c0.data(), lv.W, lv.W);
+        v01.add(f1, lv.W, lv.W + 64 + 32, view);
+        push_bias(c1.data(), lv.W, lv.W);
+    } else {
+        v01.add(mat_from(d.view[0], 0, in0), lv.W, lv.WB + 32, view);
+        push_bias(d.view[0].bias, lv.W, lv.W);
+        v01.add(mat_from(d.view[1], 0, in1), lv.W, lv.W + lv.WB + 32, view);
+        push_bias(d.view[1].bias, lv.W, lv.W);
+    }
     TapeBuilder tb;
     auto append = [&](const TapeBuilder &x) { tb.bytes.insert(tb.bytes.end(), x.bytes.begin(), x.bytes.end()); };
     if (prec == NLR_PREC_F32) {

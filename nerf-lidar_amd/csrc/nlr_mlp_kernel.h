@@ -24,6 +24,14 @@
 //     as one extra zero-padded 32-feature k-block, so every GEMM has K % 32 == 0;
 //   * nothing but the weight tape is read from global memory after the tile's input loads: all biases sit in LDS and enter
 //     as the C operand of each accumulator chain's first MFMA.
+//   * NLR_PREC_FAST never forms the bottleneck.  density_layer.2 (64 -> 256) has no activation behind it (models.py:1157-1158:
+//     bottleneck = x), so b = W2.h + c2 is linear in the trunk's hidden vector h = relu(W0.f + c0), and the head layer H1, view
+//     layer 0 and the skip columns of view layer 1 are linear in b in front of their ReLU.  build_level multiplies W2 into those
+//     three once per model (products in double, rounded once); on the tape H1 has K = 64 instead of 256, view layer 0 reads
+//     [h | enc] (3 k-blocks instead of 9), view layer 1 [x | h | enc], and D2 is the single 32-row unit that holds row 0, the raw
+//     density, with the fragments and the MFMA order it always had: density and everything computed from it keep their bits.
+//     Per wave and 256-sample tile at width 256 with both heads: 4 432 MFMAs and 1 368 fragments instead of 6 112 and 2 056.
+//     The other two precisions are the exact-parity modes and run the reference's layers as they are.
 //   * precision: NLR_PREC_FAST = trunk + heads in split-bf16 (W = Wh + Wl, x = xh + xl, three MFMAs: ~2^-16), view MLP bf16;
 //     NLR_PREC_MIXED = trunk + heads on the exact-f32 MFMA (v_mfma_f32_16x16x4_f32); NLR_PREC_F32 = everything exact f32
 //     (the whole chain at half width, twice per tile).
@@ -503,26 +511,40 @@ __global__ void __launch_bounds__(256, 1) nlr_mlp_kernel(MlpParams P) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int col = lane & 15, q = lane >> 4;
     constexpr int HTA = HT > 0 ? HT : 1;
+    // FOLD (NLR_PREC_FAST): density_layer.2 has no activation behind it, so the bottleneck b = W2.h + c2 is linear in the trunk's hidden
+    // vector h = relu(W0.f + c0), and every consumer of b is linear in b in front of its own ReLU.  build_level multiplies W2 into the
+    // head layer H1, view layer 0 and the skip columns of view layer 1 once per model; the kernel never forms the bottleneck: those
+    // three GEMMs read the KB = 2 k-blocks of h, and D2 keeps the one output unit that holds row 0, the raw density (same fragments,
+    // same MFMA order as the unfolded unit 0: density and everything derived from it keep their bits).
+    constexpr bool FOLD = X3;
+    constexpr int KB = FOLD ? 2 : BW;    // k-blocks of the vector the heads and the view layers read: h (folded) or the bottleneck
+    constexpr int D2U = FOLD ? 1 : BW;   // output units of D2
     // bias block offsets (floats)
-    constexpr int OB_D0 = 0, OB_D2 = 64, OB_H1 = OB_D2 + BW * 32, OB_H2 = OB_H1 + HT * 32, OB_V0 = OB_H2 + 32;
+    constexpr int OB_D0 = 0, OB_D2 = 64, OB_H1 = OB_D2 + D2U * 32, OB_H2 = OB_H1 + HT * 32, OB_V0 = OB_H2 + 32;
     constexpr int OB_V1 = OB_V0 + WT * 32, OB_VL = OB_V1 + WT * 32;
     // ---- the tile's program on the tape (fragments; must match build_level in nlr_api.hip)
     constexpr int TF = X3 ? 2 : 1;                        // fragments per step in the trunk / heads
     constexpr int TK = X3 ? 1 : 2;                        // k-groups per 32 input features in the trunk / heads
     constexpr int VK = VIEW_F32 ? 2 : 1;                  // ... in the view MLP
-    constexpr int FR_D0 = 2 * (FT * TK) * 2 * TF, FR_D2 = BW * (2 * TK) * 2 * TF;
-    constexpr int FR_H1 = HT * (BW * TK) * 2 * TF, FR_H2 = HT > 0 ? (HT * TK) * 2 * TF : 0;
+    constexpr int FR_D0 = 2 * (FT * TK) * 2 * TF, FR_D2 = D2U * (2 * TK) * 2 * TF;
+    constexpr int FR_H1 = HT * (KB * TK) * 2 * TF, FR_H2 = HT > 0 ? (HT * TK) * 2 * TF : 0;
     constexpr int FR_T = FR_D0 + FR_D2 + FR_H1 + FR_H2;   // trunk + heads, one half
-    constexpr int FR_V0 = WT * ((BW + 1) * VK) * 2, FR_V1 = WT * ((WT + BW + 1) * VK) * 2;
+    constexpr int FR_V0 = WT * ((KB + 1) * VK) * 2, FR_V1 = WT * ((WT + KB + 1) * VK) * 2;
     constexpr int FR_HL = WT * (WT * VK) * 2, FR_RGB = (WT * VK);
     static_assert(FR_HL % NLR_CHUNK_FRAGS == 0, "hidden view layers must cover whole chunks (width 128 or 256)");
     // bf16 view MLP: [T V0 V1 | T V0 V1 | hidden x (depth-2) | RGB];  f32 view MLP: [T V0 V1 | hidden | RGB] once per half
     constexpr int FR_HALF = LIDAR ? FR_T : FR_T + FR_V0 + FR_V1;
-    // (LIDAR: a signal() of the tape, which waits for this wave's loads, lies between the request of the next tile's inputs and
-    // the end of the second half)
-    static_assert(!LIDAR || FR_T >= 2 * NLR_CHUNK_FRAGS, "LiDAR-only: the second half must span a whole chunk");
     constexpr int F_HID = VIEW_F32 ? FR_HALF : 2 * FR_HALF;
     constexpr int F_END = F_HID + FR_RGB;                 // (+ hidden layers: whole chunks)
+    // The next tile's inputs are requested by LDS-DMA at tape position STAGE_AT of the tile's program and read at the start of the next
+    // tile with no wait of their own: a signal() of the tape (position NLR_SIG_F of every chunk, s_waitcnt vmcnt(0): it retires every
+    // load of the wave) has to lie between the request and the end of the program, padding steps included.  SIG_AT is the first one.
+    // The hidden view layers are whole chunks, so with at least one of them the condition holds; without one (view depth 2) and for
+    // the LiDAR-only program it depends on where the request falls in its chunk, and a tile that has no such signal waits itself.
+    constexpr int STAGE_AT = LIDAR ? FR_T : F_HID, PROG_END = nlr_ceil_div(LIDAR ? 2 * FR_T : F_END, NLR_CHUNK_FRAGS) * NLR_CHUNK_FRAGS;
+    constexpr int SIG_AT = STAGE_AT <= NLR_SIG_F ? NLR_SIG_F : nlr_ceil_div(STAGE_AT - NLR_SIG_F, NLR_CHUNK_FRAGS) * NLR_CHUNK_FRAGS + NLR_SIG_F;
+    constexpr bool STAGE_SIG = SIG_AT < PROG_END;         // (without hidden layers)
+    static_assert(!LIDAR || STAGE_SIG, "LiDAR-only: no tape signal between the request of the next tile's inputs and their first read");
 
     const uint32_t ntiles = (P.M + NLR_TILE - 1) / NLR_TILE;
     for (uint32_t i = threadIdx.x * 4; i < P.bias_count; i += 1024)
@@ -803,14 +825,15 @@ __global__ void __launch_bounds__(256, 1) nlr_mlp_kernel(MlpParams P) {
             if (col < 8 && s0 < P.M) P.seg[(size_t)(s0 >> 5) * 32 + 16 * (col >> 2) + 4 * q + (col & 3)] = v;
         }
     };
-    // one piece every HSTEP steps of view layer 0 of the same half (the layer with the fewest live registers)
-    constexpr int SV0 = WT * (BW + 1) * 2;
-    constexpr int HSTEP = SV0 / NHP;
-    static_assert(!COMP || HSTEP >= 1, "not enough steps for the compositing pieces");
+    // one piece every HSTEP steps of view layers 0 and 1 of the same half (folded, layer 0 of a width-128 view MLP has 24 steps: fewer
+    // than there are pieces)
+    constexpr int SV0 = WT * (KB + 1) * 2, SV1 = WT * (WT + KB + 1) * 2;
+    constexpr int HSTEP = (SV0 + SV1) / NHP;
+    static_assert(!COMP || LIDAR || HSTEP >= 1, "not enough steps for the compositing pieces");
 
     if constexpr (!VIEW_F32) {
         // =================================================== bf16 view MLP ===================================================
-        BT<4> hbe[BW + 1];  // [bottleneck | dir-enc] k-blocks of both halves (column tiles 2h, 2h+1 belong to half h)
+        BT<4> hbe[KB + 1];  // [bottleneck (FOLD: hi part of h) | dir-enc] k-blocks of both halves (column tiles 2h, 2h+1 belong to half h)
         Unit<2> fin[FT], encu[2];
         auto trunk = [&](auto hh, Unit<2> &lo_out, float (&raw_out)[2]) {
             constexpr int h = decltype(hh)::value;
@@ -832,53 +855,50 @@ __global__ void __launch_bounds__(256, 1) nlr_mlp_kernel(MlpParams P) {
 #pragma unroll
                 for (int t = 0; t < FT; ++t) nlr_split_all<false, 0>(fh[t], fl[t], fin[t]);
                 if constexpr (h == 0) NLR_STAMP(2);  // features split
-                BT<2> dh[2], dl[2];
+                // h = relu(D0): the hi part goes straight into the view MLP's operand (column tiles of this half), the lo part stays local
+                BT<2> dl[2];
                 nlr_gemm<2, FT, 2, 2, 2, F0, 8>(
                     tp, [&](auto o, f32x4(&b)[2]) { bias_rows(lds_bias + OB_D0 + 32 * decltype(o)::value, b); },
                     [&](Unit<2> &u, auto g, auto j, const uint4 &f0, const uint4 &f1, const f32x4 &bj) {
                         constexpr int G = decltype(g)::value, J = decltype(j)::value;
                         nlr_mma_x3<G == 0, 0>(u.a[J], bj, f0, f1, fh[G], fl[G]);
                     },
-                    [&](auto o, auto p, const Unit<2> &u) { nlr_split_piece<true, decltype(p)::value, 0>(dh[decltype(o)::value], dl[decltype(o)::value], u); });
-                if constexpr (h == 0) NLR_STAMP(3);  // D0
-                BT<2> hbl[BW];
-                nlr_gemm<BW, 2, 2, 2, 2, F0 + FR_D0, 8>(
-                    tp, [&](auto o, f32x4(&b)[2]) { bias_rows(lds_bias + OB_D2 + 32 * decltype(o)::value, b); },
-                    [&](Unit<2> &u, auto g, auto j, const uint4 &f0, const uint4 &f1, const f32x4 &bj) {
-                        constexpr int G = decltype(g)::value, J = decltype(j)::value;
-                        nlr_mma_x3<G == 0, 0>(u.a[J], bj, f0, f1, dh[G], dl[G]);
-                    },
                     [&](auto o, auto p, const Unit<2> &u) {
                         constexpr int O = decltype(o)::value, Pc = decltype(p)::value;
-                        if constexpr (O == 0 && Pc == 0) {
-                            raw[0] = u.a[0][0][0];
-                            raw[1] = u.a[0][1][0];
-                        }
-                        // hi part straight into the view MLP's operand (column tiles of this half), lo part local
                         constexpr int n = Pc >> 2, jb = (Pc >> 1) & 1, pr = Pc & 1;
-                        const f32x2 xv = {u.a[jb][n][2 * pr], u.a[jb][n][2 * pr + 1]};
+                        f32x2 xv = {u.a[jb][n][2 * pr], u.a[jb][n][2 * pr + 1]};
+                        xv = __builtin_elementwise_max(xv, (f32x2){0.0f, 0.0f});
                         const bf16x2 hv = __builtin_convertvector(xv, bf16x2);
                         const bf16x2 lv = __builtin_convertvector(xv - __builtin_convertvector(hv, f32x2), bf16x2);
 #pragma unroll
                         for (int e = 0; e < 2; ++e) {
                             hbe[O].n[2 * h + n][4 * jb + 2 * pr + e] = hv[e];
-                            hbl[O].n[n][4 * jb + 2 * pr + e] = lv[e];
+                            dl[O].n[n][4 * jb + 2 * pr + e] = lv[e];
                         }
+                    });
+                if constexpr (h == 0) NLR_STAMP(3);  // D0
+                // split-bf16 step against h: hi.hi, hi.lo, lo.hi per column tile (the order of nlr_mma_x3)
+                auto mma_h = [&](Unit<2> &u, auto g, auto j, const uint4 &f0, const uint4 &f1, const f32x4 &bj) {
+                    constexpr int G = decltype(g)::value, J = decltype(j)::value;
+#pragma unroll
+                    for (int n = 0; n < 2; ++n) {
+                        u.a[J][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(nlr_as<bf16x8>(f0), hbe[G].n[2 * h + n], G == 0 ? bj : u.a[J][n], 0, 0, 0);
+                        u.a[J][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(nlr_as<bf16x8>(f0), dl[G].n[n], u.a[J][n], 0, 0, 0);
+                        u.a[J][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(nlr_as<bf16x8>(f1), hbe[G].n[2 * h + n], u.a[J][n], 0, 0, 0);
+                    }
+                };
+                // D2: the one unit that holds row 0, the raw density
+                nlr_gemm<1, 2, 2, 2, 2, F0 + FR_D0, 1>(
+                    tp, [&](auto, f32x4(&b)[2]) { bias_rows(lds_bias + OB_D2, b); }, mma_h,
+                    [&](auto, auto, const Unit<2> &u) {
+                        raw[0] = u.a[0][0][0];
+                        raw[1] = u.a[0][1][0];
                     });
                 if constexpr (h == 0) NLR_STAMP(4);  // D2
                 if constexpr (HT > 0) {
                     BT<2> qh[HTA], ql[HTA];
-                    nlr_gemm<HT, BW, 2, 2, 2, F0 + FR_D0 + FR_D2, 8>(
-                        tp, [&](auto o, f32x4(&b)[2]) { bias_rows(lds_bias + OB_H1 + 32 * decltype(o)::value, b); },
-                        [&](Unit<2> &u, auto g, auto j, const uint4 &f0, const uint4 &f1, const f32x4 &bj) {
-                            constexpr int G = decltype(g)::value, J = decltype(j)::value;
-#pragma unroll
-                            for (int n = 0; n < 2; ++n) {
-                                u.a[J][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(nlr_as<bf16x8>(f0), hbe[G].n[2 * h + n], G == 0 ? bj : u.a[J][n], 0, 0, 0);
-                                u.a[J][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(nlr_as<bf16x8>(f0), hbl[G].n[n], u.a[J][n], 0, 0, 0);
-                                u.a[J][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(nlr_as<bf16x8>(f1), hbe[G].n[2 * h + n], u.a[J][n], 0, 0, 0);
-                            }
-                        },
+                    nlr_gemm<HT, KB, 2, 2, 2, F0 + FR_D0 + FR_D2, 8>(
+                        tp, [&](auto o, f32x4(&b)[2]) { bias_rows(lds_bias + OB_H1 + 32 * decltype(o)::value, b); }, mma_h,
                         [&](auto o, auto p, const Unit<2> &u) { nlr_split_piece<true, decltype(p)::value, 0>(qh[decltype(o)::value], ql[decltype(o)::value], u); });
                     if constexpr (h == 0) NLR_STAMP(5);  // H1
                     nlr_gemm<1, HT, 2, 2, 2, F0 + FR_D0 + FR_D2 + FR_H1, 1>(
@@ -990,20 +1010,21 @@ __global__ void __launch_bounds__(256, 1) nlr_mlp_kernel(MlpParams P) {
             hst.lo = hlo;
             hst.raw[0] = hraw[0];
             hst.raw[1] = hraw[1];
-            nlr_pack_all<false, 2 * h>(hbe[BW], encu[h]);
+            nlr_pack_all<false, 2 * h>(hbe[KB], encu[h]);
             Unit<2> cx;
-            nlr_gemm_pipe<WT, BW + 1, 2, 2, F0, 8, 0, 1, true>(
+            auto comp_bg = [&](auto st) {  // step `st` of view layers 0 + 1 of this half
+                constexpr int IDX = decltype(st)::value;
+                if constexpr (COMP && IDX % HSTEP == HSTEP / 2 && IDX / HSTEP < NHP) head_piece(hh, ic<IDX / HSTEP>{}, hst);
+            };
+            nlr_gemm_pipe<WT, KB + 1, 2, 2, F0, 8, 0, 1, true>(
                 tp, cx, [&](auto o, f32x4(&b)[2]) { bias_rows(lds_bias + OB_V0 + 32 * decltype(o)::value, b); },
                 [&](Unit<2> &u, auto g, auto j, const uint4 &f0, const uint4 &, const f32x4 &bj) {
                     constexpr int G = decltype(g)::value, J = decltype(j)::value;
                     nlr_mma_bf16<G == 0, 2 * h>(u.a[J], bj, f0, hbe[G]);
                 },
                 [&](auto o, auto p, const Unit<2> &u) { nlr_pack_piece<true, decltype(p)::value, 2 * h>(x[decltype(o)::value], u); }, nop,
-                [&](auto st) {
-                    constexpr int IDX = decltype(st)::value;
-                    if constexpr (COMP && IDX % HSTEP == HSTEP / 2 && IDX / HSTEP < NHP) head_piece(hh, ic<IDX / HSTEP>{}, hst);
-                });
-            nlr_gemm_pipe<WT, WT + BW + 1, 2, 2, F0 + FR_V0, 8, 8, (WT - 1) * 2, true>(
+                [&](auto st) { comp_bg(st); });
+            nlr_gemm_pipe<WT, WT + KB + 1, 2, 2, F0 + FR_V0, 8, 8, (WT - 1) * 2, true>(
                 tp, cyh[h], [&](auto o, f32x4(&b)[2]) { bias_rows(lds_bias + OB_V1 + 32 * decltype(o)::value, b); },
                 [&](Unit<2> &u, auto g, auto j, const uint4 &f0, const uint4 &, const f32x4 &bj) {
                     constexpr int G = decltype(g)::value, J = decltype(j)::value;
@@ -1011,7 +1032,8 @@ __global__ void __launch_bounds__(256, 1) nlr_mlp_kernel(MlpParams P) {
                     else nlr_mma_bf16<false, 2 * h>(u.a[J], bj, f0, hbe[G - WT]);
                 },
                 [&](auto o, auto p, const Unit<2> &u) { nlr_pack_piece<true, decltype(p)::value, 2 * h>(y[decltype(o)::value], u); },
-                [&](auto p) { nlr_pack_piece<true, decltype(p)::value, 2 * h>(x[WT - 1], cx); });
+                [&](auto p) { nlr_pack_piece<true, decltype(p)::value, 2 * h>(x[WT - 1], cx); },
+                [&](auto st) { comp_bg(ic<SV0 + decltype(st)::value>{}); });
         };
         trunk(ic<0>{}, hlo, hraw);
         NLR_STAMP(8);  // (unused)
@@ -1121,6 +1143,9 @@ __global__ void __launch_bounds__(256, 1) nlr_mlp_kernel(MlpParams P) {
         }
         NLR_STAMP(13);  // rgb stores
         nlr_pad<F_END % NLR_CHUNK_FRAGS>(tp);
+        if constexpr (!STAGE_SIG) {  // no hidden layer and no tape signal behind the request: the next tile's inputs are waited for here
+            if (staged && P.depth == 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
         NLR_STAMP(14);  // tape padding
 #ifdef NLR_STAMPS
         if (tile + gridDim.x >= ntiles && threadIdx.x == 0 && blockIdx.x < 1024) {

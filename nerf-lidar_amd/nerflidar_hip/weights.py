@@ -188,3 +188,35 @@ def inflate_hashmaps(sd: Dict[str, np.ndarray], mc: ModelConfig, log2_hashmap: i
         out[f"{prefix}.encoder.embeddings"] = table
         out[f"{prefix}.encoder.offsets"], out[f"{prefix}.encoder.grid_sizes"] = off_b, sizes_b
     return out, big
+
+
+def fold_density_layer2(sd: Dict[str, np.ndarray], cfg: MLPConfig, prefix: str = "nerf_mlp") -> Dict[str, np.ndarray]:
+    """The matrices `NLR_PREC_FAST` evaluates a NerfMLP with (float64; the library's `build_level` forms the same products in double and
+    rounds them once to float).  density_layer.2 (W2, c2) has no activation behind it, so a layer A.b + c that reads the bottleneck
+    b = W2.h + c2 equals (A.W2).h + (c + A.c2) on the trunk's 64-wide hidden vector h: the head layers 0, view layer 0 and the
+    bottleneck columns of the layer behind the skip concat are replaced that way, and of density_layer.2 the raw-density row stays.
+    With `no_sem_layer` the logits b[1:1+K] become rows 1..K of W2 (`sem_pass`).  Every other layer is returned unchanged."""
+    g = lambda name: np.asarray(sd[f"{prefix}.{name}"], np.float64)
+    W2, c2 = g("density_layer.2.weight"), g("density_layer.2.bias")
+    wb, w = cfg.bottleneck_width, cfg.net_width_viewdirs
+    if cfg.skip_layer_dir != 0 or cfg.net_depth_viewdirs < 2:
+        raise ValueError("the fold is defined for the fused path: skip_layer_dir = 0, net_depth_viewdirs >= 2")
+    out = {k[len(prefix) + 1:]: np.asarray(v, np.float64) for k, v in sd.items()
+           if k.startswith(prefix + ".") and "encoder." not in k}
+
+    def fold(name, col0):
+        A, c = g(name + ".weight"), g(name + ".bias")
+        out[name + ".weight"] = np.concatenate([A[:, :col0], A[:, col0:col0 + wb] @ W2, A[:, col0 + wb:]], axis=1)
+        out[name + ".bias"] = c + A[:, col0:col0 + wb] @ c2
+
+    out["density_layer.2.weight"], out["density_layer.2.bias"] = W2[:1], c2[:1]
+    if cfg.use_semantic:
+        if cfg.no_sem_layer:
+            out["sem_pass.weight"], out["sem_pass.bias"] = W2[1:1 + cfg.class_num], c2[1:1 + cfg.class_num]
+        else:
+            fold("sem_layer.0", 0)
+    if cfg.use_intensity:
+        fold("intensity_layer.0", 0)
+    fold("lin_second_stage_0", 0)
+    fold("lin_second_stage_1", w)
+    return out
