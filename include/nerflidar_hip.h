@@ -486,6 +486,28 @@ int nlr_box_winner(const float *tdist, const float *origins, const float *direct
 int nlr_track_box_params(const float *tracks, const float *timestamps, uint32_t N, uint32_t n_obj, uint32_t T, float *box_params,
                          void *stream);
 
+/* (7c) Track refinement (train.py:244-268, posenet_v2.py:65-76): the adjoint of "tracks -> box-frame points and view directions of
+ *      the owned samples", i.e. of get_pose (ZI/obj_utils.py:431-475) + world2object (obj_utils.py:116-181) as the last level of
+ *      ZI/models.py:401-446 feeds them to the ObjMLPs - what torch autograd walks through gather / index_put in the reference.
+ *
+ * nlr_obj_frame_backward: the forward being differentiated is that of nlr_track_box_params and of the sample's box coordinates
+ *      p = scale * (rot(t_mid * d + o) + t_w_o), dir = normalize(scale * rot(viewdir)), rot with the reference's yaw quirk
+ *      (obj_utils.py:106-107).  The K owned samples come as three parallel int32 lists (ray, sample within the ray, owning track),
+ *      sorted by (ray, sample) as nonzero() of the owner map yields them; g_pts / g_dirs [K, 3] are the cotangents of p and dir.
+ *      g_tracks [n_obj, T, 9] is OVERWRITTEN: columns 0..6 = pose gradient times w1 on the nearer record and times 1 - w1 on the
+ *      second of every (ray, track) pair, columns 7 (timestamp: the weights carry no gradient) and 8 (track id) = 0; K = 0 gives
+ *      zeros.  The two records are chosen by the device function nlr_track_box_params chooses with.  Ray origins and directions
+ *      receive nothing (this is not pose refinement).  An index outside [0,N) x [0,S) x [0,n_obj) contributes nothing.
+ *      Sums are formed per (ray, track) run in registers, per workgroup in LDS and per slab in a fixed order, never by one atomic
+ *      per sample; a table of n_obj * T * 7 > 39936 floats does not fit in LDS and is accumulated with one global atomic per
+ *      (run, record, column) instead.  Either way the result is reproducible up to the order of float additions only, like the
+ *      grid scatter.  workspace: dev, at least nlr_obj_frame_backward_workspace_bytes(K, n_obj, T) bytes (0 on the atomic path). */
+size_t nlr_obj_frame_backward_workspace_bytes(uint32_t K, uint32_t n_obj, uint32_t T);
+int nlr_obj_frame_backward(const float *tracks, const float *timestamps, const float *origins, const float *directions,
+                           const float *viewdirs, const float *tdist, uint32_t N, uint32_t S, uint32_t n_obj, uint32_t T,
+                           const int32_t *ray_idx, const int32_t *sample_idx, const int32_t *track_idx, uint32_t K, const float *g_pts,
+                           const float *g_dirs, float *g_tracks, void *workspace, size_t workspace_bytes, void *stream);
+
 typedef struct NlrObjClassDesc {
     NlrMlpDesc mlp;
     uint32_t latent_size, split_latent;  /* Config.latent_size (0 = none), MLP.split_latent (models.py:881-885,924-925) */

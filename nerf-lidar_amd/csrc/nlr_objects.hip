@@ -55,15 +55,13 @@ extern "C" int nlr_box_winner(const float *tdist, const float *origins, const fl
 #include <vector>
 
 // ---- get_pose + world2object constants (obj_utils.py:431-475, :5-28,:158-170), one thread per (ray, track) ----------
-__global__ void __launch_bounds__(256) nlr_track_box_kernel(const float *__restrict__ tracks, const float *__restrict__ ts, uint32_t N,
-                                                           uint32_t n_obj, uint32_t T, float *__restrict__ box) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (size_t)N * n_obj) return;
-    const uint32_t ray = (uint32_t)(i / n_obj), o = (uint32_t)(i - (size_t)ray * n_obj);
-    const float time = ts[ray];
-    const float *tr = tracks + (size_t)o * T * 9;
-    // the two records closest in time (torch.sort(time_diff)[..., :2]); on equal distances the earlier record first
-    uint32_t i1 = 0, i2 = 0;
+// The two records of one track closest in time to `time` (torch.sort(time_diff)[..., :2]; on equal distances the earlier record
+// first) and the weight of the first.  nlr_track_box_kernel and its adjoint nlr_obj_frame_bwd_kernel both choose through this
+// function, so a tie between records cannot fall differently in the two.
+__device__ __forceinline__ void nlr_track_records(const float *__restrict__ tr, uint32_t T, float time, uint32_t &i1, uint32_t &i2,
+                                                  float &w1) {
+    i1 = 0;
+    i2 = 0;
     float d1 = INFINITY, d2 = INFINITY;
     for (uint32_t k = 0; k < T; ++k) {
         const float d = fabsf(time - tr[k * 9 + 7]);
@@ -78,8 +76,19 @@ __global__ void __launch_bounds__(256) nlr_track_box_kernel(const float *__restr
         }
     }
     const float t1 = tr[i1 * 9 + 7], t2 = tr[i2 * 9 + 7];
-    float w1 = fabsf(time - t2) / (fabsf(t1 - t2) + 1e-9f);
+    w1 = fabsf(time - t2) / (fabsf(t1 - t2) + 1e-9f);
     w1 = fminf(fmaxf(w1, 0.0f), 1.0f);
+}
+
+__global__ void __launch_bounds__(256) nlr_track_box_kernel(const float *__restrict__ tracks, const float *__restrict__ ts, uint32_t N,
+                                                           uint32_t n_obj, uint32_t T, float *__restrict__ box) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)N * n_obj) return;
+    const uint32_t ray = (uint32_t)(i / n_obj), o = (uint32_t)(i - (size_t)ray * n_obj);
+    const float *tr = tracks + (size_t)o * T * 9;
+    uint32_t i1, i2;
+    float w1;
+    nlr_track_records(tr, T, ts[ray], i1, i2, w1);
     float pose[7];
 #pragma unroll
     for (int c = 0; c < 7; ++c) pose[c] = w1 * tr[i1 * 9 + c] + (1.0f - w1) * tr[i2 * 9 + c];
@@ -107,6 +116,226 @@ extern "C" int nlr_track_box_params(const float *tracks, const float *timestamps
     hipLaunchKernelGGL(nlr_track_box_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)stream, tracks, timestamps, N,
                        n_obj, T, box_params);
     NLR_LAUNCH_CHECK("nlr_track_box_kernel");
+    return NLR_OK;
+}
+
+// ---- adjoint of "tracks -> box-frame points and directions of the owned samples" (track refinement, train.py:244-268) ---------
+// One lane per owned sample.  The lane repeats the forward of its (ray, track) pair - records and weight from nlr_track_records,
+// blended pose, cos / sin, scale - and turns the cotangents of its point and direction into the 7 pose gradients.  Written on
+// q = p_w - center: the reference's rotation, quirk included, is linear in the point, so rot(p_w) + rot(-center) = rot(q).
+// The reduction never sends one value per sample to memory:
+//   (1) the list is sorted by (ray, sample), so the samples of one (ray, track) pair lie in one or a few stretches of adjacent
+//       lanes: a segmented shuffle reduction leaves each stretch's sum with its first lane inside the wave;
+//   (2) that lane splits it by w1 / 1 - w1 onto the two records and adds the 14 values into the workgroup's LDS slot table
+//       [n_obj][T][7] (ds_add_f32: almost all runs of a workgroup land on the same few slots);
+//   (3) the workgroup writes its table as one slab of the workspace, and nlr_obj_frame_sum_kernel adds the slabs in a fixed order.
+// A slot table beyond NLR_OBJB_SLOTS floats of LDS (large n_obj * T) skips (2) and (3): the run heads add into the zeroed g_tracks
+// with global atomics, one per (run, record, column).
+#define NLR_OBJB_SLOTS 39936      // floats of LDS for the largest slot table (156 KiB of the CU's 160 KiB) ...
+#define NLR_OBJB_SLOTS_SMALL 4096 // ... and for the usual one (16 KiB: several workgroups share a CU)
+#define NLR_OBJB_MAX_BLOCKS 256   // slabs (one per CU of an MI355X): contiguous shares of the list, so a workgroup meets few (ray, track) pairs more than once
+
+struct ObjFrameBwd {
+    const float *tracks, *ts, *origins, *dirs, *viewdirs, *tdist;
+    uint32_t N, S, n_obj, T;
+    const int32_t *ray_idx, *sample_idx, *track_idx;
+    uint32_t K, per_block;  // samples per workgroup (multiple of 256)
+    const float *g_pts, *g_dirs;
+};
+
+// SLOTS: capacity of the LDS slot table in floats, 0 = no table (run heads add into g_tracks)
+template <int SLOTS>
+__global__ void __launch_bounds__(256) nlr_obj_frame_bwd_kernel(ObjFrameBwd a, float *__restrict__ out) {
+    constexpr bool LDS_SLOTS = SLOTS > 0;
+    __shared__ float slots[LDS_SLOTS ? SLOTS : 1];
+    const uint32_t n_slots = a.n_obj * a.T * 7;
+    if (LDS_SLOTS) {
+        for (uint32_t i = threadIdx.x; i < n_slots; i += 256) slots[i] = 0.0f;
+        __syncthreads();
+    }
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t lo = blockIdx.x * a.per_block, hi = lo + a.per_block < a.K ? lo + a.per_block : a.K;
+    for (uint32_t base = lo; base < hi; base += 256) {  // (uniform trip count per workgroup: the shuffles below see whole waves)
+        const uint32_t k = base + threadIdx.x;
+        bool valid = k < hi;
+        uint32_t ray = 0, smp = 0, o = 0;
+        if (valid) {
+            ray = (uint32_t)a.ray_idx[k];
+            smp = (uint32_t)a.sample_idx[k];
+            o = (uint32_t)a.track_idx[k];
+            valid = ray < a.N && smp < a.S && o < a.n_obj;  // an index outside the batch contributes nothing
+        }
+        float g[7] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+        uint32_t i1 = 0, i2 = 0;
+        float w1 = 0.0f;
+        if (valid) {
+            const float *tr = a.tracks + (size_t)o * a.T * 9;
+            nlr_track_records(tr, a.T, a.ts[ray], i1, i2, w1);
+            float pose[7];
+#pragma unroll
+            for (int c = 0; c < 7; ++c) pose[c] = w1 * tr[i1 * 9 + c] + (1.0f - w1) * tr[i2 * 9 + c];
+            const float cs = cosf(pose[3]), sn = sinf(pose[3]);
+            float sc[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) sc[c] = 1.0f / (pose[4 + c] / 2.0f + 1e-9f);
+            const float t0 = a.tdist[(size_t)ray * (a.S + 1) + smp], t1 = a.tdist[(size_t)ray * (a.S + 1) + smp + 1];
+            const float tm = 0.5f * (t0 + t1);
+            float q[3], vd[3], gp[3], gd[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                q[c] = (tm * a.dirs[(size_t)ray * 3 + c] + a.origins[(size_t)ray * 3 + c]) - pose[c];
+                vd[c] = a.viewdirs[(size_t)ray * 3 + c];
+                gp[c] = a.g_pts[(size_t)k * 3 + c];
+                gd[c] = a.g_dirs[(size_t)k * 3 + c];
+            }
+            float g_cs = 0.0f, g_sn = 0.0f, g_sc[3];
+            // p = scale * u, u = (cs q0 - sn q1, sn ux + cs q1, q2)
+            const float ux = cs * q[0] - sn * q[1], uy = sn * ux + cs * q[1];
+            g_sc[0] = gp[0] * ux;
+            g_sc[1] = gp[1] * uy;
+            g_sc[2] = gp[2] * q[2];
+            const float guy = gp[1] * sc[1], gux = gp[0] * sc[0] + sn * guy;
+            g_sn += ux * guy - q[1] * gux;
+            g_cs += q[1] * guy + q[0] * gux;
+            g[0] = -(cs * gux);
+            g[1] = -(cs * guy - sn * gux);
+            g[2] = -(gp[2] * sc[2]);
+            // dir = e / |e|, e = scale * v, v = (cs d0 - sn d1, sn vx + cs d1, d2)
+            const float vx = cs * vd[0] - sn * vd[1], vy = sn * vx + cs * vd[1];
+            const float e[3] = {sc[0] * vx, sc[1] * vy, sc[2] * vd[2]};
+            const float inv = 1.0f / sqrtf((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
+            const float n[3] = {e[0] * inv, e[1] * inv, e[2] * inv};
+            const float dot = (n[0] * gd[0] + n[1] * gd[1]) + n[2] * gd[2];
+            float ge[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) ge[c] = (gd[c] - n[c] * dot) * inv;
+            g_sc[0] += ge[0] * vx;
+            g_sc[1] += ge[1] * vy;
+            g_sc[2] += ge[2] * vd[2];
+            const float gvy = ge[1] * sc[1], gvx = ge[0] * sc[0] + sn * gvy;
+            g_sn += vx * gvy - vd[1] * gvx;
+            g_cs += vd[1] * gvy + vd[0] * gvx;
+            g[3] = cs * g_sn - sn * g_cs;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) g[4 + c] = g_sc[c] * (-0.5f * sc[c] * sc[c]);  // scale = 1 / (wlh / 2 + 1e-9)
+        }
+        // (1) segmented reduction over the runs of equal (ray, track) inside the wave.  A run is a stretch of ADJACENT lanes: along a
+        // ray the owner can change and come back (a box inside another), so lanes are matched by run number, not by (ray, track).
+        const uint32_t key_r = valid ? ray : 0xffffffffu, key_o = valid ? o : 0xffffffffu;
+        const uint32_t prev_r = __shfl_up(key_r, 1, 64), prev_o = __shfl_up(key_o, 1, 64);
+        const bool first = lane == 0 || prev_r != key_r || prev_o != key_o;
+        const uint32_t run = (uint32_t)__popcll(__ballot(first) & ((2ull << lane) - 1ull));  // number of run starts up to this lane
+        const bool head = valid && first;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const bool same = __shfl_down(run, d, 64) == run && lane + d < 64;
+#pragma unroll
+            for (int c = 0; c < 7; ++c) {
+                const float v = __shfl_down(g[c], d, 64);
+                g[c] += same ? v : 0.0f;
+            }
+        }
+        // (2) the run's sum onto its two records
+        if (head) {
+            const size_t r1 = (size_t)o * a.T + i1, r2 = (size_t)o * a.T + i2;
+#pragma unroll
+            for (int c = 0; c < 7; ++c) {
+                if (LDS_SLOTS) {
+                    atomicAdd(&slots[r1 * 7 + c], w1 * g[c]);
+                    atomicAdd(&slots[r2 * 7 + c], (1.0f - w1) * g[c]);
+                } else {
+                    atomicAdd(out + r1 * 9 + c, w1 * g[c]);
+                    atomicAdd(out + r2 * 9 + c, (1.0f - w1) * g[c]);
+                }
+            }
+        }
+    }
+    if (LDS_SLOTS) {  // (3) the workgroup's slab
+        __syncthreads();
+        float *slab = out + (size_t)blockIdx.x * n_slots;
+        for (uint32_t i = threadIdx.x; i < n_slots; i += 256) slab[i] = slots[i];
+    }
+}
+
+// g_tracks [n_obj * T, 9]: columns 0..6 = the sum of the slabs in slab order, columns 7 and 8 = 0
+__global__ void __launch_bounds__(256) nlr_obj_frame_sum_kernel(const float *__restrict__ slabs, uint32_t n_slabs, uint32_t n_rec,
+                                                               float *__restrict__ g_tracks) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_rec * 9) return;
+    const uint32_t rec = i / 9, c = i - rec * 9;
+    float s = 0.0f;
+    if (c < 7)
+        for (uint32_t b = 0; b < n_slabs; ++b) s += slabs[(size_t)b * n_rec * 7 + rec * 7 + c];
+    g_tracks[i] = s;
+}
+
+static inline uint32_t obj_frame_blocks(uint32_t K) {
+    const uint32_t nb = (K + 255) / 256;
+    return nb < NLR_OBJB_MAX_BLOCKS ? nb : NLR_OBJB_MAX_BLOCKS;
+}
+
+extern "C" size_t nlr_obj_frame_backward_workspace_bytes(uint32_t K, uint32_t n_obj, uint32_t T) {
+    const size_t n_slots = (size_t)n_obj * T * 7;
+    if (K == 0 || n_slots == 0 || n_slots > NLR_OBJB_SLOTS) return 0;  // (the large-table path adds into g_tracks directly)
+    return (size_t)obj_frame_blocks(K) * n_slots * sizeof(float);
+}
+
+extern "C" int nlr_obj_frame_backward(const float *tracks, const float *timestamps, const float *origins, const float *directions,
+                                      const float *viewdirs, const float *tdist, uint32_t N, uint32_t S, uint32_t n_obj, uint32_t T,
+                                      const int32_t *ray_idx, const int32_t *sample_idx, const int32_t *track_idx, uint32_t K,
+                                      const float *g_pts, const float *g_dirs, float *g_tracks, void *workspace, size_t workspace_bytes,
+                                      void *stream) {
+    if (n_obj == 0 || T == 0) return NLR_OK;
+    NLR_CHECK_ARG(g_tracks, "obj_frame_backward: g_tracks is NULL");
+    hipStream_t st = (hipStream_t)stream;
+    const size_t n_rec = (size_t)n_obj * T, n_slots = n_rec * 7;
+    NLR_CHECK_ARG(n_rec * 9 < (1ull << 31), "obj_frame_backward: n_obj * T = %zu records do not fit the 32-bit slot index", n_rec);
+    if (K == 0) {
+        NLR_HIP(hipMemsetAsync(g_tracks, 0, n_rec * 9 * sizeof(float), st));
+        return NLR_OK;
+    }
+    NLR_CHECK_ARG(tracks && timestamps && origins && directions && viewdirs && tdist && ray_idx && sample_idx && track_idx && g_pts && g_dirs,
+                  "obj_frame_backward: NULL tensor");
+    NLR_CHECK_ARG(T >= 2, "obj_frame_backward: get_pose blends two recorded poses, T = %u", T);
+    NLR_CHECK_ARG(N >= 1 && S >= 1, "obj_frame_backward: %u owned samples of an empty batch (N = %u, S = %u)", K, N, S);
+    NLR_CHECK_ARG(K < (1u << 31), "obj_frame_backward: K = %u owned samples do not fit the 32-bit list index", K);
+    const uint32_t nb = obj_frame_blocks(K);
+    ObjFrameBwd a;
+    a.tracks = tracks;
+    a.ts = timestamps;
+    a.origins = origins;
+    a.dirs = directions;
+    a.viewdirs = viewdirs;
+    a.tdist = tdist;
+    a.N = N;
+    a.S = S;
+    a.n_obj = n_obj;
+    a.T = T;
+    a.ray_idx = ray_idx;
+    a.sample_idx = sample_idx;
+    a.track_idx = track_idx;
+    a.K = K;
+    a.per_block = (uint32_t)((((size_t)K + nb - 1) / nb + 255) / 256 * 256);
+    a.g_pts = g_pts;
+    a.g_dirs = g_dirs;
+    if (n_slots <= NLR_OBJB_SLOTS) {
+        const size_t need = nlr_obj_frame_backward_workspace_bytes(K, n_obj, T);
+        if (!workspace || workspace_bytes < need)
+            NLR_FAIL(NLR_ERR_WORKSPACE, "obj_frame_backward: workspace %zu B < nlr_obj_frame_backward_workspace_bytes() = %zu B", workspace_bytes,
+                     need);
+        if (n_slots <= NLR_OBJB_SLOTS_SMALL)
+            hipLaunchKernelGGL(nlr_obj_frame_bwd_kernel<NLR_OBJB_SLOTS_SMALL>, dim3(nb), dim3(256), 0, st, a, (float *)workspace);
+        else
+            hipLaunchKernelGGL(nlr_obj_frame_bwd_kernel<NLR_OBJB_SLOTS>, dim3(nb), dim3(256), 0, st, a, (float *)workspace);
+        NLR_LAUNCH_CHECK("nlr_obj_frame_bwd_kernel");
+        hipLaunchKernelGGL(nlr_obj_frame_sum_kernel, dim3((unsigned)((n_rec * 9 + 255) / 256)), dim3(256), 0, st, (const float *)workspace, nb,
+                           (uint32_t)n_rec, g_tracks);
+        NLR_LAUNCH_CHECK("nlr_obj_frame_sum_kernel");
+    } else {
+        NLR_HIP(hipMemsetAsync(g_tracks, 0, n_rec * 9 * sizeof(float), st));
+        hipLaunchKernelGGL(nlr_obj_frame_bwd_kernel<0>, dim3(nb), dim3(256), 0, st, a, g_tracks);
+        NLR_LAUNCH_CHECK("nlr_obj_frame_bwd_kernel");
+    }
     return NLR_OK;
 }
 

@@ -69,6 +69,24 @@ def load_checkpoint(ckpt_dir_or_file, step=None, prefix: str = "checkpoint_") ->
     return sd, int(ckpt.get("step", 0))
 
 
+TRACKNET_PREFIX = "tracknet_ckpt_"  # train.py:575-582
+
+
+def refined_tracks_from_checkpoint(ckpt_dir_or_file, tracks, step=None) -> np.ndarray:
+    """The refined [n_obj, T, 9] tracks of a `tracknet_ckpt_<step>.ckpt` (train.py:575-582: the state dict of Track_opt, `opt_r`
+    [n_obj, T, 1] and `opt_t` [n_obj, T, 3]) applied to the recorded `tracks` as train.py:254-256 does: columns 0:3 + opt_t, column
+    3 + opt_r.  The recorded tracks come from the dataset, the reference does not store them in the checkpoint."""
+    sd, _ = load_checkpoint(ckpt_dir_or_file, step, prefix=TRACKNET_PREFIX)
+    sd = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in sd.items()}
+    out = np.array(tracks, np.float32, copy=True)
+    for k, cols in (("opt_t", 3), ("opt_r", 1)):
+        if k not in sd or sd[k].shape != out.shape[:2] + (cols,):
+            raise ValueError(f"tracknet checkpoint: {k} is {None if k not in sd else sd[k].shape}, the tracks need {out.shape[:2] + (cols,)}")
+    out[:, :, :3] += sd["opt_t"]
+    out[:, :, 3:4] += sd["opt_r"]
+    return out
+
+
 def split_state_dict(sd: Dict[str, np.ndarray]) -> Tuple[Dict[str, np.ndarray], List[str]]:
     """(parameters of the fused path, keys that belong to branches outside it)."""
     keep, ignored = {}, []

@@ -162,6 +162,8 @@ def build_parser() -> argparse.ArgumentParser:
                     "the dynamic-object branch (Config.instance_obj=True); needs --track-classes")
     ap.add_argument("--track-classes", default=None, help="comma-separated nuScenes category per track, e.g. vehicle.car,vehicle.truck")
     ap.add_argument("--synthetic-tracks", type=int, default=0, help="N seeded boxes placed on rays of the sweep (no dataset in this image)")
+    ap.add_argument("--tracknet-ckpt", default=None, help="directory or file of a tracknet_ckpt_<step>.ckpt (track refinement): renders with "
+                    "the refined tracks instead of the recorded ones; needs --tracks or --synthetic-tracks")
     ap.add_argument("--lidar-only", action="store_true", help="render without colour (one nlr_render_lidar call per sweep, no view MLP): "
                     "writes points, points_semantic and points_intensity, no points_rgb; not with --raydrop-unet")
     return ap
@@ -173,6 +175,8 @@ def parse_args(argv=None) -> argparse.Namespace:
     if a.lidar_only and a.raydrop_unet:
         ap.error("--lidar-only renders no colour, and the ray-drop UNet's feature stack (raydrop.unet_features) takes the rgb channels: "
                  "drop one of --lidar-only / --raydrop-unet")
+    if a.tracknet_ckpt and not (a.tracks or a.synthetic_tracks):
+        ap.error("--tracknet-ckpt refines box tracks: give --tracks (with --track-classes) or --synthetic-tracks")
     return a
 
 
@@ -191,6 +195,9 @@ def main(argv=None) -> int:
             probe = nlidar.synthetic_sweep(width=a.width, seed=a.seed, scale_factor=a.scale_factor)
             tracks = nobj.synthetic_tracks(probe, a.synthetic_tracks, 20, a.seed, size=(0.02, 0.01, 0.008), depth=(0.02, 0.2))
             classes = (["vehicle.car", "vehicle.truck", "vehicle.bus.rigid"] * a.synthetic_tracks)[: a.synthetic_tracks]
+    if a.tracknet_ckpt:
+        from .checkpoints import refined_tracks_from_checkpoint
+        tracks = refined_tracks_from_checkpoint(a.tracknet_ckpt, tracks)
     if a.ckpt and dynamic:
         from .checkpoints import dynamic_model_from_checkpoint
         base = nconfig.ModelConfig()

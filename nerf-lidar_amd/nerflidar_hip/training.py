@@ -681,6 +681,57 @@ class TrainableObjMLP(torch.nn.Module):
         return out
 
 
+def _box_frame(origins, dirs, viewdirs, td, box, ri, si, tr):
+    """Box coordinates and normalised box-frame view direction of the owned samples (ray ri, sample si, track tr), from the
+    per-(ray, track) constants `box` = cos, sin, t_w_o (3), scale (3): obj_utils.py:158-176."""
+    bp = box[ri, tr]
+    t_mid = 0.5 * (td[ri, si] + td[ri, si + 1])
+    pw = t_mid[:, None] * dirs[ri] + origins[ri]
+    cs, sn = bp[:, 0], bp[:, 1]
+    rx = cs * pw[:, 0] - sn * pw[:, 1]
+    p_all = bp[:, 5:8] * (torch.stack([rx, sn * rx + cs * pw[:, 1], pw[:, 2]], dim=-1) + bp[:, 2:5])
+    vd = viewdirs[ri]
+    vx = cs * vd[:, 0] - sn * vd[:, 1]
+    d_all = bp[:, 5:8] * torch.stack([vx, sn * vx + cs * vd[:, 1], vd[:, 2]], dim=-1)
+    d_all = d_all / torch.norm(d_all, dim=-1, keepdim=True)
+    return p_all, d_all
+
+
+class _ObjFrame(torch.autograd.Function):
+    """tracks [n_obj, T, 9] -> (box-frame points, box-frame view directions) of the owned samples.  forward = `_box_frame` on the
+    constants `nlr_track_box_params` made of the same tracks (the values of the path without gradient, bit for bit); backward =
+    `nlr_obj_frame_backward`, one reduction kernel instead of the gather / index_put chain autograd would walk.  Only the tracks
+    receive a gradient: ray origins and directions are data here (no pose refinement)."""
+
+    @staticmethod
+    def forward(ctx, tracks, ts, origins, dirs, viewdirs, td, box, ri, si, tr):
+        ctx.save_for_backward(tracks.detach().contiguous(), ts, origins, dirs, viewdirs, td, ri.int().contiguous(), si.int().contiguous(),
+                              tr.int().contiguous())
+        return _box_frame(origins, dirs, viewdirs, td, box, ri, si, tr)
+
+    @staticmethod
+    def backward(ctx, g_p, g_d):
+        tracks, ts, origins, dirs, viewdirs, td, ri, si, tr = ctx.saved_tensors
+        return (obj_frame_backward(tracks, ts, origins, dirs, viewdirs, td, ri, si, tr, g_p, g_d),) + (None,) * 9
+
+
+def obj_frame_backward(tracks, ts, origins, dirs, viewdirs, td, ri, si, tr, g_pts, g_dirs) -> torch.Tensor:
+    """`nlr_obj_frame_backward`: d/d tracks [n_obj, T, 9] of the box-frame points / directions of the K owned samples (int32 lists
+    ri, si, tr sorted by (ray, sample)) contracted with their cotangents g_pts, g_dirs [K, 3]."""
+    L = _lib.lib()
+    n, S, K = td.shape[0], td.shape[1] - 1, ri.shape[0]
+    n_obj, T = tracks.shape[0], tracks.shape[1]
+    g_pts, g_dirs = g_pts.contiguous().float(), g_dirs.contiguous().float()
+    out = torch.empty_like(tracks)
+    need = L.nlr_obj_frame_backward_workspace_bytes(K, n_obj, T)
+    ws = torch.empty(need, dtype=torch.uint8, device=tracks.device) if need else None
+    with torch.cuda.device(tracks.device):
+        _lib.check(L.nlr_obj_frame_backward(_lib.ptr(tracks), _lib.ptr(ts), _lib.ptr(origins), _lib.ptr(dirs), _lib.ptr(viewdirs), _lib.ptr(td),
+                                            n, S, n_obj, T, _lib.ptr(ri), _lib.ptr(si), _lib.ptr(tr), K, _lib.ptr(g_pts), _lib.ptr(g_dirs),
+                                            _lib.ptr(out), _lib.ptr(ws), need, _lib.current_stream()), "nlr_obj_frame_backward")
+    return out
+
+
 class TrainableModel(torch.nn.Module):
     """`Model` (ZI/models.py:31-576, no GLO) as a trainable module: submodules `prop_mlp_<i>` and `nerf_mlp` with the reference's
     parameter names, so a reference checkpoint loads with `load_reference` and the trained `state_dict()` goes straight into
@@ -754,10 +805,13 @@ class TrainableModel(torch.nn.Module):
         return latent_reg * torch.stack(z).sum()
 
     # -- dynamic objects (models.py:401-477) --------------------------------------------------------------------------------------
-    def _object_merge(self, o: Dict[str, torch.Tensor], rgbs: torch.Tensor, batch, tdist: torch.Tensor, box: torch.Tensor, last: bool):
+    def _object_merge(self, o: Dict[str, torch.Tensor], rgbs: torch.Tensor, batch, tdist: torch.Tensor, box: torch.Tensor, last: bool,
+                      refine=None):
         """Overwrite density / rgb / semantic of the samples inside the tracks' boxes with their ObjMLP's output.  Returns
         (density, rgbs, semantic, obj_mask).  Owner of a sample = the last track whose box holds the interval midpoint
-        (`nlr_box_winner`; the reference's track loop overwrites earlier tracks).  Sample positions carry no gradient."""
+        (`nlr_box_winner`; the reference's track loop overwrites earlier tracks).  Sample positions carry no gradient, unless
+        refine = (tracks, timestamps) hands over a track tensor that requires one (track refinement, last level only): then the
+        box-frame points and directions lead back to it through `_ObjFrame`."""
         n, S = tdist.shape[0], tdist.shape[1] - 1
         dev = tdist.device
         origins = batch["origins"].reshape(n, 3).contiguous().float()
@@ -775,16 +829,10 @@ class TrainableModel(torch.nn.Module):
             return density, rgbs, sem, mask
         ri, si = sel[:, 0], sel[:, 1]
         tr = winner[ri, si].long()
-        bp = box[ri, tr]                                   # cos, sin, t_w_o (3), scale (3): obj_utils.py:158-176
-        t_mid = 0.5 * (td[ri, si] + td[ri, si + 1])
-        pw = t_mid[:, None] * dirs[ri] + origins[ri]
-        cs, sn = bp[:, 0], bp[:, 1]
-        rx = cs * pw[:, 0] - sn * pw[:, 1]
-        p_all = bp[:, 5:8] * (torch.stack([rx, sn * rx + cs * pw[:, 1], pw[:, 2]], dim=-1) + bp[:, 2:5])
-        vd = viewdirs[ri]
-        vx = cs * vd[:, 0] - sn * vd[:, 1]
-        d_all = bp[:, 5:8] * torch.stack([vx, sn * vx + cs * vd[:, 1], vd[:, 2]], dim=-1)
-        d_all = d_all / torch.norm(d_all, dim=-1, keepdim=True)
+        if refine is not None:
+            p_all, d_all = _ObjFrame.apply(refine[0], refine[1], origins, dirs, viewdirs, td, box, ri, si, tr)
+        else:
+            p_all, d_all = _box_frame(origins, dirs, viewdirs, td, box, ri, si, tr)
         table = torch.stack([self.latent_vector_dict[f"obj_latent_{t}"] for t in range(len(self.class_ids))])
         lat_all = table[tr]
         rank = self._class_rank[tr]
@@ -834,6 +882,8 @@ class TrainableModel(torch.nn.Module):
             with torch.cuda.device(dev):
                 _lib.check(L.nlr_track_box_params(_lib.ptr(tracks), _lib.ptr(ts), n, tracks.shape[0], tracks.shape[1], _lib.ptr(box),
                                                   _lib.current_stream()), "nlr_track_box_params")
+            # track refinement (train.py:244-268): a track that requires a gradient gets one from the last level's object samples
+            refine = (tracks, ts) if tracks.requires_grad and torch.is_grad_enabled() else None
         for li, (S, level) in enumerate(zip(samples, self.levels())):
             last = li == len(samples) - 1
             use_dil = mc.dilation_bias > 0 or mc.dilation_multiplier > 0                      # models.py:322-346
@@ -851,7 +901,7 @@ class TrainableModel(torch.nn.Module):
             rgbs = o["rgb"] if last else torch.zeros(n, S, 3, device=dev)   # a PropMLP renders black (models.py:1119-1122)
             obj_mask = None
             if box is not None:
-                dens_m, rgbs, sem_m, obj_mask = self._object_merge(o, rgbs, batch, tdist, box, last)
+                dens_m, rgbs, sem_m, obj_mask = self._object_merge(o, rgbs, batch, tdist, box, last, refine if last else None)
                 o = dict(o, density=dens_m)
                 if sem_m is not None:
                     o["semantic"] = sem_m
@@ -907,10 +957,73 @@ def create_optimizer(model: torch.nn.Module, lr_init: float = 0.01, lr_final: fl
     return opt, (lambda step: learning_rate_decay(step, lr_init, lr_final, max_steps, lr_delay_steps, lr_delay_mult))
 
 
+class TrackNet(torch.nn.Module):
+    """`Track_opt` (ZI/posenet_v2.py:65-76) with the reference's parameter names, so its `tracknet_ckpt_*` files load: one yaw
+    offset `opt_r` [n_obj, T, 1] and one translation offset `opt_t` [n_obj, T, 3] per recorded pose of every track, zeros at the
+    start.  The recorded `tracks` [n_obj, T, 9] ride along as a buffer outside the state dict (the reference keeps them as a plain
+    attribute).  forward() = the refined track of train.py:251-256."""
+
+    def __init__(self, tracks):
+        super().__init__()
+        tracks = torch.as_tensor(np.asarray(tracks.detach().cpu() if isinstance(tracks, torch.Tensor) else tracks, np.float32))
+        if tracks.dim() != 3 or tracks.shape[-1] != 9:
+            raise ValueError(f"tracks must be [n_obj, T, 9] (center3, theta_z, wlh3, timestamp, id), got {tuple(tracks.shape)}")
+        self.register_buffer("tracks", tracks, persistent=False)
+        self.opt_r = torch.nn.Parameter(torch.zeros(tracks.shape[0], tracks.shape[1], 1))
+        self.opt_t = torch.nn.Parameter(torch.zeros(tracks.shape[0], tracks.shape[1], 3))
+
+    def forward(self) -> torch.Tensor:
+        track = self.tracks.clone()
+        track[:, :, :3] = self.tracks[:, :, :3] + self.opt_t
+        track[:, :, 3:4] = self.tracks[:, :, 3:4] + self.opt_r
+        return track
+
+
+TRACK_OPT_STEPS = 5000  # length of the refinement window (train.py:245,257,468: a literal there)
+
+
+def create_tracknet(tracks, track_start_opt: int = 5000, max_steps: int = 25000, tn_lr_init: float = 1e-4, tn_lr_final: float = 1e-5,
+                    lr_delay_steps: int = 5000, lr_delay_mult: float = 1e-8, adam_beta1: float = 0.9, adam_beta2: float = 0.99,
+                    adam_eps: float = 1e-15):
+    """train_utils.py:304-327: the TrackNet, its Adam (betas and eps of `create_optimizer`) and its learning-rate function, the
+    main schedule shifted to the start of the window: learning_rate_decay(step - start, max_steps = max_steps - start).
+    Returns (tracknet, optimizer, lr_fn)."""
+    net = TrackNet(tracks)
+    opt = torch.optim.Adam(net.parameters(), lr=tn_lr_init, betas=(adam_beta1, adam_beta2), eps=adam_eps)
+    return net, opt, (lambda step: learning_rate_decay(step - track_start_opt, tn_lr_init, tn_lr_final, max_steps - track_start_opt,
+                                                       lr_delay_steps, lr_delay_mult))
+
+
+def track_phase(step: Optional[int], track_start_opt: int = 5000) -> str:
+    """Where `step` lies relative to the refinement window of train.py:245-266: 'before' (the model renders its recorded tracks),
+    'refine' for start < step < start + 5000 (refined track with gradient), 'frozen' for step > start + 5000 (refined track under
+    no_grad).  (sic) step == start + 5000 matches neither comparison of the reference and renders the recorded tracks once more."""
+    if step is None:
+        raise ValueError("track refinement needs the step number (training_step(..., step=))")
+    if track_start_opt < step < track_start_opt + TRACK_OPT_STEPS:
+        return "refine"
+    return "frozen" if step > track_start_opt + TRACK_OPT_STEPS else "before"
+
+
+def current_track(tracknet: Optional[TrackNet], step: Optional[int], track_start_opt: int = 5000) -> Optional[torch.Tensor]:
+    """The `curr_track` of train.py:244-268 for this step: None before the window (and without a TrackNet), the refined track with
+    gradient inside it, the refined track without one after it."""
+    if tracknet is None:
+        return None
+    phase = track_phase(step, track_start_opt)
+    if phase == "refine":
+        return tracknet()
+    if phase == "frozen":
+        with torch.no_grad():
+            return tracknet()
+    return None
+
+
 def training_step(model: TrainableModel, optimizer: torch.optim.Optimizer, batch: Dict[str, torch.Tensor], train_frac: float = 1.0,
                   randomized: bool = True, hash_decay_mult: float = 0.1, tv_weight: float = 0.0, grad_max_norm: float = 0.0,
                   grad_max_val: float = 0.0, latent_reg: float = 0.001, as_tensors: bool = False, color_rays: Optional[int] = None,
-                  check_color_rays: bool = False, **loss_kw):
+                  check_color_rays: bool = False, tracknet: Optional[TrackNet] = None, tn_optimizer: Optional[torch.optim.Optimizer] = None,
+                  tn_lr_fn=None, step: Optional[int] = None, track_start_opt: int = 5000, **loss_kw):
     """One optimiser step as train.py:272-459 takes it: forward with random jitter, the loss dictionary (`losses.total_loss` +
     hash decay), backward through the HIP backward kernels, optional total-variation gradient on the tables (grid.py:176-198),
     gradient clipping incl. the unconditional nan_to_num_ (train_utils.clip_gradients), step.  Returns the loss terms as floats, or
@@ -919,12 +1032,25 @@ def training_step(model: TrainableModel, optimizer: torch.optim.Optimizer, batch
     color_rays: None, or the number n of leading rays with colour supervision (`TrainableModel.forward`): the caller promises
     `batch['mask_rgb']` = 0 on the rays [n, N), as train.py:316-320 sets it for the LiDAR rays at the end of a batch
     (`losses.nusc_masks(lidar_supervision=True)` and `scene.supervise(colourless=..)` build such masks).  check_color_rays (off by default: it reads the mask back, one host
-    synchronisation) verifies the promise and raises ValueError when it is broken."""
+    synchronisation) verifies the promise and raises ValueError when it is broken.
+    tracknet / tn_optimizer / tn_lr_fn (`create_tracknet`) with `step`: track refinement as train.py:244-268,468-471 runs it.  Before
+    the window (step <= track_start_opt) the model renders its recorded tracks; inside it the TrackNet's learning rate is set, its
+    gradients are zeroed, the model renders the refined track with gradient and, after the model's own step, the TrackNet's
+    gradients are clipped (the same `clip_gradients`) and its optimiser steps; after it the model renders the refined track under
+    no_grad.  Without a tracknet the step is the one described above."""
     from . import losses as nlosses
     if check_color_rays and color_rays is not None:
         nlosses.check_colourless(batch, color_rays)
+    refining = tracknet is not None and track_phase(step, track_start_opt) == "refine"
+    if refining:
+        if tn_optimizer is None or tn_lr_fn is None:
+            raise ValueError("track refinement inside the window needs tn_optimizer and tn_lr_fn (create_tracknet)")
+        for group in tn_optimizer.param_groups:
+            group["lr"] = tn_lr_fn(step)
+        tn_optimizer.zero_grad()
     optimizer.zero_grad(set_to_none=True)
-    renderings, history = model(batch, train_frac=train_frac, randomized=randomized, color_rays=color_rays)
+    track_kw = {} if tracknet is None else {"curr_track": current_track(tracknet, step, track_start_opt)}
+    renderings, history = model(batch, train_frac=train_frac, randomized=randomized, color_rays=color_rays, **track_kw)
     terms = nlosses.total_loss(renderings, history, batch, **loss_kw)
     if hash_decay_mult > 0:  # (Config.obj_nodecay, nuscenes_single.gin:24: the object grids stay out)
         terms["hash_decay"] = hash_decay_loss([lv.encoder for lv in model.levels()], hash_decay_mult)
@@ -937,6 +1063,9 @@ def training_step(model: TrainableModel, optimizer: torch.optim.Optimizer, batch
             lv.encoder.grad_total_variation(tv_weight)
     clip_gradients(model, grad_max_norm, grad_max_val)
     optimizer.step()
+    if refining:
+        clip_gradients(tracknet, grad_max_norm, grad_max_val)
+        tn_optimizer.step()
     out = {k: v.detach() for k, v in terms.items()}
     out["loss"] = loss.detach()
     return out if as_tensors else {k: float(v) for k, v in out.items()}
