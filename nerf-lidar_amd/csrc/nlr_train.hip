@@ -2,9 +2,9 @@
 //
 //   ZI/render.py:170-189,192-252  compute_alpha_weights + volumetric_rendering, differentiated by hand:
 //       w_k = alpha_k T_k,  alpha_k = 1 - exp(-dd_k),  T_k = exp(-sum_{j<k} dd_j),  dd_k = density_k * (t_{k+1} - t_k) * |d|
-//       dw_k/ddd_k = T_k - w_k,   dw_k/ddd_j = -w_k (j < k)
-//       => dL/ddd_j = G_j (T_j - w_j) - sum_{k>j} G_k w_k        with G = dL/dw
-//       G_k = g_w[k] + sum_c g_rgb[c] (rgb[c,k] - bg [1 - acc > 0]) + g_depth (tmid_k / accc - [acc > eps] sdep / accc^2) + g_acc
+//       dw_k/ddd_k = T_k - w_k = T_k exp(-dd_k),   dw_k/ddd_j = -w_k (j < k)
+//       => dL/ddd_j = G_j T_j exp(-dd_j) - sum_{k>j} G_k w_k        with G = dL/dw
+//       G_k = g_w[k] + sum_c g_rgb[c] (rgb[c,k] - bg [1 - acc >= 0]) + g_depth (tmid_k / accc - [acc >= eps] sdep / accc^2) + g_acc
 //     semantic and intensity are composited with DETACHED weights (render.py:240-252, sem_detach=True): their upstream
 //     gradients reach only the per-sample semantic / intensity values.
 //   ZI/models.py:203-223  hash_decay_loss = sum over encoders of mean_{level,channel}( mean_{rows of level} emb^2 )
@@ -33,12 +33,12 @@ __global__ void __launch_bounds__(256) nlr_composite_bwd_kernel(CompositeBwdPara
     const float *td = P.tdist + (size_t)ray * (S + 1);
     const float *dn = P.density + (size_t)ray * S;
 
-    float dd[NLR_CB_MAXPER], tm[NLR_CB_MAXPER], dl[NLR_CB_MAXPER], w[NLR_CB_MAXPER], T[NLR_CB_MAXPER];
+    float dd[NLR_CB_MAXPER], tm[NLR_CB_MAXPER], dl[NLR_CB_MAXPER], w[NLR_CB_MAXPER], T[NLR_CB_MAXPER], E[NLR_CB_MAXPER];
     float run = 0.0f;
 #pragma unroll
     for (int i = 0; i < NLR_CB_MAXPER; ++i) {
         const uint32_t k = k0 + i;
-        dd[i] = tm[i] = dl[i] = w[i] = T[i] = 0.0f;
+        dd[i] = tm[i] = dl[i] = w[i] = T[i] = E[i] = 0.0f;
         if (i < (int)per && k < S) {
             const float ta0 = td[k], ta1 = td[k + 1];
             dl[i] = (ta1 - ta0) * dnorm;
@@ -57,7 +57,8 @@ __global__ void __launch_bounds__(256) nlr_composite_bwd_kernel(CompositeBwdPara
     for (int i = 0; i < NLR_CB_MAXPER; ++i) {
         const uint32_t k = k0 + i;
         if (i < (int)per && k < S) {
-            const float alpha = 1.0f - expf(-dd[i]);
+            E[i] = expf(-dd[i]);
+            const float alpha = 1.0f - E[i];
             T[i] = expf(-cum);
             w[i] = alpha * T[i];
             cum += dd[i];
@@ -71,8 +72,9 @@ __global__ void __launch_bounds__(256) nlr_composite_bwd_kernel(CompositeBwdPara
     const float gr0 = P.g_rgb ? P.g_rgb[(size_t)ray * 3] : 0.0f, gr1 = P.g_rgb ? P.g_rgb[(size_t)ray * 3 + 1] : 0.0f,
                 gr2 = P.g_rgb ? P.g_rgb[(size_t)ray * 3 + 2] : 0.0f;
     const float gd = P.g_depth ? P.g_depth[ray] : 0.0f, ga = P.g_acc ? P.g_acc[ray] : 0.0f, gi = P.g_int ? P.g_int[ray] : 0.0f;
-    const float bgterm = (1.0f - acc > 0.0f) ? P.bg * ((gr0 + gr1) + gr2) : 0.0f;  // d(max(1-acc,0) bg)/dw_k = -bg
-    const float dterm = (acc > NLR_EPS) ? sdep / (accc * accc) : 0.0f;
+    // clamp_min passes its gradient where the input EQUALS the bound (torch: grad * (x >= min)); 1 - acc == 0 is every saturated ray
+    const float bgterm = (1.0f - acc >= 0.0f) ? P.bg * ((gr0 + gr1) + gr2) : 0.0f;  // d(max(1-acc,0) bg)/dw_k = -bg
+    const float dterm = (acc >= NLR_EPS) ? sdep / (accc * accc) : 0.0f;
 
     // G_k w_k per sample, per-lane totals, suffix sums over lanes
     float G[NLR_CB_MAXPER], tot = 0.0f;
@@ -98,15 +100,18 @@ __global__ void __launch_bounds__(256) nlr_composite_bwd_kernel(CompositeBwdPara
                 for (uint32_t c = 0; c < P.K; ++c) P.d_sem[(size_t)c * Mt + mi] = w[i] * (P.g_sem ? P.g_sem[(size_t)ray * P.K + c] : 0.0f);
         }
     }
-    const float tincl = nlr_wave_incl_scan_add(tot, lane);
-    const float total = __shfl(tincl, 63, 64);
-    float suffix = total - tincl;  // sum of G w over the lanes to the right
+    // sum of G w over the lanes to the right: a scan in reverse lane order, the small terms of the tail first.  (total - prefix leaves
+    // ulp(total) on every lane whose own suffix is far below the total, i.e. on all the samples behind a surface.)
+    const float rincl = nlr_wave_incl_scan_add(__shfl(tot, 63 - lane, 64), lane);  // at lane i: lanes 63 - i .. 63
+    float suffix = __shfl(rincl, 62 - lane, 64);
+    if (lane == 63) suffix = 0.0f;
 #pragma unroll
     for (int i = NLR_CB_MAXPER - 1; i >= 0; --i) {
         const uint32_t k = k0 + i;
         if (i < (int)per && k < S) {
-            // T - w = T exp(-dd): 0 for the opaque last interval (its dd does not come from the density)
-            const float own = (P.opaque && k == S - 1) ? 0.0f : G[i] * (T[i] - w[i]);
+            // dw/ddd = T - w = T exp(-dd), taken as the product: the difference cancels to 0 once exp(-dd) < 2^-24, where the
+            // product still has its full precision.  0 for the opaque last interval (its dd does not come from the density)
+            const float own = (P.opaque && k == S - 1) ? 0.0f : G[i] * (T[i] * E[i]);
             const float ddd = own - suffix;
             P.d_density[(size_t)ray * S + k] = (P.opaque && k == S - 1) ? 0.0f : ddd * dl[i];
             suffix += G[i] * w[i];

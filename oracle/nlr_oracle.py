@@ -273,6 +273,13 @@ def sample_u(num_samples: int, rand_u: Optional[torch.Tensor] = None):
     return torch.linspace(0, 1 - u_max, num_samples) + rand_u * max_jitter
 
 
+def resample_logits(sdist, weights, anneal=1., resample_padding=0.):
+    """ZI/models.py:350-355: weights ** anneal as logits, with the Dirichlet padding on the histogram (`Model.resample_padding`)
+    added to the weights; a zero-width interval gets no mass."""
+    return torch.where(sdist[..., 1:] > sdist[..., :-1], anneal * torch.log(weights + resample_padding),
+                       torch.full_like(sdist[..., :-1], -torch.inf))
+
+
 def sample_intervals(t, w_logits, num_samples, domain, rand_u=None):
     """ZI/stepfun.py:251-294 -> sample :175-218 -> invert_cdf :154-161."""
     u = sample_u(num_samples, rand_u)
@@ -476,8 +483,7 @@ def model_forward(sd_np, mc, batch: Dict[str, torch.Tensor], train_frac=1.0, com
             anneal = (mc.anneal_slope * train_frac) / ((mc.anneal_slope - 1) * train_frac + 1)
         else:
             anneal = 1.
-        logits = torch.where(sdist[..., 1:] > sdist[..., :-1], anneal * torch.log(weights + mc.resample_padding),
-                             torch.full_like(sdist[..., :-1], -torch.inf))
+        logits = resample_logits(sdist, weights, anneal, mc.resample_padding)
         sdist = sample_intervals(sdist, logits, num_samples, (init_s_near, init_s_far),
                                  None if rand_jitter is None else rand_jitter[i_level])
         tdist = s_to_t(sdist)

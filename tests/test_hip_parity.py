@@ -289,7 +289,7 @@ def test_gridencoder_total_variation_method():
 # ------------------------------------------------------------------------------------------------
 # a-2 / a-3 / a-4 resampling
 # ------------------------------------------------------------------------------------------------
-def _resample(prev_t, prev_w, dilation, S, near, far, jitter=None):
+def _resample(prev_t, prev_w, dilation, S, near, far, jitter=None, anneal=1.0, resample_padding=0.0):
     n = prev_t.shape[0]
     npv = 0 if prev_w is None else prev_w.shape[1]
     sd = torch.empty(n, S + 1, device=DEV)
@@ -298,7 +298,7 @@ def _resample(prev_t, prev_w, dilation, S, near, far, jitter=None):
     pw = cu(prev_w) if prev_w is not None else None
     nr, fr = cu(near), cu(far)
     jt = cu(jitter) if jitter is not None else None
-    rc = _lib.lib().nlr_resample_level(_lib.ptr(pt), _lib.ptr(pw), npv, float(dilation), 1.0, 0.0, S, _lib.ptr(jt), _lib.ptr(nr),
+    rc = _lib.lib().nlr_resample_level(_lib.ptr(pt), _lib.ptr(pw), npv, float(dilation), float(anneal), float(resample_padding), S, _lib.ptr(jt), _lib.ptr(nr),
                                        _lib.ptr(fr), -1.5, n, _lib.ptr(sd), _lib.ptr(td), None)
     _lib.check(rc)
     torch.cuda.synchronize()
@@ -325,7 +325,7 @@ def test_resample_with_dilation(name, S):
     assert (np.diff(sd, axis=-1) >= 0).all() and sd.min() >= 0 and sd.max() <= 1
 
 
-@pytest.mark.parametrize("n_prev,S", [(1, 16), (2, 8), (37, 48), (64, 64), (100, 32), (190, 64), (256, 128)])
+@pytest.mark.parametrize("n_prev,S", [(1, 16), (2, 8), (37, 48), (64, 64), (100, 32), (190, 64), (256, 128), (512, 64), (512, 1024), (300, 2), (3, 1024)])
 def test_resample_dilation_ties_and_odd_sizes(n_prev, S):
     """The dilation stage ranks the merged fenceposts by binary search and takes window maxima from a range-max table:
     exercise ties (repeated fenceposts = zero-width bins, fenceposts exactly `dilation` apart, values pinned at 0 and 1),
@@ -354,6 +354,42 @@ def test_resample_dilation_ties_and_odd_sizes(n_prev, S):
     assert np.abs(sd[ok] - ref_s.numpy()[ok]).mean() <= 2e-6
     np.testing.assert_allclose(sd[ok], ref_s.numpy()[ok], atol=2e-4, rtol=0)
     assert (np.diff(sd[ok], axis=-1) >= 0).all()
+
+
+@pytest.mark.parametrize("resample_padding", [0.0, 0.01])
+@pytest.mark.parametrize("anneal", [0.25, 0.7])
+@pytest.mark.parametrize("n_prev,S", [(64, 64), (100, 48)])
+@pytest.mark.parametrize("dilated", [True, False])
+def test_resample_anneal_and_padding(dilated, n_prev, S, anneal, resample_padding):
+    """The kernel's `anneal` and `resample_padding` (every other test passes 1 and 0): logits = anneal * log(w + padding), -inf for
+    zero-width bins (ZI/models.py:343-355), on the dilated and on the plain step function, against the pinned oracle chain at the
+    tolerances of the dilation tests above.  The padding gives bins without weight a share of the samples; the sample positions
+    (ZI/stepfun.py:203-206) do not depend on it."""
+    rng = np.random.default_rng(200 + n_prev)
+    rows, d = 48, 0.03125
+    t = np.sort(rng.random((rows, n_prev + 1)).astype(np.float32), axis=-1)
+    t[0, 0], t[0, -1] = 0.0, 1.0
+    t[1, 5] = t[1, 4]                                   # a zero-width bin
+    w = rng.random((rows, n_prev)).astype(np.float32) ** 4 + 1e-4
+    w[2, : n_prev // 2] = 0.0                           # half the ray without weight: reached only through the padding
+    w = w / w.sum(-1, keepdims=True)
+    near, far = np.full((rows,), 0.008, np.float32), np.full((rows,), 2.0, np.float32)
+    sd, td = _resample(t, w, d if dilated else 0.0, S, near, far, anneal=anneal, resample_padding=resample_padding)
+    tt, ww = T(t), T(w)
+    if dilated:
+        tt, ww = orc.max_dilate_weights(tt, ww, d, (0., 1.), renormalize=True)
+        tt, ww = tt[..., 1:-1], ww[..., 1:-1]
+    ref_s = orc.sample_intervals(tt, orc.resample_logits(tt, ww, anneal, resample_padding), S, (0., 1.))
+    ok = torch.isfinite(ref_s).all(-1).numpy()
+    assert ok.sum() >= rows - 2
+    assert np.abs(sd[ok] - ref_s.numpy()[ok]).mean() <= 2e-6
+    np.testing.assert_allclose(sd[ok], ref_s.numpy()[ok], atol=2e-4, rtol=0)
+    _, s_to_t = orc.construct_ray_warps(T(near)[:, None], T(far)[:, None], -1.5)
+    np.testing.assert_allclose(td[ok], s_to_t(ref_s).numpy()[ok], atol=1e-4, rtol=1e-4)
+    assert (np.diff(sd[ok], axis=-1) >= 0).all() and sd[ok].min() >= 0 and sd[ok].max() <= 1
+    # the two parameters are really used: the same call with anneal = 1, padding = 0 gives other samples
+    sd1, _ = _resample(t, w, d if dilated else 0.0, S, near, far)
+    assert np.abs(sd1 - sd)[ok].max() > 1e-3
 
 
 @pytest.mark.parametrize("name", _names("fn_sample_intervals"))
