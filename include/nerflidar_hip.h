@@ -479,6 +479,7 @@ int nlr_box_winner(const float *tdist, const float *origins, const float *direct
  *      class's network on them -> results written over density [N,S], rgb [3,N,S] and semantic [K,N,S] in place (rgb and
  *      semantic may be NULL: proposal levels replace the density only, models.py:466-477).  workspace: dev, at least
  *      nlr_objects_workspace_bytes(o, N, S) bytes.  winner_out [N,S] int32 optional.
+ *      box_params must be 16-byte aligned: the kernels read each 32-byte record as two 16-byte loads.
  *
  * nlr_render_rays_dynamic: nlr_render_rays with the object merge between the MLP and the compositing of every level.
  *      `winner` (optional) receives one [N, S_l] int32 owner map per level (ray_history's obj_mask = winner >= 0).

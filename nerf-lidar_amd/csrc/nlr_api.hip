@@ -508,7 +508,6 @@ extern "C" int nlr_profile_end(NlrModel *m, void *stream, float *total_ms, uint3
 }
 
 // ---- workspace ------------------------------------------------------------------------------------
-static size_t al(size_t b) { return (b + 255) & ~(size_t)255; }
 
 struct Carve {
     char *base;

@@ -6,6 +6,9 @@
 #define NLR_OBJ_MAX_DEPTH 4
 #define NLR_OBJ_MAX_DEG 4
 
+// workspace carving of both files: every slab starts on a 256-byte boundary
+static inline size_t al(size_t b) { return (b + 255) & ~(size_t)255; }
+
 struct NlrObjects;
 int nlr_objects_apply_impl(const NlrObjects *o, const NlrRays *rays, const float *tdist, const float *box_params, uint32_t N, uint32_t S,
                            uint32_t n_obj, float *density, float *rgb, float *semantic, uint32_t K, int32_t *winner_out, void *workspace,

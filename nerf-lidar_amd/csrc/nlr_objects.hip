@@ -1,60 +1,69 @@
-// Dynamic-object branch (scope row f-1): which box, if any, owns each sample.
+// Dynamic-object branch (scope row f-1, header section 7b): pose blend -> owner of every sample + per-class compaction ->
+// object networks, and the adjoint of the box-frame map for track refinement.  All of it on the device.
 //
 //   ZI/models.py:401-477 loops over tracks and lets every later track overwrite the samples of earlier ones, so a sample
 //   belongs to the LAST track whose box contains its interval midpoint.  ZI/obj_utils.py:203-216 (box_pts) decides "inside"
 //   by |p_o| < 1 on all three axes of p_o = scale * (R(p_w) + t_w_o), R = rotate_yaw_z with the reference's quirk
 //   (y' from the already rotated x', obj_utils.py:106-107).
-// The per-(ray, track) constants (cos, sin, t_w_o, scale) are computed by the caller with the reference's own torch
-// expressions; the kernel only repeats the multiply / add chain in the same order (-ffp-contract=off), so a sample lands on
-// the same side of a box face as in the reference.  One thread per sample, the track loop in registers: the reference
-// materialises [N, S, N_obj, 3] tensors for this.
+// The order of the float operations in that map decides on which side of a box face a sample lands, so the map is written
+// ONCE, in the nlr_box_* / nlr_track_* device functions below, and every kernel of this file goes through them: the
+// per-(ray, track) constants (nlr_track_box_kernel), the owner map (nlr_box_owner_kernel, one thread per sample with the
+// track loop in registers: the reference materialises [N, S, N_obj, 3] tensors for this), the networks' inputs
+// (nlr_objmlp_kernel) and the forward half of the adjoint (nlr_obj_frame_bwd_kernel).  Built with -ffp-contract=off: the
+// multiply / add chains below are the reference's torch expressions, operation by operation.
 #include "nlr_kernels.h"
-
-__global__ void __launch_bounds__(256) nlr_box_winner_kernel(const float *__restrict__ tdist, const float *__restrict__ origins,
-                                                            const float *__restrict__ dirs, const float *__restrict__ box,
-                                                            uint32_t N, uint32_t S, uint32_t n_obj, int32_t *__restrict__ winner) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;  // (N * S < 2^32, checked by the host: no 64-bit division here)
-    if (i >= N * S) return;
-    const uint32_t ray = i / S, k = i - ray * S;
-    const float t0 = tdist[(size_t)ray * (S + 1) + k], t1 = tdist[(size_t)ray * (S + 1) + k + 1];
-    const float tm = 0.5f * (t0 + t1);
-    float p[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) p[c] = tm * dirs[(size_t)ray * 3 + c] + origins[(size_t)ray * 3 + c];
-    int32_t w = -1;
-    const float *b = box + (size_t)ray * n_obj * 8;
-    for (uint32_t o = 0; o < n_obj; ++o, b += 8) {
-        const float cs = b[0], sn = b[1];
-        const float rx = cs * p[0] - sn * p[1];
-        const float ry = sn * rx + cs * p[1];  // (sic) the rotated x
-        const float x = b[5] * (rx + b[2]), y = b[6] * (ry + b[3]), z = b[7] * (p[2] + b[4]);
-        if (fabsf(x) < 1.0f && fabsf(y) < 1.0f && fabsf(z) < 1.0f) w = (int32_t)o;
-    }
-    winner[i] = w;
-}
-
-extern "C" int nlr_box_winner(const float *tdist, const float *origins, const float *directions, const float *box_params, uint32_t N,
-                              uint32_t S, uint32_t n_obj, int32_t *winner, void *stream) {
-    if (N == 0 || S == 0) return NLR_OK;
-    NLR_CHECK_ARG(tdist && origins && directions && winner && (box_params || n_obj == 0), "box_winner: NULL tensor");
-    const size_t M = (size_t)N * S;
-    NLR_CHECK_ARG(M < (1ull << 32), "box_winner: N * S = %zu does not fit the 32-bit sample index", M);
-    hipLaunchKernelGGL(nlr_box_winner_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, (hipStream_t)stream, tdist, origins, directions,
-                       box_params, N, S, n_obj, winner);
-    NLR_LAUNCH_CHECK("nlr_box_winner_kernel");
-    return NLR_OK;
-}
-
-// =============================================================================================================
-// The whole branch on the device (header section 7b): pose blend -> owner + per-class compaction -> object networks
-// =============================================================================================================
 #include "nlr_grid_level.h"
 #include "nlr_objects.h"
 
 #include <memory>
 #include <vector>
 
-// ---- get_pose + world2object constants (obj_utils.py:431-475, :5-28,:158-170), one thread per (ray, track) ----------
+// ---- the box-frame map ---------------------------------------------------------------------------------------------------
+// A box record is the 8 floats nlr_track_box_kernel writes per (ray, track), passed by value as two f32x4:
+//   b0 = (cos, sin, t_w_o.x, t_w_o.y), b1 = (t_w_o.z, scale.x, scale.y, scale.z).
+
+// world position of the midpoint of interval k of `ray`
+__device__ __forceinline__ void nlr_interval_midpoint(const float *__restrict__ tdist, const float *__restrict__ origins,
+                                                      const float *__restrict__ dirs, uint32_t S, uint32_t ray, uint32_t k, float (&p)[3]) {
+    const float t0 = tdist[(size_t)ray * (S + 1) + k], t1 = tdist[(size_t)ray * (S + 1) + k + 1];
+    const float tm = 0.5f * (t0 + t1);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) p[c] = tm * dirs[(size_t)ray * 3 + c] + origins[(size_t)ray * 3 + c];
+}
+
+// rotate_yaw_z on (x, y) with the reference's quirk: (sic) y' from the already rotated x' (obj_utils.py:106-107)
+__device__ __forceinline__ void nlr_rotate_yaw(float cs, float sn, float x, float y, float &rx, float &ry) {
+    rx = cs * x - sn * y;
+    ry = sn * rx + cs * y;
+}
+
+// world point -> box coordinates (world2object, obj_utils.py:158-170)
+__device__ __forceinline__ void nlr_box_coords(f32x4 b0, f32x4 b1, const float (&p)[3], float (&x)[3]) {
+    float rx, ry;
+    nlr_rotate_yaw(b0[0], b0[1], p[0], p[1], rx, ry);
+    x[0] = b1[1] * (rx + b0[2]);
+    x[1] = b1[2] * (ry + b0[3]);
+    x[2] = b1[3] * (p[2] + b1[0]);
+}
+
+// view direction -> normalised box-frame direction (obj_utils.py:171-176)
+__device__ __forceinline__ void nlr_box_dir(f32x4 b0, f32x4 b1, const float (&v)[3], float (&d)[3]) {
+    float vx, vy;
+    nlr_rotate_yaw(b0[0], b0[1], v[0], v[1], vx, vy);
+    d[0] = b1[1] * vx;
+    d[1] = b1[2] * vy;
+    d[2] = b1[3] * v[2];
+    const float nrm = sqrtf((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) d[c] = d[c] / nrm;
+}
+
+// box_pts' intersection map (obj_utils.py:203-216): strictly inside on all three axes; branch-free
+__device__ __forceinline__ int nlr_box_inside(const float (&x)[3]) {
+    return (int)(fabsf(x[0]) < 1.0f) & (int)(fabsf(x[1]) < 1.0f) & (int)(fabsf(x[2]) < 1.0f);
+}
+
+// ---- get_pose + world2object constants (obj_utils.py:431-475, :5-28,:158-170) ---------------------------------------------
 // The two records of one track closest in time to `time` (torch.sort(time_diff)[..., :2]; on equal distances the earlier record
 // first) and the weight of the first.  nlr_track_box_kernel and its adjoint nlr_obj_frame_bwd_kernel both choose through this
 // function, so a tie between records cannot fall differently in the two.
@@ -80,31 +89,41 @@ __device__ __forceinline__ void nlr_track_records(const float *__restrict__ tr, 
     w1 = fminf(fmaxf(w1, 0.0f), 1.0f);
 }
 
+// One track at one time: the two records and the weight of the first (nlr_track_records), the blended pose (center3, theta,
+// wlh3) and the box record b0 / b1 made of it.  The forward and the forward half of the adjoint.
+struct TrackBox {
+    uint32_t i1, i2;
+    float w1, pose[7];
+    f32x4 b0, b1;
+};
+__device__ __forceinline__ TrackBox nlr_track_box(const float *__restrict__ tr, uint32_t T, float time) {
+    TrackBox t;
+    nlr_track_records(tr, T, time, t.i1, t.i2, t.w1);
+#pragma unroll
+    for (int c = 0; c < 7; ++c) t.pose[c] = t.w1 * tr[t.i1 * 9 + c] + (1.0f - t.w1) * tr[t.i2 * 9 + c];
+    const float cs = cosf(t.pose[3]), sn = sinf(t.pose[3]);
+    float tx, ty;
+    nlr_rotate_yaw(cs, sn, -t.pose[0], -t.pose[1], tx, ty);  // t_w_o = rotate_yaw_z(-center, theta)
+    t.b0 = f32x4{cs, sn, tx, ty};
+    t.b1[0] = -t.pose[2];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) t.b1[1 + c] = 1.0f / (t.pose[4 + c] / 2.0f + 1e-9f);
+    return t;
+}
+
+// one thread per (ray, track)
 __global__ void __launch_bounds__(256) nlr_track_box_kernel(const float *__restrict__ tracks, const float *__restrict__ ts, uint32_t N,
                                                            uint32_t n_obj, uint32_t T, float *__restrict__ box) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (size_t)N * n_obj) return;
     const uint32_t ray = (uint32_t)(i / n_obj), o = (uint32_t)(i - (size_t)ray * n_obj);
-    const float *tr = tracks + (size_t)o * T * 9;
-    uint32_t i1, i2;
-    float w1;
-    nlr_track_records(tr, T, ts[ray], i1, i2, w1);
-    float pose[7];
-#pragma unroll
-    for (int c = 0; c < 7; ++c) pose[c] = w1 * tr[i1 * 9 + c] + (1.0f - w1) * tr[i2 * 9 + c];
-    const float cs = cosf(pose[3]), sn = sinf(pose[3]);
-    // t_w_o = rotate_yaw_z(-center, theta) with the reference's quirk (y' from the rotated x', obj_utils.py:106-107)
-    const float nx = -pose[0], ny = -pose[1];
-    const float px = cs * nx - sn * ny;
-    const float py = sn * px + cs * ny;
+    const TrackBox t = nlr_track_box(tracks + (size_t)o * T * 9, T, ts[ray]);
     float *b = box + i * 8;
-    b[0] = cs;
-    b[1] = sn;
-    b[2] = px;
-    b[3] = py;
-    b[4] = -pose[2];
 #pragma unroll
-    for (int c = 0; c < 3; ++c) b[5 + c] = 1.0f / (pose[4 + c] / 2.0f + 1e-9f);
+    for (int c = 0; c < 4; ++c) {
+        b[c] = t.b0[c];
+        b[4 + c] = t.b1[c];
+    }
 }
 
 extern "C" int nlr_track_box_params(const float *tracks, const float *timestamps, uint32_t N, uint32_t n_obj, uint32_t T,
@@ -169,28 +188,22 @@ __global__ void __launch_bounds__(256) nlr_obj_frame_bwd_kernel(ObjFrameBwd a, f
         uint32_t i1 = 0, i2 = 0;
         float w1 = 0.0f;
         if (valid) {
-            const float *tr = a.tracks + (size_t)o * a.T * 9;
-            nlr_track_records(tr, a.T, a.ts[ray], i1, i2, w1);
-            float pose[7];
-#pragma unroll
-            for (int c = 0; c < 7; ++c) pose[c] = w1 * tr[i1 * 9 + c] + (1.0f - w1) * tr[i2 * 9 + c];
-            const float cs = cosf(pose[3]), sn = sinf(pose[3]);
-            float sc[3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) sc[c] = 1.0f / (pose[4 + c] / 2.0f + 1e-9f);
-            const float t0 = a.tdist[(size_t)ray * (a.S + 1) + smp], t1 = a.tdist[(size_t)ray * (a.S + 1) + smp + 1];
-            const float tm = 0.5f * (t0 + t1);
-            float q[3], vd[3], gp[3], gd[3];
+            float pw[3], q[3], vd[3], gp[3], gd[3];
+            const TrackBox t = nlr_track_box(a.tracks + (size_t)o * a.T * 9, a.T, a.ts[ray]);
+            i1 = t.i1, i2 = t.i2, w1 = t.w1;
+            const float cs = t.b0[0], sn = t.b0[1], sc[3] = {t.b1[1], t.b1[2], t.b1[3]};
+            nlr_interval_midpoint(a.tdist, a.origins, a.dirs, a.S, ray, smp, pw);
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
-                q[c] = (tm * a.dirs[(size_t)ray * 3 + c] + a.origins[(size_t)ray * 3 + c]) - pose[c];
+                q[c] = pw[c] - t.pose[c];
                 vd[c] = a.viewdirs[(size_t)ray * 3 + c];
                 gp[c] = a.g_pts[(size_t)k * 3 + c];
                 gd[c] = a.g_dirs[(size_t)k * 3 + c];
             }
             float g_cs = 0.0f, g_sn = 0.0f, g_sc[3];
             // p = scale * u, u = (cs q0 - sn q1, sn ux + cs q1, q2)
-            const float ux = cs * q[0] - sn * q[1], uy = sn * ux + cs * q[1];
+            float ux, uy;
+            nlr_rotate_yaw(cs, sn, q[0], q[1], ux, uy);
             g_sc[0] = gp[0] * ux;
             g_sc[1] = gp[1] * uy;
             g_sc[2] = gp[2] * q[2];
@@ -201,7 +214,8 @@ __global__ void __launch_bounds__(256) nlr_obj_frame_bwd_kernel(ObjFrameBwd a, f
             g[1] = -(cs * guy - sn * gux);
             g[2] = -(gp[2] * sc[2]);
             // dir = e / |e|, e = scale * v, v = (cs d0 - sn d1, sn vx + cs d1, d2)
-            const float vx = cs * vd[0] - sn * vd[1], vy = sn * vx + cs * vd[1];
+            float vx, vy;
+            nlr_rotate_yaw(cs, sn, vd[0], vd[1], vx, vy);
             const float e[3] = {sc[0] * vx, sc[1] * vy, sc[2] * vd[2]};
             const float inv = 1.0f / sqrtf((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
             const float n[3] = {e[0] * inv, e[1] * inv, e[2] * inv};
@@ -340,6 +354,7 @@ extern "C" int nlr_obj_frame_backward(const float *tracks, const float *timestam
 }
 
 // ---- owner of every sample + per-class lists of the owned samples ---------------------------------------------------------
+// nlr_box_owner_kernel is the one owner map of the library: nlr_box_winner launches it with n_classes = 0 for the map alone.
 // Three small kernels and no atomics (device-scope atomics on one counter serialise at the memory side across the 8 XCDs:
 // 10 k of them cost more than the rest of the branch): (1) owner map + the number of owned samples of every class in every
 // wave, (2) exclusive scan of those counts per class, (3) scatter.  The lists come out in sample order.
@@ -354,11 +369,8 @@ __global__ void __launch_bounds__(256) nlr_box_owner_kernel(const float *__restr
     int32_t w = -1;
     if (in) {
         const uint32_t ray = i / S, k = i - ray * S;
-        const float t0 = tdist[(size_t)ray * (S + 1) + k], t1 = tdist[(size_t)ray * (S + 1) + k + 1];
-        const float tm = 0.5f * (t0 + t1);
         float p[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) p[c] = tm * dirs[(size_t)ray * 3 + c] + origins[(size_t)ray * 3 + c];
+        nlr_interval_midpoint(tdist, origins, dirs, S, ray, k, p);
         const f32x4 *b = reinterpret_cast<const f32x4 *>(box + (size_t)ray * n_obj * 8);  // (32-byte records of a float array)
         // four boxes per trip: their eight 16-byte loads are issued together, and the inside test is branch-free
         for (uint32_t o0 = 0; o0 < n_obj; o0 += 4) {
@@ -371,22 +383,33 @@ __global__ void __launch_bounds__(256) nlr_box_owner_kernel(const float *__restr
             }
 #pragma unroll
             for (uint32_t u = 0; u < 4; ++u) {
-                const float cs = b0[u][0], sn = b0[u][1];
-                const float rx = cs * p[0] - sn * p[1];
-                const float ry = sn * rx + cs * p[1];  // (sic) the rotated x
-                const float x = b1[u][1] * (rx + b0[u][2]), y = b1[u][2] * (ry + b0[u][3]), z = b1[u][3] * (p[2] + b1[u][0]);
-                const int inside = (int)(fabsf(x) < 1.0f) & (int)(fabsf(y) < 1.0f) & (int)(fabsf(z) < 1.0f) & (int)(o0 + u < n_obj);
+                float x[3];
+                nlr_box_coords(b0[u], b1[u], p, x);
+                const int inside = nlr_box_inside(x) & (int)(o0 + u < n_obj);
                 w = inside ? (int32_t)(o0 + u) : w;
             }
         }
         winner[i] = w;
     }
+    if (n_classes == 0) return;  // (nlr_box_winner: the owner map alone, no track_class and no count buffer)
     const int32_t cls = w >= 0 ? track_class[w] : -1;
     const uint32_t lane = threadIdx.x & 63, gw = i >> 6;
     for (uint32_t c = 0; c < n_classes; ++c) {
         const uint64_t mask = __ballot(cls == (int32_t)c);
         if (lane == 0) wave_counts[(size_t)c * gridDim.x * 4 + gw] = (uint32_t)__popcll(mask);
     }
+}
+
+extern "C" int nlr_box_winner(const float *tdist, const float *origins, const float *directions, const float *box_params, uint32_t N,
+                              uint32_t S, uint32_t n_obj, int32_t *winner, void *stream) {
+    if (N == 0 || S == 0) return NLR_OK;
+    NLR_CHECK_ARG(tdist && origins && directions && winner && (box_params || n_obj == 0), "box_winner: NULL tensor");
+    const size_t M = (size_t)N * S;
+    NLR_CHECK_ARG(M < (1ull << 32), "box_winner: N * S = %zu does not fit the 32-bit sample index", M);
+    hipLaunchKernelGGL(nlr_box_owner_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, (hipStream_t)stream, tdist, origins, directions,
+                       box_params, N, S, n_obj, (const int32_t *)nullptr, 0u, winner, (uint32_t *)nullptr);
+    NLR_LAUNCH_CHECK("nlr_box_owner_kernel");
+    return NLR_OK;
 }
 
 // exclusive scan of one class's per-wave counts (blockIdx.x = class), in place; counts[c] = total
@@ -527,40 +550,28 @@ __global__ void __launch_bounds__(64 * NLR_OBJ_WAVES) nlr_objmlp_kernel(const Ob
         const uint32_t m = list[valid ? base + lane : count - 1];
         const uint32_t ray = m / a.S, k = m - ray * a.S;
         // ---- box coordinates of the interval midpoint, obj_utils.py:158-176,203-216
-        const float t0 = a.tdist[(size_t)ray * (a.S + 1) + k], t1 = a.tdist[(size_t)ray * (a.S + 1) + k + 1];
-        const float tm = 0.5f * (t0 + t1);
-        float pw[3], vd[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            pw[c] = tm * a.dirs[(size_t)ray * 3 + c] + a.origins[(size_t)ray * 3 + c];
-            vd[c] = want_rgb ? a.viewdirs[(size_t)ray * 3 + c] : 0.0f;
-        }
+        float pw[3], po[3];
+        nlr_interval_midpoint(a.tdist, a.origins, a.dirs, a.S, ray, k, pw);
         const uint32_t tr = (uint32_t)a.winner[m];
-        const float *b = a.box + ((size_t)ray * a.n_obj + tr) * 8;
-        const float cs = b[0], sn = b[1];
-        const float rx = cs * pw[0] - sn * pw[1];
-        const float ry = sn * rx + cs * pw[1];
+        const f32x4 *b = reinterpret_cast<const f32x4 *>(a.box + ((size_t)ray * a.n_obj + tr) * 8);  // (32-byte records of a float array)
+        const f32x4 b0 = b[0], b1 = b[1];
+        nlr_box_coords(b0, b1, pw, po);
         Gauss g;  // GridEncoder(bound = 1): (x + 1) / 2 (grid.py:162)
-        g.x0 = ((b[5] * (rx + b[2])) + 1.0f) / 2.0f;
-        g.x1 = ((b[6] * (ry + b[3])) + 1.0f) / 2.0f;
-        g.x2 = ((b[7] * (pw[2] + b[4])) + 1.0f) / 2.0f;
+        g.x0 = (po[0] + 1.0f) / 2.0f;
+        g.x1 = (po[1] + 1.0f) / 2.0f;
+        g.x2 = (po[2] + 1.0f) / 2.0f;
         g.zs = 0.0f;
         float de[3], ds0[3 * NLR_OBJ_MAX_DEG], ds1[3 * NLR_OBJ_MAX_DEG];  // [x | sin(2^j x) | sin(2^j x + pi/2)], j-major
         if (want_rgb) {  // view direction in the box frame, normalised (obj_utils.py:171-176), then pos_enc (coord.py:199-210)
-            const float vx = cs * vd[0] - sn * vd[1];
-            const float vy = sn * vx + cs * vd[1];
-            float d[3] = {b[5] * vx, b[6] * vy, b[7] * vd[2]};
-            const float nrm = sqrtf((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
+            float vd[3];
 #pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                d[c] = d[c] / nrm;
-                de[c] = d[c];
-            }
+            for (int c = 0; c < 3; ++c) vd[c] = a.viewdirs[(size_t)ray * 3 + c];
+            nlr_box_dir(b0, b1, vd, de);
 #pragma unroll
             for (int j = 0; j < NLR_OBJ_MAX_DEG; ++j)
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
-                    const float xb = d[c] * (float)(1 << j);
+                    const float xb = de[c] * (float)(1 << j);
                     ds0[3 * j + c] = sinf(xb);
                     ds1[3 * j + c] = sinf(xb + 0.5f * 3.14159265358979323846f);
                 }
@@ -648,11 +659,8 @@ __global__ void __launch_bounds__(64 * NLR_OBJ_WAVES) nlr_objmlp_kernel(const Ob
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------
-struct ObjClass {
-    ObjNet net;
-};
 struct NlrObjects {
-    std::vector<ObjClass> cls;
+    std::vector<ObjNet> cls;
     ObjNet *nets_dev = nullptr;  // the same, as the kernel reads them
     std::vector<void *> allocs;
     int32_t *track_class = nullptr;  // dev
@@ -728,7 +736,7 @@ extern "C" int nlr_objects_create(const NlrObjectsDesc *d, NlrObjects **out, voi
     for (uint32_t c = 0; c < d->n_classes; ++c) {
         const NlrObjClassDesc &cd = d->classes[c];
         const NlrMlpDesc &md = cd.mlp;
-        ObjNet &n = o->cls[c].net;
+        ObjNet &n = o->cls[c];
         memset(&n, 0, sizeof(n));
 #define OBJ_REQ(cond, ...)                   \
     if (!(cond)) {                           \
@@ -790,25 +798,19 @@ extern "C" int nlr_objects_create(const NlrObjectsDesc *d, NlrObjects **out, voi
                 "objects_create: the classes' grids must share level_dim and table dtype (one kernel instance serves them all)");
 #undef OBJ_REQ
     }
-    {
-        std::vector<ObjNet> nets;
-        for (auto &c : o->cls) nets.push_back(c.net);
-        if ((rc = obj_upload(o, nets.data(), nets.size() * sizeof(ObjNet), (void **)&o->nets_dev, st))) return fail(rc);
-    }
+    if ((rc = obj_upload(o, o->cls.data(), o->cls.size() * sizeof(ObjNet), (void **)&o->nets_dev, st))) return fail(rc);
     *out = own.release();
     return NLR_OK;
 }
 
 extern "C" void nlr_objects_destroy(NlrObjects *o) { delete o; }
 
-static inline size_t obj_al(size_t b) { return (b + 255) & ~(size_t)255; }
-
 extern "C" size_t nlr_objects_workspace_bytes(const NlrObjects *o, uint32_t N, uint32_t S) {
     if (!o) return 0;
     const size_t M = (size_t)N * S;
     const size_t nw = ((M + 255) / 256) * 4;
-    return 256 + 256 /* counts */ + obj_al(M * 4) /* winner */ + obj_al(o->cls.size() * M * 4) /* lists */ +
-           obj_al(o->cls.size() * nw * 4) /* per-wave counts / offsets */;
+    return 256 + 256 /* counts */ + al(M * 4) /* winner */ + al(o->cls.size() * M * 4) /* lists */ +
+           al(o->cls.size() * nw * 4) /* per-wave counts / offsets */;
 }
 
 int nlr_objects_apply_impl(const NlrObjects *o, const NlrRays *rays, const float *tdist, const float *box_params, uint32_t N, uint32_t S,
@@ -828,10 +830,10 @@ int nlr_objects_apply_impl(const NlrObjects *o, const NlrRays *rays, const float
     uint32_t *counts = (uint32_t *)p;
     p += 256;
     int32_t *winner = (int32_t *)p;
-    p += obj_al(M * 4);
+    p += al(M * 4);
     uint32_t *lists = (uint32_t *)p;
     const uint32_t nc = (uint32_t)o->cls.size();
-    p += obj_al((size_t)nc * M * 4);
+    p += al((size_t)nc * M * 4);
     uint32_t *wave_counts = (uint32_t *)p;
     const uint32_t nblk = (uint32_t)((M + 255) / 256), nw = nblk * 4;
     hipLaunchKernelGGL(nlr_box_owner_kernel, dim3(nblk), dim3(256), 0, st, tdist, rays->origins, rays->directions, box_params, N, S, n_obj,
@@ -863,7 +865,7 @@ int nlr_objects_apply_impl(const NlrObjects *o, const NlrRays *rays, const float
     a.density = density;
     a.rgb = rgb;
     a.sem = semantic;
-    const GridParams &gp0 = o->cls[0].net.gp;
+    const GridParams &gp0 = o->cls[0].gp;
 #define OBJ_LAUNCH(T, C, LM) hipLaunchKernelGGL((nlr_objmlp_kernel<T, C, LM>), dim3(grid, nc), dim3(64 * NLR_OBJ_WAVES), 0, st, o->nets_dev, a)
     const bool f32t = gp0.table_dtype == 0;
     if (gp0.C == 2) { if (f32t) OBJ_LAUNCH(float, 2, 8); else OBJ_LAUNCH(__half, 2, 8); }

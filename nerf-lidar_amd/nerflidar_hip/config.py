@@ -118,6 +118,21 @@ class ModelConfig:
     def level_samples(self) -> List[int]:
         return [int(s) for s in self.num_prop_samples[: self.num_levels - 1]] + [int(self.num_nerf_samples)]
 
+    def level_schedule(self, train_frac: float = 1.0):
+        """(S, dilation, anneal) of every level, as the level loop hands them to the resampling (ZI/models.py:322-346)."""
+        use_dil = self.dilation_bias > 0 or self.dilation_multiplier > 0
+        anneal = (self.anneal_slope * train_frac) / ((self.anneal_slope - 1) * train_frac + 1) if self.anneal_slope > 0 else 1.0
+        prod = 1.0
+        for li, S in enumerate(self.level_samples()):
+            yield S, (self.dilation_bias + self.dilation_multiplier * 1.0 / prod) if (li > 0 and use_dil) else 0.0, anneal
+            prod *= S
+
+    def deterministic_bg(self) -> float:
+        """Background value of a render without random draws (ZI/models.py:488-500): the range's value if it is a point, else its
+        midpoint."""
+        lo, hi = self.bg_intensity_range
+        return float(lo) if lo == hi else (lo + hi) / 2
+
 
 def obj_mlp_config(class_type: int = 255, latent_size: int = 128, log2_hashmap: int = 21, use_semantic: bool = True) -> MLPConfig:
     """ObjMLP as `Model.__init__` builds it in latent mode (ZI/models.py:125-142) under the shipped gin

@@ -198,6 +198,13 @@ class GridEncoder(nn.Module):
         self.embeddings = nn.Parameter(torch.empty(rows, level_dim))
         self.reset_parameters()
 
+    @classmethod
+    def from_mlp_config(cls, cfg) -> "GridEncoder":
+        """The hash grid an `MLPConfig` describes (ZI/models.py:867-880), on the CPU with fresh embeddings."""
+        return cls(input_dim=3, num_levels=cfg.grid_num_levels, level_dim=cfg.grid_level_dim, base_resolution=cfg.grid_base_resolution,
+                   desired_resolution=cfg.grid_disired_resolution, log2_hashmap_size=cfg.grid_log2_hashmap_size, gridtype="hash",
+                   align_corners=False)
+
     @torch.no_grad()
     def reset_parameters(self):
         nn.init.uniform_(self.embeddings, -self.init_std, self.init_std)

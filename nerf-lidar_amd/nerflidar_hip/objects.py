@@ -107,15 +107,84 @@ def _pos_enc(x: torch.Tensor, deg: int) -> torch.Tensor:
     return torch.cat([x, torch.sin(torch.cat([xb, xb + 0.5 * np.pi], dim=-1))], dim=-1)
 
 
+def box_frame(origins, dirs, viewdirs, td, box, ri, si, tr):
+    """Box coordinates and normalised box-frame view direction of the owned samples (ray ri, sample si, track tr), from the
+    per-(ray, track) constants `box` = cos, sin, t_w_o (3), scale (3): obj_utils.py:158-176."""
+    bp = box[ri, tr]
+    t_mid = 0.5 * (td[ri, si] + td[ri, si + 1])
+    pw = t_mid[:, None] * dirs[ri] + origins[ri]
+    cs, sn = bp[:, 0], bp[:, 1]
+    rx = cs * pw[:, 0] - sn * pw[:, 1]
+    p_all = bp[:, 5:8] * (torch.stack([rx, sn * rx + cs * pw[:, 1], pw[:, 2]], dim=-1) + bp[:, 2:5])
+    vd = viewdirs[ri]
+    vx = cs * vd[:, 0] - sn * vd[:, 1]
+    d_all = bp[:, 5:8] * torch.stack([vx, sn * vx + cs * vd[:, 1], vd[:, 2]], dim=-1)
+    d_all = d_all / torch.norm(d_all, dim=-1, keepdim=True)
+    return p_all, d_all
+
+
+def track_box_params(tracks: torch.Tensor, timestamps: torch.Tensor) -> torch.Tensor:
+    """[N, n_obj, 8] world -> box constants of every ray and track [n_obj, T, 9] at the ray's timestamp (`nlr_track_box_params`:
+    get_pose + the constants of world2object, obj_utils.py:431-475,116-176)."""
+    dev = tracks.device
+    tracks = tracks.contiguous()
+    ts = timestamps.reshape(-1).to(dev, torch.float32).contiguous()
+    box = torch.empty(ts.shape[0], tracks.shape[0], 8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().nlr_track_box_params(_lib.ptr(tracks), _lib.ptr(ts), ts.shape[0], tracks.shape[0], tracks.shape[1],
+                                                   _lib.ptr(box), _lib.current_stream()), "nlr_track_box_params")
+    return box
+
+
+def check_instance_obj(config) -> None:
+    """The `Config.instance_obj` settings the reference itself cannot run."""
+    if config.use_intensity:
+        raise NotImplementedError("instance_obj with use_intensity: ObjMLP has no intensity head and the reference's merge assigns "
+                                  "None into the intensity tensor (ZI/models.py:469) - not a runnable configuration")
+    if config.latent_size <= 0:
+        raise NotImplementedError("per-instance ObjMLPs (Config.latent_size = 0) are not a runnable configuration under the shipped "
+                                  "gin (ObjMLP.split_latent = True indexes latent = None, ZI/models.py:1201-1203)")
+
+
+# ---- the Linear stacks, written once over `linear(name, x)`: how the layer of that reference name is applied ------------------
+def view_mlp(cfg: MLPConfig, linear, x: torch.Tensor, *extras: torch.Tensor) -> torch.Tensor:
+    """ZI/models.py:1190-1255: rgb from [bottleneck x | extras] (direction encoding, texture latent; broadcast to x's leading
+    axes by the caller) through `net_depth_viewdirs` layers with the skip concatenation behind layer `skip_layer_dir`."""
+    h = inputs = torch.cat([x, *extras], dim=-1)
+    for i in range(cfg.net_depth_viewdirs):
+        h = F.relu(linear(f"lin_second_stage_{i}", h))
+        if i == cfg.skip_layer_dir:
+            h = torch.cat([h, inputs], dim=-1)
+    rgb = torch.sigmoid(cfg.rgb_premultiplier * linear("rgb_layer", h) + cfg.rgb_bias)
+    return rgb * (1 + 2 * cfg.rgb_padding) - cfg.rgb_padding
+
+
+def obj_mlp_forward(cfg: MLPConfig, encoder, linear, pts: torch.Tensor, viewdirs: torch.Tensor, latent: Optional[torch.Tensor]):
+    """ZI/models.py:1036-1265 for ObjMLP: pts [n,3] in box coordinates, unit viewdirs [n,3], latent [n, latent_size] or None.
+    Hash grid on the box coordinates, [grid | shape half of the latent] -> 64 -> bottleneck, fixed one-hot semantic of the class,
+    view MLP on [bottleneck | pos_enc(dir) | texture half]."""
+    feats = encoder(pts.contiguous(), bound=1)
+    if latent is not None:
+        feats = torch.cat([feats, latent[:, : cfg.latent_size // 2] if cfg.split_latent else latent], dim=-1)
+    x = linear("density_layer.2", F.relu(linear("density_layer.0", feats)))
+    out = {"density": F.softplus(x[..., 0] + cfg.density_bias)}
+    if cfg.use_semantic:
+        sem = torch.zeros(x.shape[0], cfg.class_num, device=x.device)
+        if cfg.class_type != 255:
+            sem[:, cfg.class_type] = 1.0
+        out["semantic"] = sem
+    tex = (latent[:, cfg.latent_size // 2:],) if cfg.split_latent else ()
+    out["rgb"] = view_mlp(cfg, linear, x, _pos_enc(viewdirs, cfg.deg_view), *tex)
+    return out
+
+
 class ObjMLP:
     """One class's object network: our `GridEncoder` (HIP op) + the Linear stack of ZI/models.py:MLP as ObjMLP configures it."""
 
     def __init__(self, prefix: str, cfg: MLPConfig, sd: Dict[str, np.ndarray], device):
         self.cfg, self.prefix = cfg, prefix
         dev = torch.device(device)
-        self.encoder = GridEncoder(input_dim=3, num_levels=cfg.grid_num_levels, level_dim=cfg.grid_level_dim,
-                                   base_resolution=cfg.grid_base_resolution, desired_resolution=cfg.grid_disired_resolution,
-                                   log2_hashmap_size=cfg.grid_log2_hashmap_size, gridtype="hash", align_corners=False).to(dev)
+        self.encoder = GridEncoder.from_mlp_config(cfg).to(dev)
         emb = torch.from_numpy(np.ascontiguousarray(sd[f"{prefix}.encoder.embeddings"], np.float32))
         if tuple(emb.shape) != tuple(self.encoder.embeddings.shape):
             raise ValueError(f"{prefix}.encoder.embeddings: shape {tuple(emb.shape)}, expected {tuple(self.encoder.embeddings.shape)}")
@@ -129,39 +198,13 @@ class ObjMLP:
             self.lin[name] = (torch.from_numpy(np.ascontiguousarray(w, np.float32)).to(dev),
                               torch.from_numpy(np.ascontiguousarray(b, np.float32)).to(dev))
 
-    def _l(self, name, x):
-        w, b = self.lin[name]
-        return F.linear(x, w, b)
-
     @torch.no_grad()
     def forward(self, pts: torch.Tensor, viewdirs: torch.Tensor, latent: Optional[torch.Tensor]):
-        """ZI/models.py:1036-1265 for ObjMLP: pts [n,3] in box coordinates, unit viewdirs [n,3], latent [latent_size] (one track)
-        or [n, latent_size] (a code per point: points of several tracks of this class in one call)."""
-        cfg = self.cfg
-        feats = self.encoder(pts.contiguous(), bound=1)
-        if latent is not None:
-            if latent.dim() == 1:  # one track: the reference repeats its code for every point (models.py:438)
-                latent = latent[None, :].expand(feats.shape[0], -1)
-            feats = torch.cat([feats, latent[:, : cfg.latent_size // 2] if cfg.split_latent else latent], dim=-1)
-        x = self._l("density_layer.2", F.relu(self._l("density_layer.0", feats)))
-        out = {"density": F.softplus(x[..., 0] + cfg.density_bias)}
-        if cfg.use_semantic:
-            sem = torch.zeros(x.shape[0], cfg.class_num, device=x.device)
-            if cfg.class_type != 255:
-                sem[:, cfg.class_type] = 1.0
-            out["semantic"] = sem
-        h = [x, _pos_enc(viewdirs, cfg.deg_view)]
-        if cfg.split_latent:
-            h.append(latent[:, cfg.latent_size // 2:])
-        h = torch.cat(h, dim=-1)
-        inputs = h
-        for i in range(cfg.net_depth_viewdirs):
-            h = F.relu(self._l(f"lin_second_stage_{i}", h))
-            if i == cfg.skip_layer_dir:
-                h = torch.cat([h, inputs], dim=-1)
-        rgb = torch.sigmoid(cfg.rgb_premultiplier * self._l("rgb_layer", h) + cfg.rgb_bias)
-        out["rgb"] = rgb * (1 + 2 * cfg.rgb_padding) - cfg.rgb_padding
-        return out
+        """`obj_mlp_forward` on the loaded tensors; latent [latent_size] (one track: the reference repeats its code for every
+        point, models.py:438) or [n, latent_size] (a code per point: points of several tracks of this class in one call)."""
+        if latent is not None and latent.dim() == 1:
+            latent = latent[None, :].expand(pts.shape[0], -1)
+        return obj_mlp_forward(self.cfg, self.encoder, lambda name, x: F.linear(x, *self.lin[name]), pts, viewdirs, latent)
 
 
 class DynamicModel(Model):
@@ -176,9 +219,7 @@ class DynamicModel(Model):
         import dataclasses
         static_mc = dataclasses.replace(mc, config=dataclasses.replace(mc.config, instance_obj=False))
         super().__init__(static_mc, state_dict, device=device, **kw)
-        if mc.config.use_intensity:
-            raise NotImplementedError("instance_obj with use_intensity: ObjMLP has no intensity head and the reference's merge "
-                                      "assigns None into the intensity tensor (ZI/models.py:469) - not a runnable configuration")
+        check_instance_obj(mc.config)
         sd = {k: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)) for k, v in state_dict.items()}
         self.tracks = torch.as_tensor(np.asarray(tracks, np.float32), device=self.device)
         self.class_ids = [query_class(c) for c in class_names]
@@ -193,8 +234,8 @@ class DynamicModel(Model):
         self._class_rank = torch.tensor([self._class_list.index(c) for c in self.class_ids], device=self.device)
         self._track_rank = torch.arange(1, len(self.class_ids) + 1, device=self.device)
         self.latents = [torch.from_numpy(np.ascontiguousarray(sd[f"latent_vector_dict.obj_latent_{t}"], np.float32)).to(self.device)
-                        for t in range(len(self.class_ids))] if lat > 0 else [None] * len(self.class_ids)
-        self._latent_table = torch.stack(self.latents) if lat > 0 else None
+                        for t in range(len(self.class_ids))]
+        self._latent_table = torch.stack(self.latents)
         self._objects = C.c_void_p(None)
         self._build_native(sd, lat)
 
@@ -212,11 +253,11 @@ class DynamicModel(Model):
             descs[i].latent_size, descs[i].split_latent = lat, int(net.cfg.split_latent)
             descs[i].class_type = int(net.cfg.class_type)
         tc = np.ascontiguousarray([self._class_list.index(c) for c in self.class_ids], np.int32)
-        lt = np.ascontiguousarray(self._latent_table.cpu().numpy(), np.float32) if lat > 0 else None
+        lt = np.ascontiguousarray(self._latent_table.cpu().numpy(), np.float32)
         od = _lib.NlrObjectsDesc()
         od.n_classes, od.classes = n_cls, descs
         od.n_tracks, od.track_class = len(self.class_ids), tc.ctypes.data
-        od.latents = lt.ctypes.data if lt is not None else None
+        od.latents = lt.ctypes.data
         with torch.cuda.device(self.device):
             rc = _lib.lib().nlr_objects_create(C.byref(od), C.byref(self._objects), _lib.current_stream())
         self._keep.clear()
@@ -248,18 +289,11 @@ class DynamicModel(Model):
         _lib.check(rc, name)
 
     def box_params(self, timestamp: torch.Tensor, curr_track=None) -> torch.Tensor:
-        """[N, n_obj, 8] world -> box constants of every ray and track at the ray's timestamp (`nlr_track_box_params`:
-        get_pose + the constants of world2object, obj_utils.py:431-475,116-176)."""
+        """`track_box_params` of the stored tracks, or of `curr_track` (models.py:307-313), at the rays' timestamps."""
         if curr_track is None:
             curr_track = getattr(self, "_track_override", None)
-        tracks = self.tracks if curr_track is None else torch.as_tensor(curr_track, device=self.device, dtype=torch.float32)
-        tracks = tracks.contiguous()
-        ts = timestamp.reshape(-1).to(self.device, torch.float32).contiguous()
-        box = torch.empty(ts.shape[0], tracks.shape[0], 8, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().nlr_track_box_params(_lib.ptr(tracks), _lib.ptr(ts), ts.shape[0], tracks.shape[0], tracks.shape[1],
-                                                       _lib.ptr(box), _lib.current_stream()), "nlr_track_box_params")
-        return box
+        return track_box_params(self.tracks if curr_track is None else torch.as_tensor(curr_track, device=self.device, dtype=torch.float32),
+                                timestamp)
 
     @torch.no_grad()
     def render_rays(self, batch, train_frac: float = 1.0, compute_extras: bool = True, sample_n: int = 7, sample_m: int = 3,
@@ -333,18 +367,14 @@ class DynamicModel(Model):
         new = lambda *shape, dtype=f32: torch.empty(*shape, device=dev, dtype=dtype)
         ws = torch.empty(max(int(L.nlr_workspace_bytes(self._handle, n)), 1 << 20), dtype=torch.uint8, device=dev)
         st = _lib.current_stream()
-        samples = mc.level_samples()
+        n_levels = len(mc.level_samples())
         prev_s = prev_w = None
-        n_prev, prod = 0, 1.0
+        n_prev = 0
         hist: List[Dict[str, torch.Tensor]] = []
         r: Dict[str, torch.Tensor] = {}
         with torch.cuda.device(dev):
-            for li, S in enumerate(samples):
-                last = li == len(samples) - 1
-                use_dil = mc.dilation_bias > 0 or mc.dilation_multiplier > 0                      # models.py:322-346
-                dilation = (mc.dilation_bias + mc.dilation_multiplier * 1.0 / prod) if (li > 0 and use_dil) else 0.0
-                prod *= S
-                anneal = (mc.anneal_slope * train_frac) / ((mc.anneal_slope - 1) * train_frac + 1) if mc.anneal_slope > 0 else 1.0
+            for li, (S, dilation, anneal) in enumerate(mc.level_schedule(train_frac)):
+                last = li == n_levels - 1
                 sdist, tdist = new(n, S + 1), new(n, S + 1)
                 _lib.check(L.nlr_resample_level(_lib.ptr(prev_s), _lib.ptr(prev_w), n_prev, float(dilation), float(anneal),
                                                 float(mc.resample_padding), S, None, _lib.ptr(near), _lib.ptr(far), float(mc.power_lambda),
@@ -370,18 +400,8 @@ class DynamicModel(Model):
                     order = torch.sort(self._class_rank[tr], stable=True)[1]
                     ri, si, tr = ri[order], si[order], tr[order]
                     per_class = torch.bincount(self._class_rank[tr], minlength=len(self._class_list)).tolist()   # host sync 2
-                    # box coordinates of the owned samples, by the expressions of obj_utils.world2object (:158-176)
-                    bp = box_params[ri, tr]
-                    t_mid = 0.5 * (tdist[ri, si] + tdist[ri, si + 1])
-                    pw = t_mid[:, None] * dirs[ri] + origins[ri]
-                    cs, sn = bp[:, 0], bp[:, 1]
-                    rx = cs * pw[:, 0] - sn * pw[:, 1]
-                    p_all = bp[:, 5:8] * (torch.stack([rx, sn * rx + cs * pw[:, 1], pw[:, 2]], dim=-1) + bp[:, 2:5])
-                    vd = viewdirs[ri]
-                    vx = cs * vd[:, 0] - sn * vd[:, 1]
-                    d_all = bp[:, 5:8] * torch.stack([vx, sn * vx + cs * vd[:, 1], vd[:, 2]], dim=-1)
-                    d_all = d_all / torch.norm(d_all, dim=-1, keepdim=True)
-                    lat_all = self._latent_table[tr] if self._latent_table is not None else None
+                    p_all, d_all = box_frame(origins, dirs, viewdirs, tdist, box_params, ri, si, tr)
+                    lat_all = self._latent_table[tr]
                     idx = ri * S + si
                     lo = 0
                     for rank, cnt in enumerate(per_class):
@@ -389,7 +409,7 @@ class DynamicModel(Model):
                             continue
                         sl = slice(lo, lo + cnt)
                         lo += cnt
-                        o = self.obj_mlps[self._class_list[rank]].forward(p_all[sl], d_all[sl], None if lat_all is None else lat_all[sl])
+                        o = self.obj_mlps[self._class_list[rank]].forward(p_all[sl], d_all[sl], lat_all[sl])
                         density.view(-1)[idx[sl]] = o["density"]
                         if last:
                             rgb.view(3, -1)[:, idx[sl]] = o["rgb"].t()
@@ -410,9 +430,8 @@ class DynamicModel(Model):
                             r["labels"] = new(n, dtype=torch.int32)
                     for k, t in r.items():
                         setattr(out, k, t.data_ptr())
-                bg = mc.bg_intensity_range[0] if mc.bg_intensity_range[0] == mc.bg_intensity_range[1] else sum(mc.bg_intensity_range) / 2
                 _lib.check(L.nlr_composite_level(_lib.ptr(density), _lib.ptr(tdist), _lib.ptr(dirs), _lib.ptr(rgb), _lib.ptr(sem), None,
-                                                 _lib.ptr(far), _lib.ptr(origins), n, S, K, int(mc.opaque_background), float(bg),
+                                                 _lib.ptr(far), _lib.ptr(origins), n, S, K, int(mc.opaque_background), mc.deterministic_bg(),
                                                  int(compute_extras and last), float(scale_factor if last else 0.0), _lib.ptr(weights),
                                                  C.byref(out) if last else None, _lib.ptr(depth_l), st), "nlr_composite_level")
                 h = {"depth": depth_l, "obj_mask": obj_mask}

@@ -16,6 +16,9 @@ import numpy as np
 import torch
 
 from . import _lib
+from .config import obj_mlp_config
+from .gridencoder import GridEncoder
+from .objects import _pos_enc, box_frame, check_instance_obj, obj_mlp_forward, query_class, track_box_params, view_mlp
 
 
 class _Composite(torch.autograd.Function):
@@ -422,7 +425,6 @@ class TrainableNerfLevel(torch.nn.Module):
         fused_wgrad (needs fused_mlp): the weight and bias gradients from nlr_mlp_train_wgrad (one MFMA kernel, f32 accumulation
         over all of M, bit-reproducible) instead of split-K library GEMMs."""
         super().__init__()
-        from .gridencoder import GridEncoder
         nn = torch.nn
         self.cfg = cfg
         if fused_wgrad and not fused_mlp:
@@ -439,9 +441,7 @@ class TrainableNerfLevel(torch.nn.Module):
             # the fused kernels wire the skip concatenation into view layer 1 (nlr_mlp_train.hip); another position has the same
             # parameter count, so nothing downstream would notice (the inference path rejects it too, nlr_api.hip)
             raise NotImplementedError(f"fused training MLP: skip_layer_dir = {cfg.skip_layer_dir} is not wired, only 0 (use fused_mlp=False)")
-        self.encoder = GridEncoder(input_dim=3, num_levels=cfg.grid_num_levels, level_dim=cfg.grid_level_dim,
-                                   base_resolution=cfg.grid_base_resolution, desired_resolution=cfg.grid_disired_resolution,
-                                   log2_hashmap_size=cfg.grid_log2_hashmap_size, gridtype="hash", align_corners=False)
+        self.encoder = GridEncoder.from_mlp_config(cfg)
         feat = cfg.grid_num_levels * cfg.grid_level_dim
         self.density_layer = nn.Sequential(nn.Linear(feat, 64), nn.ReLU(), nn.Linear(64, cfg.bottleneck_width))
         in_rgb = cfg.bottleneck_width + cfg.dim_dir_enc
@@ -473,7 +473,6 @@ class TrainableNerfLevel(torch.nn.Module):
         view MLP (`lin_second_stage_*`, `rgb_layer`) forward and backward and come back with rgb = 0.  THE CALLER PROMISES that the
         loss ignores their colour: `batch['mask_rgb']` is zero on rays [n, N) (train.py:316-320).  Under that promise every gradient
         is the one the masked loss gives without `color_rays`; nothing here reads the mask (a step stays free of host reads)."""
-        from .objects import _pos_enc
         F = torch.nn.functional
         cfg = self.cfg
         nc = _check_color_rays(color_rays, tdist.shape[0])
@@ -494,14 +493,7 @@ class TrainableNerfLevel(torch.nn.Module):
         n_all = x.shape[0]
         if nc is not None:  # the view MLP on the rays with colour supervision only
             x, enc = x[:nc], enc[:nc]
-        h = torch.cat([x, enc[:, None, :].expand(-1, x.shape[1], -1)], dim=-1)
-        inputs = h
-        for i in range(cfg.net_depth_viewdirs):
-            h = F.relu(getattr(self, f"lin_second_stage_{i}")(h))
-            if i == cfg.skip_layer_dir:
-                h = torch.cat([h, inputs], dim=-1)
-        rgb = torch.sigmoid(cfg.rgb_premultiplier * self.rgb_layer(h) + cfg.rgb_bias)
-        rgb = rgb * (1 + 2 * cfg.rgb_padding) - cfg.rgb_padding
+        rgb = view_mlp(cfg, lambda name, t: getattr(self, name)(t), x, enc[:, None, :].expand(-1, x.shape[1], -1))
         if nc is not None:  # rgb = 0 for the rest (a zeros block carries no gradient)
             rgb = torch.cat([rgb, rgb.new_zeros(n_all - nc, *rgb.shape[1:])], dim=0)
         out["rgb"] = rgb
@@ -530,7 +522,6 @@ class TrainableNerfLevel(torch.nn.Module):
         return ws
 
     def _forward_fused(self, batch, feats, color_rays=None):
-        from .objects import _pos_enc
         cfg = self.cfg
         n, S = feats.shape[0], feats.shape[1]
         self._color_rays = color_rays
@@ -596,12 +587,9 @@ class TrainablePropLevel(torch.nn.Module):
         """fused: the density network through `nlr_prop_mlp_forward` / `_backward` instead of two library GEMMs with 6-8 wide
         operands; same parameters, same gradients (fp32 both ways)."""
         super().__init__()
-        from .gridencoder import GridEncoder
         nn = torch.nn
         self.cfg, self.fused = cfg, bool(fused)
-        self.encoder = GridEncoder(input_dim=3, num_levels=cfg.grid_num_levels, level_dim=cfg.grid_level_dim,
-                                   base_resolution=cfg.grid_base_resolution, desired_resolution=cfg.grid_disired_resolution,
-                                   log2_hashmap_size=cfg.grid_log2_hashmap_size, gridtype="hash", align_corners=False)
+        self.encoder = GridEncoder.from_mlp_config(cfg)
         self.density_layer = nn.Sequential(nn.Linear(cfg.grid_num_levels * cfg.grid_level_dim, 64), nn.ReLU(), nn.Linear(64, 1))
 
     load_reference = TrainableNerfLevel.load_reference
@@ -629,13 +617,10 @@ class TrainableObjMLP(torch.nn.Module):
 
     def __init__(self, cfg):
         super().__init__()
-        from .gridencoder import GridEncoder
         from .weights import mlp_param_shapes
         nn = torch.nn
         self.cfg = cfg
-        self.encoder = GridEncoder(input_dim=3, num_levels=cfg.grid_num_levels, level_dim=cfg.grid_level_dim,
-                                   base_resolution=cfg.grid_base_resolution, desired_resolution=cfg.grid_disired_resolution,
-                                   log2_hashmap_size=cfg.grid_log2_hashmap_size, gridtype="hash", align_corners=False)
+        self.encoder = GridEncoder.from_mlp_config(cfg)
         for name, (o, i), kaiming in mlp_param_shapes(cfg):
             lin = nn.Linear(i, o)
             if kaiming:
@@ -654,51 +639,11 @@ class TrainableObjMLP(torch.nn.Module):
     load_reference = TrainableNerfLevel.load_reference
 
     def forward(self, pts: torch.Tensor, viewdirs: torch.Tensor, latent: Optional[torch.Tensor]) -> Dict[str, torch.Tensor]:
-        from .objects import _pos_enc
-        F = torch.nn.functional
-        cfg = self.cfg
-        feats = self.encoder(pts.contiguous(), bound=1)
-        if latent is not None:
-            feats = torch.cat([feats, latent[:, : cfg.latent_size // 2] if cfg.split_latent else latent], dim=-1)
-        x = self.density_layer(feats)
-        out = {"density": F.softplus(x[..., 0] + cfg.density_bias)}
-        if cfg.use_semantic:
-            sem = torch.zeros(x.shape[0], cfg.class_num, device=x.device)
-            if cfg.class_type != 255:
-                sem[:, cfg.class_type] = 1.0
-            out["semantic"] = sem
-        h = [x, _pos_enc(viewdirs, cfg.deg_view)]
-        if cfg.split_latent:
-            h.append(latent[:, cfg.latent_size // 2:])
-        h = torch.cat(h, dim=-1)
-        inputs = h
-        for i in range(cfg.net_depth_viewdirs):
-            h = F.relu(getattr(self, f"lin_second_stage_{i}")(h))
-            if i == cfg.skip_layer_dir:
-                h = torch.cat([h, inputs], dim=-1)
-        rgb = torch.sigmoid(cfg.rgb_premultiplier * self.rgb_layer(h) + cfg.rgb_bias)
-        out["rgb"] = rgb * (1 + 2 * cfg.rgb_padding) - cfg.rgb_padding
-        return out
-
-
-def _box_frame(origins, dirs, viewdirs, td, box, ri, si, tr):
-    """Box coordinates and normalised box-frame view direction of the owned samples (ray ri, sample si, track tr), from the
-    per-(ray, track) constants `box` = cos, sin, t_w_o (3), scale (3): obj_utils.py:158-176."""
-    bp = box[ri, tr]
-    t_mid = 0.5 * (td[ri, si] + td[ri, si + 1])
-    pw = t_mid[:, None] * dirs[ri] + origins[ri]
-    cs, sn = bp[:, 0], bp[:, 1]
-    rx = cs * pw[:, 0] - sn * pw[:, 1]
-    p_all = bp[:, 5:8] * (torch.stack([rx, sn * rx + cs * pw[:, 1], pw[:, 2]], dim=-1) + bp[:, 2:5])
-    vd = viewdirs[ri]
-    vx = cs * vd[:, 0] - sn * vd[:, 1]
-    d_all = bp[:, 5:8] * torch.stack([vx, sn * vx + cs * vd[:, 1], vd[:, 2]], dim=-1)
-    d_all = d_all / torch.norm(d_all, dim=-1, keepdim=True)
-    return p_all, d_all
+        return obj_mlp_forward(self.cfg, self.encoder, lambda name, x: self.get_submodule(name)(x), pts, viewdirs, latent)
 
 
 class _ObjFrame(torch.autograd.Function):
-    """tracks [n_obj, T, 9] -> (box-frame points, box-frame view directions) of the owned samples.  forward = `_box_frame` on the
+    """tracks [n_obj, T, 9] -> (box-frame points, box-frame view directions) of the owned samples.  forward = `objects.box_frame` on the
     constants `nlr_track_box_params` made of the same tracks (the values of the path without gradient, bit for bit); backward =
     `nlr_obj_frame_backward`, one reduction kernel instead of the gather / index_put chain autograd would walk.  Only the tracks
     receive a gradient: ray origins and directions are data here (no pose refinement)."""
@@ -707,7 +652,7 @@ class _ObjFrame(torch.autograd.Function):
     def forward(ctx, tracks, ts, origins, dirs, viewdirs, td, box, ri, si, tr):
         ctx.save_for_backward(tracks.detach().contiguous(), ts, origins, dirs, viewdirs, td, ri.int().contiguous(), si.int().contiguous(),
                               tr.int().contiguous())
-        return _box_frame(origins, dirs, viewdirs, td, box, ri, si, tr)
+        return box_frame(origins, dirs, viewdirs, td, box, ri, si, tr)
 
     @staticmethod
     def backward(ctx, g_p, g_d):
@@ -757,16 +702,9 @@ class TrainableModel(torch.nn.Module):
         self.nerf_mlp = TrainableNerfLevel(ncfg, fused_mlp=fused_mlp, fused_wgrad=fused_wgrad)
         self.instance_obj = bool(mc.config.instance_obj)
         if self.instance_obj:
-            from .config import obj_mlp_config
-            from .objects import query_class
             if tracks is None or class_names is None:
                 raise ValueError("Config.instance_obj = True needs tracks [N_obj, T, 9] and one class name per track (dataset.bboxes)")
-            if mc.config.use_intensity:
-                raise NotImplementedError("instance_obj with use_intensity: ObjMLP has no intensity head and the reference's merge assigns "
-                                          "None into the intensity tensor (ZI/models.py:469) - not a runnable configuration")
-            if mc.config.latent_size <= 0:
-                raise NotImplementedError("per-instance ObjMLPs (Config.latent_size = 0) are not a runnable configuration under the shipped "
-                                          "gin (ObjMLP.split_latent = True indexes latent = None, ZI/models.py:1201-1203)")
+            check_instance_obj(mc.config)
             self.register_buffer("tracks", torch.as_tensor(np.asarray(tracks, np.float32)))
             self.class_ids = [query_class(c) for c in class_names]
             self._class_list = sorted(set(self.class_ids))
@@ -832,7 +770,7 @@ class TrainableModel(torch.nn.Module):
         if refine is not None:
             p_all, d_all = _ObjFrame.apply(refine[0], refine[1], origins, dirs, viewdirs, td, box, ri, si, tr)
         else:
-            p_all, d_all = _box_frame(origins, dirs, viewdirs, td, box, ri, si, tr)
+            p_all, d_all = box_frame(origins, dirs, viewdirs, td, box, ri, si, tr)
         table = torch.stack([self.latent_vector_dict[f"obj_latent_{t}"] for t in range(len(self.class_ids))])
         lat_all = table[tr]
         rank = self._class_rank[tr]
@@ -869,27 +807,20 @@ class TrainableModel(torch.nn.Module):
         dirs = batch["directions"].reshape(n, 3).contiguous().float()
         randomized = randomized or rand is not None
         prev_s = prev_w = None
-        n_prev, prod = 0, 1.0
+        n_prev = 0
         renderings, history = [], []
-        samples = mc.level_samples()
+        n_levels = len(mc.level_samples())
         box = None
         if self.instance_obj:
             if "timestamp" not in batch:
                 raise RuntimeError("batch['timestamp'] is missing (ZI/models.py:315)")
             tracks = (self.tracks if curr_track is None else torch.as_tensor(curr_track, device=dev, dtype=torch.float32)).contiguous()
             ts = batch["timestamp"].reshape(-1).to(dev, torch.float32).contiguous()
-            box = torch.empty(n, tracks.shape[0], 8, device=dev)
-            with torch.cuda.device(dev):
-                _lib.check(L.nlr_track_box_params(_lib.ptr(tracks), _lib.ptr(ts), n, tracks.shape[0], tracks.shape[1], _lib.ptr(box),
-                                                  _lib.current_stream()), "nlr_track_box_params")
+            box = track_box_params(tracks, ts)  # (tracks and ts are kept in this form for `refine`: the adjoint reads the same two tensors)
             # track refinement (train.py:244-268): a track that requires a gradient gets one from the last level's object samples
             refine = (tracks, ts) if tracks.requires_grad and torch.is_grad_enabled() else None
-        for li, (S, level) in enumerate(zip(samples, self.levels())):
-            last = li == len(samples) - 1
-            use_dil = mc.dilation_bias > 0 or mc.dilation_multiplier > 0                      # models.py:322-346
-            dilation = (mc.dilation_bias + mc.dilation_multiplier * 1.0 / prod) if (li > 0 and use_dil) else 0.0
-            prod *= S
-            anneal = (mc.anneal_slope * train_frac) / ((mc.anneal_slope - 1) * train_frac + 1) if mc.anneal_slope > 0 else 1.0
+        for li, ((S, dilation, anneal), level) in enumerate(zip(mc.level_schedule(train_frac), self.levels())):
+            last = li == n_levels - 1
             sdist, tdist = torch.empty(n, S + 1, device=dev), torch.empty(n, S + 1, device=dev)
             jit = torch.rand(n, device=dev, generator=rand) if randomized else None
             with torch.cuda.device(dev):
@@ -908,12 +839,8 @@ class TrainableModel(torch.nn.Module):
             # background colour (models.py:488-500): the range's value if it is a point, its midpoint for a deterministic render,
             # otherwise one uniform draw per ray and channel - composited here (the kernel's background is a scalar)
             lo_bg, hi_bg = mc.bg_intensity_range
-            bg_rand = None
-            if lo_bg == hi_bg:
-                bg = float(lo_bg)
-            elif not randomized:
-                bg = (lo_bg + hi_bg) / 2
-            else:
+            bg, bg_rand = mc.deterministic_bg(), None
+            if randomized and lo_bg != hi_bg:
                 bg, bg_rand = 0.0, torch.rand(n, 3, device=dev, generator=rand) * (hi_bg - lo_bg) + lo_bg
             r = volumetric_render(o["density"], tdist, dirs, rgbs, o.get("semantic") if last else None, o.get("intensity") if last else None,
                                   bool(mc.opaque_background), bg)

@@ -3,7 +3,7 @@ T = 20 recorded poses, the samples of the last level that the tracks own.
 Stage: the adjoint "cotangents of the box-frame points / directions of the owned samples -> d/d tracks", two forms on the same
 tensors in one process:
   (a) plain torch autograd: a differentiable torch restatement of the box parameters (`objects.get_pose` + the constants of
-      world2object) followed by the indexing ops of `training._box_frame`; timed as backward alone (graph kept) and as forward + backward;
+      world2object) followed by the indexing ops of `objects.box_frame`; timed as backward alone (graph kept) and as forward + backward;
   (b) `nlr_obj_frame_backward`.
 HIP events around 20 calls after 3 warm-up calls, five repetitions, (a) and (b) alternating; medians.  Both forms are first compared
 with the same adjoint in float64 on the CPU; the script stops if the kernel misses the gate of its tests (2e-5 per column).
@@ -76,7 +76,7 @@ def torch_box(trk):
 
 def torch_forward():
     trk = tracks.clone().requires_grad_(True)
-    p, dd = ntrain._box_frame(o, d, v, td, torch_box(trk), ri, si, tr)
+    p, dd = nobj.box_frame(o, d, v, td, torch_box(trk), ri, si, tr)
     return trk, (p * g_p).sum() + (dd * g_d).sum()
 
 
@@ -92,7 +92,7 @@ pose = nobj.get_pose(c64(ts)[:, None], t64)
 cs64, sn64 = torch.cos(pose[..., 3]), torch.sin(pose[..., 3])
 px64 = cs64 * -pose[..., 0] - sn64 * -pose[..., 1]
 box64 = torch.cat([torch.stack([cs64, sn64, px64, sn64 * px64 + cs64 * -pose[..., 1], -pose[..., 2]], dim=-1), 1.0 / (pose[..., 4:7] / 2.0 + 1e-9)], dim=-1)
-p64, d64 = ntrain._box_frame(c64(o), c64(d), c64(v), c64(td), box64, ri.cpu(), si.cpu(), tr.cpu())
+p64, d64 = nobj.box_frame(c64(o), c64(d), c64(v), c64(td), box64, ri.cpu(), si.cpu(), tr.cpu())
 want = torch.autograd.grad((p64 * c64(g_p)).sum() + (d64 * c64(g_d)).sum(), t64)[0]
 err = lambda x: [float((x[..., c] - want[..., c]).abs().max() / want[..., c].abs().max()) for c in range(7)]
 err_a, err_b = err(ga), err(gb)

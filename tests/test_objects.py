@@ -289,3 +289,120 @@ def test_object_abi_error_paths():
     torch.cuda.synchronize()
     assert float(dens.abs().max()) == 0.0
     assert L.nlr_track_box_params(_lib.ptr(model.tracks), _lib.ptr(td), n, 3, 1, _lib.ptr(box3), None) == -1 and b"T = 1" in L.nlr_last_error()
+
+
+# ---- the owner map and the compaction at the edges of their loops -------------------------------------------------------------
+# (N, S, n_obj): the smallest shapes that reach the four-boxes-per-trip tail clamp of nlr_box_owner_kernel with 1, 3, 0, 1 and 1
+# leftover boxes, sample counts that are no multiple of 64 or 256, and exactly one whole block (64 * 4).
+OWNER_CASES = [(3, 2, 1), (37, 5, 3), (37, 5, 4), (64, 4, 5), (130, 7, 9)]
+# The test asserts, over the box constants the kernel wrote, that no |coordinate| of any (sample, box) pair lies within 1e-6 of 1.  The
+# seed was picked with torch's CPU expressions for those constants, where the closest pair of the five cases is 1.6e-4 away.
+OWNER_SEED = 4
+
+
+def _owner_scene(N, S, n_obj, seed=OWNER_SEED):
+    """Seeded rays in a narrow cone, sorted random tdist in [0, 1], and tracks from `synthetic_tracks` on those rays: track 1
+    sits on top of track 0 (the later one must win) and the last of three or more tracks is moved out of every ray's reach."""
+    gen = torch.Generator().manual_seed(1000 * seed + 100 * n_obj + N)
+    o = (torch.rand(N, 3, generator=gen) - 0.5) * 0.04
+    d = torch.tensor([1.0, 0.2, 0.1]) + (torch.rand(N, 3, generator=gen) - 0.5) * 0.5
+    td = torch.sort(torch.rand(N, S + 1, generator=gen), dim=-1)[0].contiguous()
+    ts = torch.rand(N, 1, generator=gen)
+    tracks = nobj.synthetic_tracks({"origins": o.numpy(), "directions": d.numpy()}, n_obj, 5, seed, size=(0.3, 0.2, 0.2), depth=(0.2, 0.8))
+    if n_obj >= 2:
+        tracks[1, :, :8] = tracks[0, :, :8]
+    if n_obj >= 3:
+        tracks[-1, :, :3] += 50.0
+    return o, d, td, ts, tracks
+
+
+def _owner_reference(o, d, td, box):
+    """float32 on the CPU, operation by operation in the order of the device functions (csrc/nlr_objects.hip): interval midpoint,
+    quirk rotation, scale-and-shift, strict |x| < 1, the last containing track wins.  -> (winner [N,S], box coordinates
+    [N,S,n_obj,3])."""
+    tm = 0.5 * (td[:, :-1] + td[:, 1:])
+    p = tm[..., None] * d[:, None, :] + o[:, None, :]                       # [N, S, 3]
+    b = box[:, None]                                                        # [N, 1, n_obj, 8]
+    px, py, pz = (p[..., None, c] for c in range(3))
+    rx = b[..., 0] * px - b[..., 1] * py
+    ry = b[..., 1] * rx + b[..., 0] * py                                    # (sic) the rotated x
+    x = torch.stack([b[..., 5] * (rx + b[..., 2]), b[..., 6] * (ry + b[..., 3]), b[..., 7] * (pz + b[..., 4])], dim=-1)
+    inside = (x.abs() < 1.0).all(-1)                                        # [N, S, n_obj]
+    idx = torch.arange(box.shape[1], dtype=torch.int32).expand_as(inside)
+    winner = torch.where(inside, idx, torch.full_like(idx, -1)).max(-1)[0] if box.shape[1] else torch.full(inside.shape[:2], -1, dtype=torch.int32)
+    return winner.int(), x
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("N,S,n_obj", OWNER_CASES)
+def test_owner_map_and_compaction_at_the_loop_edges(N, S, n_obj):
+    """`nlr_box_winner` and `nlr_objects_apply` (both through nlr_box_owner_kernel) against a float32 CPU restatement over the box
+    constants the kernel reads; then scan + scatter: exactly the owned samples get a density."""
+    import ctypes as C
+    from nerflidar_hip import _lib
+    g = golden("obj_REF_small")
+    mc, _, _, cfgs, sd = _scene(g)
+    names = [NAMES[t % 3] for t in range(n_obj)]
+    sd.update(nweights.synth_object_state_dict(cfgs, n_obj, seed=int(g["seed"])))
+    o, d, td, ts, tracks = _owner_scene(N, S, n_obj)
+    mc.config.instance_obj = True
+    model = nobj.DynamicModel(mc, sd, tracks, names, obj_log2_hashmap=int(g["log2_hashmap"]))
+    box = model.box_params(ts.cuda())
+    want, x = _owner_reference(o, d, td, box.cpu())
+    # ---- the conditions of the comparison, on the CPU
+    margin = float((x.abs() - 1.0).abs().min())
+    n_in = (x.abs() < 1.0).all(-1).sum(-1)
+    print(f"owner case {(N, S, n_obj)}: margin {margin:.3e}, owned {int((want >= 0).sum())} of {N * S}, in two boxes {int((n_in >= 2).sum())}")
+    assert margin > 1e-6                                    # no sample on a box face within rounding
+    if n_obj >= 2:
+        assert int((n_in >= 2).sum()) >= 1                  # the overlap decides something
+    if n_obj >= 3:
+        assert not bool((want == n_obj - 1).any())          # a track no sample reaches
+    if (N, S, n_obj) != OWNER_CASES[0]:
+        assert int((want >= 0).sum()) >= 10
+    # ---- nlr_box_winner
+    L = _lib.lib()
+    od, dd, tdd = o.cuda(), d.cuda(), td.cuda()
+    got = torch.full((N, S), -7, dtype=torch.int32, device="cuda")
+    _lib.check(L.nlr_box_winner(_lib.ptr(tdd), _lib.ptr(od), _lib.ptr(dd), _lib.ptr(box), N, S, n_obj, _lib.ptr(got), None), "nlr_box_winner")
+    assert torch.equal(got.cpu(), want)
+    # ---- nlr_objects_apply: the same map, and scan + scatter on a density buffer that starts at -1 (a softplus is never -1)
+    rays = _lib.NlrRays()
+    rays.origins, rays.directions = od.data_ptr(), dd.data_ptr()
+    dens = torch.full((N, S), -1.0, device="cuda")
+    got2 = torch.full((N, S), -7, dtype=torch.int32, device="cuda")
+    ws = torch.empty(int(L.nlr_objects_workspace_bytes(model._objects, N, S)), dtype=torch.uint8, device="cuda")
+    _lib.check(L.nlr_objects_apply(model._objects, C.byref(rays), _lib.ptr(tdd), _lib.ptr(box), N, S, n_obj, _lib.ptr(dens), None, None, 0,
+                                   _lib.ptr(got2), _lib.ptr(ws), ws.numel(), None), "nlr_objects_apply")
+    torch.cuda.synchronize()
+    assert torch.equal(got2.cpu(), want)
+    assert torch.equal((dens != -1.0).cpu(), want >= 0)
+    # ---- no tracks at all: every sample is free
+    got.fill_(-7)
+    _lib.check(L.nlr_box_winner(_lib.ptr(tdd), _lib.ptr(od), _lib.ptr(dd), None, N, S, 0, _lib.ptr(got), None), "nlr_box_winner")
+    assert bool((got == -1).all())
+
+
+@pytest.mark.gpu
+def test_obj_mlp_stack_has_one_definition_and_two_binders():
+    """`objects.ObjMLP` (loaded tensors) and `training.TrainableObjMLP` (modules) bind the same `obj_mlp_forward`: with the same
+    weights every output is the same, bit for bit; a 1-D latent is the expanded one."""
+    from nerflidar_hip import training as ntrain
+    g = golden("obj_REF_small")
+    mc, _, cids, cfgs, sd = _scene(g)
+    cid = cids[0]
+    a = nobj.ObjMLP(f"obj_mlp_{cid}", cfgs[cid], sd, "cuda")
+    b = ntrain.TrainableObjMLP(cfgs[cid]).load_reference(sd, f"obj_mlp_{cid}.").cuda()
+    gen = torch.Generator().manual_seed(5)
+    n = 301
+    pts = (torch.rand(n, 3, generator=gen) * 2 - 1).cuda()
+    dirs = torch.nn.functional.normalize(torch.randn(n, 3, generator=gen), dim=-1).cuda()
+    lat = torch.randn(n, cfgs[cid].latent_size, generator=gen).cuda()
+    with torch.no_grad():
+        ra, rb = a.forward(pts, dirs, lat), b(pts, dirs, lat)
+        r1, re = a.forward(pts, dirs, lat[0]), a.forward(pts, dirs, lat[:1].expand(n, -1))
+    assert list(ra) == list(rb) == ["density", "semantic", "rgb"]
+    for k in ra:
+        assert torch.equal(ra[k], rb[k]), k
+        assert torch.equal(r1[k], re[k]), k
+    assert float(ra["density"].max()) > 0 and float(ra["rgb"].std()) > 0
