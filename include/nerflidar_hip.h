@@ -559,6 +559,14 @@ int nlr_prop_mlp_backward(const float *feat, const float *w1, const float *b1, c
  *     The forward materialises nothing of size [N, S, sample_n, L, C]; the backward one such tensor (the per-point feature
  *     gradients it hands to nlr_grid_encode_backward) in caller-provided scratch.  The sample positions carry no gradient
  *     (Model.stop_level_grad); rand_deg as in NlrRenderCfg; f32 grad table.
+ *     backward_rays: the gradient with respect to the RAYS instead, for pose refinement (ZI/train.py:199-221 moves origins,
+ *     directions, base_x and base_y by the refined pose; the loss reaches it through them, train.py:459-466): with
+ *     m = o + t d + lx bx + ly by the multisample position of render.py:147-164, d_origins = sum gm, d_directions = sum t gm,
+ *     d_base_x = sum lx gm, d_base_y = sum ly gm over the ray's samples, multisamples and levels, gm = d loss / d m through the
+ *     contraction (coord.py:51-63, position and footprint), the erf re-weighting (models.py:976) and the trilinear weights
+ *     (gridencoder.cu:137-197, kernel_input_backward :290-330).  tdist, radii and rand_deg are data.  Each output is [N, 3] f32,
+ *     OVERWRITTEN, and may be NULL.  No atomics: a fixed-order reduction per ray, bitwise repeatable.  Tables f32 / f16, level_dim
+ *     1, 2, 4, 8, every gridtype / align_corners / interp of the forward; anything else NLR_ERR_UNSUPPORTED.
  * ------------------------------------------------------------------------------------------ */
 int nlr_encode_features_forward(const NlrRays *rays, const float *tdist, uint32_t N, uint32_t S, uint32_t sample_n, uint32_t sample_m,
                                 float std_scale, const float *rand_deg, const NlrGridDesc *grid, uint32_t re_weights, float *features,
@@ -572,6 +580,10 @@ int nlr_encode_features_backward_ws(const NlrRays *rays, const float *tdist, uin
                                     float std_scale, const float *rand_deg, const NlrGridDesc *grid, uint32_t re_weights,
                                     const float *d_features, float *points_tmp, float *grad_tmp, float *grad_table, void *workspace,
                                     size_t workspace_bytes, void *stream);
+int nlr_encode_features_backward_rays(const NlrRays *rays, const float *tdist, uint32_t N, uint32_t S, uint32_t sample_n, uint32_t sample_m,
+                                      float std_scale, const float *rand_deg, const NlrGridDesc *grid, uint32_t re_weights,
+                                      const float *d_features /* [N*S, L*C] */, float *d_origins, float *d_directions, float *d_base_x,
+                                      float *d_base_y /* [N,3] f32, written, any may be NULL */, void *stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,201 @@
+// Ray gradient of the fused cast + encode operator (header section 9): d loss / d (origins, directions, base_x, base_y) from the
+// gradient of the features, for pose refinement (ZI/train.py:199-221: the refined pose moves exactly these tensors).
+//
+// The forward map is nlr_cast_one + nlr_erf_weight_fast + the trilinear gather of nlr_grid_level.h:
+//   m = o + t d + lx bx + ly by          (t, lx, ly, std: functions of tdist, radii, rand_deg - data)
+//   y = m or contract(m),  zs = std or cbrt(det J) std      (coord.py:51-63; the branch is m2 > 1)
+//   x01 = (y / 2 + 1) / 2,  f_l = (1/n) sum_j w_l(zs_j) tri_l(x01_j)
+// and per multisample and level, with upstream g_l, the chain is
+//   g_l . [ w_l dtri_l/dx dx/dm + tri_l dw_l/dzs dzs/dm ]
+// (second term only with re_weights on a contracted sample).  At a cell face, at m2 = 1 and at the clamp of the erf argument the
+// derivative is that of the branch the forward takes.
+//
+// One wave per ray.  Lane i walks the ray's (sample, multisample) pairs i, i + 64, ... and all levels of each, 8 * C gathers in flight
+// per level, and keeps the ray's 12 numbers in registers; an xor butterfly over the 64 lanes then sums them and lane 0 stores.  No
+// atomics: the order of every sum is fixed by (S, n, L) alone, so the result is bitwise repeatable and does not depend on the launch.
+#include "nlr_kernels.h"
+
+#include "nlr_cast.h"
+#include "nlr_grid_level.h"
+
+#define NLR_RAYS_PER_BLOCK 4u
+
+// d (sum_c gf[c] tri_c) / d x01[0..2] and the sum itself at one level, from the 8 corner values the forward gathers (the caller has
+// checked that the point lies inside the unit cube).
+template <typename T, int C, int MODE>
+__device__ __forceinline__ void nlr_level_grad_m(const GridParams &gp, uint32_t level, const Gauss &g, const float *__restrict__ gf,
+                                                 float (&dpos)[3], float &tri) {
+    const T *grid = (const T *)gp.table + (size_t)gp.offset[level] * C;
+    float pos[3];
+    uint32_t pg[3];
+    nlr_level_cell(gp, level, g, pg, pos);
+    float slope[3] = {1.0f, 1.0f, 1.0f};  // d (interpolation weight) / d (position in the cell)
+    if (gp.interp == 1) {
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            slope[d] = 6.0f * pos[d] * (1.0f - pos[d]);
+            pos[d] = pos[d] * pos[d] * (3.0f - 2.0f * pos[d]);
+        }
+    }
+    uint32_t idx[8];
+    nlr_corner_idx<MODE>(gp, level, pg, idx);
+    float s[8];  // corner values contracted with the upstream gradient
+#pragma unroll
+    for (int c8 = 0; c8 < 8; ++c8) {
+        float a = 0.0f;
+#pragma unroll
+        for (int c = 0; c < C; ++c) a = fmaf(gf[c], nlr_ld<T>(grid + (size_t)idx[c8] * C + c), a);
+        s[c8] = a;
+    }
+    const float wx[2] = {1 - pos[0], pos[0]}, wy[2] = {1 - pos[1], pos[1]}, wz[2] = {1 - pos[2], pos[2]};
+    float v = 0.0f, dx = 0.0f, dy = 0.0f, dz = 0.0f;
+#pragma unroll
+    for (int c8 = 0; c8 < 8; ++c8) {
+        const int ix = c8 & 1, iy = (c8 >> 1) & 1, iz = (c8 >> 2) & 1;
+        v = fmaf((wx[ix] * wy[iy]) * wz[iz], s[c8], v);
+        dx = fmaf((ix ? wy[iy] : -wy[iy]) * wz[iz], s[c8], dx);
+        dy = fmaf((iy ? wx[ix] : -wx[ix]) * wz[iz], s[c8], dy);
+        dz = fmaf((iz ? wx[ix] : -wx[ix]) * wy[iy], s[c8], dz);
+    }
+    const float scale = gp.scale[level];  // d (position on the level) / d x01
+    dpos[0] = dx * (slope[0] * scale);
+    dpos[1] = dy * (slope[1] * scale);
+    dpos[2] = dz * (slope[2] * scale);
+    tri = v;
+}
+
+template <typename T, int C>
+__global__ void __launch_bounds__(256) nlr_encode_rays_kernel(CastParams cp, GridParams gp, int re_weights, const float *__restrict__ d_feat,
+                                                              float *__restrict__ d_o, float *__restrict__ d_d, float *__restrict__ d_bx,
+                                                              float *__restrict__ d_by) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t ray = blockIdx.x * NLR_RAYS_PER_BLOCK + (threadIdx.x >> 6);
+    if (ray >= cp.N) return;  // (a whole wave: the kernel has no barrier)
+    float o[3], d[3], bx[3], by[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        o[c] = cp.origins[(size_t)ray * 3 + c];
+        d[c] = cp.directions[(size_t)ray * 3 + c];
+        bx[c] = cp.base_x[(size_t)ray * 3 + c];
+        by[c] = cp.base_y[(size_t)ray * 3 + c];
+    }
+    const float radius = cp.radii[ray];
+    const float inv_n = 1.0f / (float)cp.n;
+    const uint32_t LC = gp.L * C;
+    float acc[12];  // d_o | d_d | d_bx | d_by
+#pragma unroll
+    for (int i = 0; i < 12; ++i) acc[i] = 0.0f;
+    const uint32_t items = cp.S * cp.n;
+    for (uint32_t it = lane; it < items; it += 64u) {
+        const uint32_t k = it / cp.n, j = it - k * cp.n;
+        const float t0 = cp.tdist[(size_t)ray * (cp.S + 1) + k], t1 = cp.tdist[(size_t)ray * (cp.S + 1) + k + 1];
+        CastTaps tp;
+        const Gauss g = nlr_cast_one(cp, ray, k, j, t0, t1, o, d, bx, by, radius, nullptr, &tp);
+        if (nlr_outside_unit_cube(g)) continue;  // encodes as zeros on every level: no gradient
+        const float inv_s8 = __frsqrt_rn(8.0f * (g.zs * g.zs));
+        const bool footprint = re_weights && tp.contracted;  // zs depends on the position only through the contraction
+        const float *gf = d_feat + ((size_t)ray * cp.S + k) * LC;
+        float gx[3] = {0.0f, 0.0f, 0.0f}, gzs = 0.0f;  // d / d x01, d / d g.zs of this multisample's share of the loss
+        for (uint32_t l = 0; l < gp.L; ++l) {
+            float up[C];
+#pragma unroll
+            for (int c = 0; c < C; ++c) up[c] = gf[l * C + c] * inv_n;
+            float dp[3], tri;
+            const uint32_t mode = gp.mode[l];
+            if (mode == 0) nlr_level_grad_m<T, C, 0>(gp, l, g, up, dp, tri);
+            else if (mode == 1) nlr_level_grad_m<T, C, 1>(gp, l, g, up, dp, tri);
+            else nlr_level_grad_m<T, C, 2>(gp, l, g, up, dp, tri);
+            float w = 1.0f;
+            if (re_weights) {
+                const float u = inv_s8 * gp.inv_gsize[l];  // nlr_erf_weight_fast: w = erf(min(u, 1e10)), u = 1 / (sqrt(8) zs G)
+                w = erff(fminf(u, 1e10f));
+                // dw/dzs = 2/sqrt(pi) exp(-u^2) du/dzs, du/dzs = -u / zs; nothing beyond the cap
+                if (footprint && u < 1e10f) gzs = fmaf(tri, (1.1283791670955126f * expf(-(u * u))) * (-u / g.zs), gzs);
+            }
+#pragma unroll
+            for (int c = 0; c < 3; ++c) gx[c] = fmaf(w, dp[c], gx[c]);
+        }
+        // x01 = (y / 2 + 1) / 2, g.zs = zs / 2
+        float gm[3] = {gx[0] * 0.25f, gx[1] * 0.25f, gx[2] * 0.25f};
+        if (tp.contracted) {
+            // y = sc(m2) p, sc = (2 sqrt(m2) - 1) / m2; zs = cbrt(det) std, det = sc^2 / m2; m2 = |p|^2 (its clamp at eps is far below 1)
+            const float m2 = tp.m2, sq = sqrtf(m2);
+            const float sc = (2.0f * sq - 1.0f) / m2;
+            const float dsc = (1.0f / m2 - 1.0f / sq) / m2;  // d sc / d m2 = m2^-2 - m2^-3/2
+            const float gy_p = (gm[0] * tp.p[0] + gm[1] * tp.p[1]) + gm[2] * tp.p[2];
+            float along = gy_p * dsc;  // coefficient of d m2 / d p = 2 p
+            if (footprint) {
+                // d zs / d m2 = zs / (3 det) d det / d m2, d det / d m2 = (2 sc dsc - sc^2 / m2) / m2
+                const float det = (1.0f / m2) * (sc * sc);
+                const float ddet = (2.0f * sc * dsc - (sc * sc) / m2) / m2;
+                const float zs = cbrtf(det) * tp.std;
+                along = fmaf(gzs * 0.5f, (zs / (3.0f * det)) * ddet, along);
+            }
+#pragma unroll
+            for (int c = 0; c < 3; ++c) gm[c] = fmaf(2.0f * along, tp.p[c], sc * gm[c]);
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            acc[c] += gm[c];
+            acc[3 + c] = fmaf(tp.t, gm[c], acc[3 + c]);
+            acc[6 + c] = fmaf(tp.lx, gm[c], acc[6 + c]);
+            acc[9 + c] = fmaf(tp.ly, gm[c], acc[9 + c]);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 12; ++i) acc[i] = nlr_wave_sum(acc[i]);
+    if (lane == 0) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            if (d_o) d_o[(size_t)ray * 3 + c] = acc[c];
+            if (d_d) d_d[(size_t)ray * 3 + c] = acc[3 + c];
+            if (d_bx) d_bx[(size_t)ray * 3 + c] = acc[6 + c];
+            if (d_by) d_by[(size_t)ray * 3 + c] = acc[9 + c];
+        }
+    }
+}
+
+extern "C" int nlr_encode_features_backward_rays(const NlrRays *rays, const float *tdist, uint32_t N, uint32_t S, uint32_t sample_n,
+                                                 uint32_t sample_m, float std_scale, const float *rand_deg, const NlrGridDesc *grid,
+                                                 uint32_t re_weights, const float *d_features, float *d_origins, float *d_directions,
+                                                 float *d_base_x, float *d_base_y, void *stream) {
+    if (N == 0) return NLR_OK;
+    NLR_CHECK_ARG(grid && grid->table && grid->offsets && tdist && d_features, "encode_features_backward_rays: NULL argument");
+    if (grid->level_dim != 1 && grid->level_dim != 2 && grid->level_dim != 4 && grid->level_dim != 8)
+        NLR_FAIL(NLR_ERR_UNSUPPORTED, "encode_features_backward_rays: level_dim = %u, the kernel has instances for 1, 2, 4 and 8", grid->level_dim);
+    if (grid->table_dtype != 0 && grid->table_dtype != 1)
+        NLR_FAIL(NLR_ERR_UNSUPPORTED, "encode_features_backward_rays: table_dtype = %d, the kernel reads f32 (0) and f16 (1) tables",
+                 (int)grid->table_dtype);
+    CastParams cp;
+    GridParams gp;
+    int rc = nlr_fill_cast_params(&cp, rays, tdist, rand_deg, N, S, sample_n, sample_m, std_scale);
+    if (rc) return rc;
+    rc = nlr_fill_grid_params(&gp, grid->table, grid->table_dtype, grid->offsets, grid->num_levels, grid->level_dim, grid->log2_per_level_scale,
+                              grid->base_resolution, grid->gridtype, (int)grid->align_corners, grid->interp);
+    if (rc) return rc;
+    // (a lane's pair counter advances by 64 past the last pair before it stops)
+    NLR_CHECK_ARG((uint64_t)S * sample_n + 64 < (1ull << 32), "encode_features_backward_rays: S * sample_n = %llu does not fit the 32-bit pair counter",
+                  (unsigned long long)S * sample_n);
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid_dim((N + NLR_RAYS_PER_BLOCK - 1) / NLR_RAYS_PER_BLOCK), block(64 * NLR_RAYS_PER_BLOCK);
+#define NLR_RAYS(T, C) \
+    hipLaunchKernelGGL((nlr_encode_rays_kernel<T, C>), grid_dim, block, 0, st, cp, gp, (int)re_weights, d_features, d_origins, d_directions, d_base_x, d_base_y)
+    if (gp.table_dtype == 0) {
+        switch (gp.C) {
+            case 1: NLR_RAYS(float, 1); break;
+            case 2: NLR_RAYS(float, 2); break;
+            case 4: NLR_RAYS(float, 4); break;
+            default: NLR_RAYS(float, 8); break;
+        }
+    } else {
+        switch (gp.C) {
+            case 1: NLR_RAYS(__half, 1); break;
+            case 2: NLR_RAYS(__half, 2); break;
+            case 4: NLR_RAYS(__half, 4); break;
+            default: NLR_RAYS(__half, 8); break;
+        }
+    }
+#undef NLR_RAYS
+    NLR_LAUNCH_CHECK("nlr_encode_rays_kernel");
+    return NLR_OK;
+}

@@ -16,20 +16,34 @@ __device__ __forceinline__ float nlr_ld<float>(const float *p) { return *p; }
 template <>
 __device__ __forceinline__ float nlr_ld<__half>(const __half *p) { return __half2float(*p); }
 
-// Trilinear interpolation of C channels at one level (gridencoder.cu:137-197); acc += w_erf * value.
-template <typename T, int C, int MODE>
-__device__ __forceinline__ void nlr_level_accum_m(const GridParams &gp, uint32_t level, const Gauss &g, float werf, float (&acc)[C]) {
-    if ((g.x0 < 0 || g.x0 > 1) || (g.x1 < 0 || g.x1 > 1) || (g.x2 < 0 || g.x2 > 1)) return;  // zeros
-    const T *grid = (const T *)gp.table + (size_t)gp.offset[level] * C;
+// gridencoder.cu:124-135: a point outside [0,1]^3 encodes as zeros on every level
+__device__ __forceinline__ bool nlr_outside_unit_cube(const Gauss &g) {
+    return (g.x0 < 0 || g.x0 > 1) || (g.x1 < 0 || g.x1 > 1) || (g.x2 < 0 || g.x2 > 1);
+}
+// The cell of a point on one level (gridencoder.cu:141-152): integer cell coordinates pg and the position inside the cell, pos in
+// [0, 1), BEFORE the smoothstep of interp = 1.
+__device__ __forceinline__ void nlr_level_cell(const GridParams &gp, uint32_t level, const Gauss &g, uint32_t (&pg)[3], float (&pos)[3]) {
     const float scale = gp.scale[level];
     const float half = gp.align_corners ? 0.0f : 0.5f;
-    float pos[3] = {fmaf(g.x0, scale, half), fmaf(g.x1, scale, half), fmaf(g.x2, scale, half)};
-    uint32_t pg[3];
+    pos[0] = fmaf(g.x0, scale, half), pos[1] = fmaf(g.x1, scale, half), pos[2] = fmaf(g.x2, scale, half);
 #pragma unroll
     for (int d = 0; d < 3; ++d) {
         pg[d] = (uint32_t)floorf(pos[d]);
         pos[d] -= (float)pg[d];
-        if (gp.interp == 1) pos[d] = pos[d] * pos[d] * (3.0f - 2.0f * pos[d]);
+    }
+}
+
+// Trilinear interpolation of C channels at one level (gridencoder.cu:137-197); acc += w_erf * value.
+template <typename T, int C, int MODE>
+__device__ __forceinline__ void nlr_level_accum_m(const GridParams &gp, uint32_t level, const Gauss &g, float werf, float (&acc)[C]) {
+    if (nlr_outside_unit_cube(g)) return;  // zeros
+    const T *grid = (const T *)gp.table + (size_t)gp.offset[level] * C;
+    float pos[3];
+    uint32_t pg[3];
+    nlr_level_cell(gp, level, g, pg, pos);
+    if (gp.interp == 1) {
+#pragma unroll
+        for (int d = 0; d < 3; ++d) pos[d] = pos[d] * pos[d] * (3.0f - 2.0f * pos[d]);
     }
     uint32_t idx[8];
     nlr_corner_idx<MODE>(gp, level, pg, idx);

@@ -87,6 +87,28 @@ def refined_tracks_from_checkpoint(ckpt_dir_or_file, tracks, step=None) -> np.nd
     return out
 
 
+POSENET_PREFIX = "posenet_ckpt_"  # train.py:96,567-574
+
+
+def save_posenet(ckpt_dir, posenet, step: int, optimizer=None) -> str:
+    """`posenet_ckpt_<step>.ckpt` as train.py:567-574 writes it: the state dict of LearnPose (`r`, `t`, and `init_c2w` if it has one)."""
+    return save_checkpoint(ckpt_dir, posenet.state_dict(), step, optimizer_state=None if optimizer is None else optimizer.state_dict(),
+                           prefix=POSENET_PREFIX)
+
+
+def restore_posenet(ckpt_dir_or_file, posenet, step=None) -> int:
+    """Loads the newest (or the given step's) `posenet_ckpt_*` into `posenet` (train.py:96) and returns its step.  A pose count
+    that does not match the checkpoint's raises ValueError."""
+    sd, at = load_checkpoint(ckpt_dir_or_file, step, prefix=POSENET_PREFIX)
+    sd = {(k[len("module."):] if k.startswith("module.") else k): torch.from_numpy(np.ascontiguousarray(v)) for k, v in sd.items()}
+    want = {k: tuple(v.shape) for k, v in posenet.state_dict().items()}
+    got = {k: tuple(v.shape) for k, v in sd.items()}
+    if want != got:
+        raise ValueError(f"posenet checkpoint holds {got}, the PoseNet needs {want}")
+    posenet.load_state_dict(sd)
+    return at
+
+
 def split_state_dict(sd: Dict[str, np.ndarray]) -> Tuple[Dict[str, np.ndarray], List[str]]:
     """(parameters of the fused path, keys that belong to branches outside it)."""
     keep, ignored = {}, []

@@ -167,3 +167,34 @@ def supervise(batch: Dict[str, torch.Tensor], rot_seed: int = 0, scale_factor: f
         keep = torch.arange(n, device=ones.device) < n - colourless
         out.update(mask_rgb=keep, sem_mask=keep)
     return out
+
+
+def perturb_frames(batch: Dict[str, torch.Tensor], n_frames: int, seed: int, rot: float = 0.01, trans: float = 0.002):
+    """Gives the rays of `batch` to `n_frames` frames (ray i belongs to frame i mod n_frames: `glo_idx`) and moves every frame by
+    a seeded pose error: a rotation of up to `rot` rad per axis-angle component and a translation of up to `trans` scene units per
+    axis.  Returns (perturbed batch, r_true [n_frames, 3], t_true [n_frames, 3]): the correction a `training.PoseNet` with t_ratio
+    = 1 has to learn, i.e. `training.refine_batch(perturbed, pose(r_true, t_true))` gives the rays of `batch` back.  Supervision keys
+    stay with their rays."""
+    from .training import PoseNet, POSE_RAY_KEYS
+    dev = batch["origins"].device
+    n = batch["origins"].shape[0]
+    true = PoseNet(n_frames, num_lidars=0)
+    with torch.no_grad():
+        true.r.copy_(torch.from_numpy(synth.uniform(seed, 9400, (n_frames, 3), -rot, rot)))
+        true.t.copy_(torch.from_numpy(synth.uniform(seed, 9401, (n_frames, 3), -trans, trans)))
+        ids = torch.arange(n) % n_frames
+        P = true(ids).to(dev)
+        out = dict(batch)
+        out["origins"] = batch["origins"].reshape(n, 3) - P[:, :3, 3]
+        for k in POSE_RAY_KEYS[1:] + ("viewdirs",):                      # v = R^T v_true
+            out[k] = (batch[k].reshape(n, 3, 1) * P[:, :3, :3]).sum(1)
+        out["glo_idx"] = ids.float()[:, None].to(dev)
+    return out, true.r.detach().clone(), true.t.detach().clone()
+
+
+def hit_point_error_m(refined: Dict[str, torch.Tensor], true: Dict[str, torch.Tensor], scale_factor: float = 1.0 / 250.0) -> float:
+    """Mean distance in metres between where the rays of `refined` and the rays of `true` put their supervised depth: the pose error
+    as the scene sees it (rotation and translation in one unit)."""
+    n = true["origins"].shape[0]
+    hit = lambda b: b["origins"].reshape(n, 3) + true["depth"].reshape(n, 1) * b["directions"].reshape(n, 3)
+    return float((hit(refined) - hit(true)).norm(dim=-1).mean() / scale_factor)

@@ -66,7 +66,22 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--colourless-fraction", type=float, default=0.0,
                     help="the last round(F * rays) rays of every batch carry no colour or semantic supervision (mask_rgb = sem_mask = 0, as "
                          "train.py:316-320 sets them for LiDAR rays) and skip the view MLP (training_step(color_rays=..)); 0: off")
+    ap.add_argument("--pose-refine", action="store_true",
+                    help="pose refinement (Config.pose_refine, train.py:199-221): the rays of every batch belong to --pose-frames frames whose "
+                         "poses carry a seeded error (scene.perturb_frames); a PoseNet learns the correction over the whole run and the "
+                         "summary reports the pose error before and after")
+    ap.add_argument("--pose-frames", type=int, default=4)
+    ap.add_argument("--pn-lr-init", type=float, default=4e-5, help="configs.py:153")
+    ap.add_argument("--pn-lr-final", type=float, default=2e-6, help="configs.py:154")
     return ap
+
+
+def pose_error(posenet, seed: int, frames: int, dev, scale_factor: float, rays: int = 4096) -> float:
+    """Hit-point error in metres (scene.hit_point_error_m) of a held-out batch under the PoseNet's current correction."""
+    true = nscene.supervise(nscene.random_lidar_rays(rays, seed, 0, dev, seed, scale_factor), seed, scale_factor)
+    bad, _, _ = nscene.perturb_frames(true, frames, seed)
+    with torch.no_grad():
+        return nscene.hit_point_error_m(ntrain.refine_batch(bad, posenet(bad["glo_idx"])), true, scale_factor)
 
 
 def main(argv=None) -> int:
@@ -87,6 +102,14 @@ def main(argv=None) -> int:
     tm = ntrain.TrainableModel(mc, fused_mlp=bool(a.fused), fused_wgrad=a.fused_wgrad).to(dev)
     delay = a.lr_delay_steps if a.lr_delay_steps is not None else max(a.steps // 5, 1)
     opt, lr_fn = ntrain.create_optimizer(tm, a.lr_init, a.lr_final, a.steps, delay)
+    pose_kw, posenet = {}, None
+    if a.pose_refine:  # the window is the whole run: (0, steps + 1), as nuscenes_single.gin:6-7 starts it at step 0
+        window = (0, a.steps + 1)
+        posenet, pn_opt, pn_lr_fn = ntrain.create_posenet(a.pose_frames, 0, *window, pn_lr_init=a.pn_lr_init, pn_lr_final=a.pn_lr_final, t_ratio=1.0,
+                                                          lr_delay_steps=delay)
+        posenet = posenet.to(dev)
+        pose_kw = dict(posenet=posenet, pn_optimizer=pn_opt, pn_lr_fn=pn_lr_fn, pose_window=window)
+        pose_err_before = pose_error(posenet, a.seed, a.pose_frames, dev, a.scale_factor)
     t0 = time.time()
     log = []
     for step in range(1, a.steps + 1):                                     # train.py:180: steps count from 1
@@ -94,9 +117,11 @@ def main(argv=None) -> int:
             g["lr"] = lr_fn(step)                                          # train.py:187-190
         batch = nscene.supervise(nscene.random_lidar_rays(a.rays, a.seed, step, dev, a.seed, a.scale_factor), a.seed, a.scale_factor,
                                  colourless=colourless)
+        if posenet is not None:
+            batch, _, _ = nscene.perturb_frames(batch, a.pose_frames, a.seed)
         train_frac = float(np.clip((step - 1) / max(a.steps - 1, 1), 0, 1))  # train.py:184
         terms = ntrain.training_step(tm, opt, batch, train_frac=train_frac, randomized=True, hash_decay_mult=a.hash_decay,
-                                     depth_lam=a.depth_lam, sem_lam=a.sem_lam, as_tensors=True, color_rays=color_rays)
+                                     depth_lam=a.depth_lam, sem_lam=a.sem_lam, as_tensors=True, color_rays=color_rays, step=step, **pose_kw)
         if step % a.log_every == 0 or step == 1 or step == a.steps:          # the only host read of the loop
             torch.cuda.synchronize()
             rec = dict(step=step, lr=lr_fn(step), elapsed_s=round(time.time() - t0, 1), **{k: round(float(v), 6) for k, v in terms.items()})
@@ -115,6 +140,10 @@ def main(argv=None) -> int:
     summary = dict(workload=a.workload, log2_hashmap=a.log2_hashmap, steps=a.steps, rays_per_step=a.rays, fused=bool(a.fused), fused_wgrad=a.fused_wgrad,
                    colourless_fraction=a.colourless_fraction, train_seconds=round(train_s, 1), train_rays_per_s=round(a.steps * a.rays / train_s), checkpoint=path,
                    checkpoint_bytes=os.path.getsize(path), restored_step=step, held_out_sweep=ev, final_terms=log[-1])
+    if posenet is not None:
+        nckpt.save_posenet(a.out, posenet, a.steps, pn_opt)
+        summary["pose_refine"] = dict(frames=a.pose_frames, hit_point_error_m_before=round(pose_err_before, 4),
+                                      hit_point_error_m_after=round(pose_error(posenet, a.seed, a.pose_frames, dev, a.scale_factor), 4))
     print(json.dumps(summary), flush=True)
     with open(os.path.join(a.out, "train_summary.json"), "w") as f:
         json.dump(dict(summary=summary, log=log), f, indent=1)

@@ -76,13 +76,18 @@ class _Composite(torch.autograd.Function):
                                                    opaque, bg, _lib.ptr(g_rgb), _lib.ptr(g_depth), _lib.ptr(g_sem), _lib.ptr(g_int), _lib.ptr(g_acc),
                                                    _lib.ptr(g_w), _lib.ptr(dd), _lib.ptr(d_rgb), _lib.ptr(d_sem), _lib.ptr(d_int), _lib.current_stream())
         _lib.check(rc, "nlr_composite_backward")
-        return (dd, None, None, None if d_rgb is None else d_rgb.permute(1, 2, 0), None if d_sem is None else d_sem.permute(1, 2, 0), d_int,
+        d_dirs = None
+        if ctx.needs_input_grad[2]:
+            # dirs enters as |d| in density * dt * |d| only (render.py:176-178): dL/d|d| = sum_s dd_s density_s / |d|, d|d|/dd = d / |d|
+            d_dirs = dr * ((dd * d).sum(-1) / (dr * dr).sum(-1))[:, None]
+        return (dd, None, d_dirs, None if d_rgb is None else d_rgb.permute(1, 2, 0), None if d_sem is None else d_sem.permute(1, 2, 0), d_int,
                 None, None)
 
 
 def volumetric_render(density, tdist, dirs, rgbs, semantic=None, intensity=None, opaque_background=True, bg=1.0) -> Dict[str, torch.Tensor]:
     """Differentiable `weights = compute_alpha_weights(...)`, `volumetric_rendering(...)` with the reference's keys
-    (`rgb`, `depth`, `semantic`, `intensity`, `acc`) plus `weights` [N,S].  Gradients: density, rgbs, semantic, intensity."""
+    (`rgb`, `depth`, `semantic`, `intensity`, `acc`) plus `weights` [N,S].  Gradients: density, rgbs, semantic, intensity, and
+    `dirs` when it requires one (pose refinement), computed from the density gradient the backward kernel returns."""
     rgb, depth, sem, inten, acc, w = _Composite.apply(density, tdist, dirs, rgbs, semantic, intensity, opaque_background, bg)
     out = {"rgb": rgb, "depth": depth, "acc": acc, "weights": w}
     if semantic is not None:
@@ -180,11 +185,13 @@ def encode_features(encoder, means: torch.Tensor, stds: torch.Tensor, re_weights
 class _EncodeFeatures(torch.autograd.Function):
     """cast_rays -> contraction -> GridEncoder -> erf re-weighting -> mean over the multisamples (ZI/models.py:965-979) as one
     operator: `nlr_encode_features_forward` (the fused kernel of the inference path) and `nlr_encode_features_backward`
-    (per-point feature gradients in one kernel, then the grid operator's scatter).  Differentiable with respect to the table only: sample positions carry
-    no gradient in training (`Model.stop_level_grad`)."""
+    (per-point feature gradients in one kernel, then the grid operator's scatter).  Differentiable with respect to the table, and -
+    when `encode_features_fused` hands over `rays` = the batch's origins, directions, base_x, base_y because one of them requires a
+    gradient (pose refinement) - with respect to those four through `nlr_encode_features_backward_rays`.  tdist carries no gradient
+    in training (`Model.stop_level_grad`)."""
 
     @staticmethod
-    def forward(ctx, table, encoder, batch, tdist, sample_n, sample_m, std_scale, rand_deg, re_weights):
+    def forward(ctx, table, encoder, batch, tdist, sample_n, sample_m, std_scale, rand_deg, re_weights, *rays):
         from .models import _RAY_KEYS
         n, S = tdist.shape[0], tdist.shape[1] - 1
         dev = tdist.device
@@ -196,6 +203,7 @@ class _EncodeFeatures(torch.autograd.Function):
         tab = table.detach().contiguous()
         ctx.args = (encoder, keep, td, rd, int(sample_n), int(sample_m), float(std_scale), int(bool(re_weights)))
         ctx.save_for_backward(tab)
+        ctx.ray_shapes = [(t.shape, t.dtype) for t in rays]
         feats = torch.empty(n * S, encoder.output_dim, device=dev)
         rays, gd = _EncodeFeatures._descs(encoder, keep, tab)
         with torch.cuda.device(dev):
@@ -225,25 +233,47 @@ class _EncodeFeatures(torch.autograd.Function):
         encoder, keep, td, rd, sample_n, sample_m, std_scale, re_w = ctx.args
         n, S = td.shape[0], td.shape[1] - 1
         g = g.reshape(n * S, -1).contiguous().float()
-        grad = torch.zeros(tab.shape, device=tab.device, dtype=torch.float32)
-        pts = torch.empty(n * S * sample_n, 3, device=tab.device)                      # scratch: unit-cube positions of the multisamples
-        gpt = torch.empty(n * S * sample_n, encoder.output_dim, device=tab.device)     # scratch: their feature gradients
         rays, gd = _EncodeFeatures._descs(encoder, keep, tab)
-        from .gridencoder import backward_workspace
+        d_table = None
+        if not ctx.ray_shapes or ctx.needs_input_grad[0]:  # (with rays: skipped when the table wants none - pose-only steps on a frozen field)
+            grad = torch.zeros(tab.shape, device=tab.device, dtype=torch.float32)
+            pts = torch.empty(n * S * sample_n, 3, device=tab.device)                      # scratch: unit-cube positions of the multisamples
+            gpt = torch.empty(n * S * sample_n, encoder.output_dim, device=tab.device)     # scratch: their feature gradients
+            from .gridencoder import backward_workspace
+            with torch.cuda.device(tab.device):
+                ws = backward_workspace(n * S * sample_n, tab.shape[1], encoder.num_levels, float(np.log2(encoder.per_level_scale)),
+                                        int(encoder.base_resolution), encoder._offsets_host, encoder.gridtype_id, encoder.align_corners, tab.device)
+                _lib.check(_lib.lib().nlr_encode_features_backward_ws(C.byref(rays), _lib.ptr(td), n, S, sample_n, sample_m, std_scale, _lib.ptr(rd),
+                                                                      C.byref(gd), re_w, _lib.ptr(g), _lib.ptr(pts), _lib.ptr(gpt), _lib.ptr(grad),
+                                                                      _lib.ptr(ws), 0 if ws is None else ws.numel(), _lib.current_stream()),
+                           "nlr_encode_features_backward")
+            d_table = grad.to(tab.dtype)
+        if not ctx.ray_shapes:
+            return (d_table,) + (None,) * 8
+        if not any(ctx.needs_input_grad[9:13]):  # (the batch's viewdirs alone require a gradient)
+            return (d_table,) + (None,) * 12
+        d_rays = [torch.empty(n, 3, device=tab.device) if w else None for w in ctx.needs_input_grad[9:13]]
         with torch.cuda.device(tab.device):
-            ws = backward_workspace(n * S * sample_n, tab.shape[1], encoder.num_levels, float(np.log2(encoder.per_level_scale)),
-                                    int(encoder.base_resolution), encoder._offsets_host, encoder.gridtype_id, encoder.align_corners, tab.device)
-            _lib.check(_lib.lib().nlr_encode_features_backward_ws(C.byref(rays), _lib.ptr(td), n, S, sample_n, sample_m, std_scale, _lib.ptr(rd),
-                                                                  C.byref(gd), re_w, _lib.ptr(g), _lib.ptr(pts), _lib.ptr(gpt), _lib.ptr(grad),
-                                                                  _lib.ptr(ws), 0 if ws is None else ws.numel(), _lib.current_stream()),
-                       "nlr_encode_features_backward")
-        return (grad.to(tab.dtype),) + (None,) * 8
+            _lib.check(_lib.lib().nlr_encode_features_backward_rays(C.byref(rays), _lib.ptr(td), n, S, sample_n, sample_m, std_scale, _lib.ptr(rd),
+                                                                    C.byref(gd), re_w, _lib.ptr(g), *[_lib.ptr(t) for t in d_rays],
+                                                                    _lib.current_stream()), "nlr_encode_features_backward_rays")
+        return (d_table,) + (None,) * 8 + tuple(None if t is None else t.reshape(shape).to(dtype) for t, (shape, dtype) in zip(d_rays, ctx.ray_shapes))
 
 
 def encode_features_fused(encoder, batch, tdist, sample_n: int = 7, sample_m: int = 3, std_scale: float = 0.35, rand_deg=None,
                           re_weights: bool = True) -> torch.Tensor:
-    """[N, S, L*C] features of the intervals of `tdist`: `cast_contract` + `encode_features` in one kernel each way."""
-    return _EncodeFeatures.apply(encoder.embeddings, encoder, batch, tdist, sample_n, sample_m, std_scale, rand_deg, re_weights)
+    """[N, S, L*C] features of the intervals of `tdist`: `cast_contract` + `encode_features` in one kernel each way.  Ray tensors
+    that require a gradient (`rays_require_grad`) get one; otherwise the calls are the ones of a batch of plain data."""
+    rays = tuple(batch[k] for k in POSE_RAY_KEYS) if rays_require_grad(batch) else ()
+    return _EncodeFeatures.apply(encoder.embeddings, encoder, batch, tdist, sample_n, sample_m, std_scale, rand_deg, re_weights, *rays)
+
+
+POSE_RAY_KEYS = ("origins", "directions", "base_x", "base_y")  # what the encode's ray gradient reaches (viewdirs: the view MLP's input)
+
+
+def rays_require_grad(batch) -> bool:
+    """Does the loss have to reach the batch's ray tensors (pose refinement, train.py:207-221)?"""
+    return torch.is_grad_enabled() and any(isinstance(batch.get(k), torch.Tensor) and batch[k].requires_grad for k in POSE_RAY_KEYS + ("viewdirs",))
 
 
 # ---- fused NerfMLP for training: nlr_mlp_train_forward / nlr_mlp_train_backward (csrc/nlr_mlp_train.hip) ---------------------------
@@ -372,7 +402,28 @@ class _FusedMLP(torch.autograd.Function):
                 off += p.numel()
         else:
             grads = _wgrad_bmm(level, M, f, e, acts, gacts, Mc)
-        return (d_feat, None, None) + tuple(grads)
+        d_enc = _enc_grad(level, gacts, Mc, e) if ctx.needs_input_grad[1] else None
+        return (d_feat, d_enc, None) + tuple(grads)
+
+
+def _enc_grad(level, gacts, M_color, e):
+    """d loss / d enc [N, 32] of the fused NerfMLP from what its backward saved: for every Linear that reads the direction encoding
+    (view layer 0, and the layer behind the skip concatenation), the pre-activation gradient summed over the ray's samples in f32,
+    times that layer's weight columns for `enc` (the bf16 values the kernels multiplied with).  Rays beyond M_color rows ran no view
+    MLP: zeros."""
+    S, E = level._S, level.cfg.dim_dir_enc
+    n_color = M_color // S
+    d_enc = torch.zeros_like(e)
+    params = level._mlp_params()
+    for i, l in enumerate(level._plan.linears):
+        col = 0
+        for src, _, n in l.blocks:
+            if src == 2 and n_color:
+                gsum = gacts[:M_color, l.g_col:l.g_col + l.n_out].float().reshape(n_color, S, l.n_out).sum(1)
+                w = params[2 * i].detach()[:, col:col + E].to(torch.bfloat16).float()
+                d_enc[:n_color, :E] += gsum @ w
+            col += n
+    return d_enc
 
 
 class _Linear(NamedTuple):
@@ -421,7 +472,10 @@ class TrainableNerfLevel(torch.nn.Module):
 
     def __init__(self, cfg, table_std: float = 1e-4, fused_mlp: bool = False, fused_wgrad: bool = False):
         """fused_mlp: run the Linear stack through nlr_mlp_train_forward / _backward (bf16 MFMA chains, f32 accumulation) instead
-        of torch Linear modules; parameters, their names and their gradients are the same objects either way.
+        of torch Linear modules; parameters, their names and their gradients are the same objects either way.  It also chooses the
+        encode: the fused cast + encode operator with it, `cast_contract` + `GridEncoder` without - except for a batch whose ray
+        tensors require a gradient (`rays_require_grad`), which runs the fused operator on the fp32 model too, because only that
+        operator has a ray gradient (its features differ from the unfused route's by a few ulp).
         fused_wgrad (needs fused_mlp): the weight and bias gradients from nlr_mlp_train_wgrad (one MFMA kernel, f32 accumulation
         over all of M, bit-reproducible) instead of split-K library GEMMs."""
         super().__init__()
@@ -432,7 +486,9 @@ class TrainableNerfLevel(torch.nn.Module):
         self.fused_mlp = bool(fused_mlp)
         self.fused_wgrad = bool(fused_wgrad)
         self._wgrad_ws = {}  # device -> workspace of nlr_mlp_train_wgrad, allocated once
-        self.fused_encode = bool(fused_mlp)  # cast + encode + re-weight + mean as one operator (encode_features_fused)
+        # cast + encode + re-weight + mean as one operator (encode_features_fused).  Whatever this says, a batch whose ray tensors
+        # require a gradient (pose refinement; viewdirs alone included) takes that operator: `cast_contract` carries no gradient
+        self.fused_encode = bool(fused_mlp)
         self._plan = None
         self._color_rays = None  # set by forward(color_rays=..) for _FusedMLP, like _S
         if self.fused_mlp and cfg.use_semantic and cfg.no_sem_layer:
@@ -476,7 +532,7 @@ class TrainableNerfLevel(torch.nn.Module):
         F = torch.nn.functional
         cfg = self.cfg
         nc = _check_color_rays(color_rays, tdist.shape[0])
-        if self.fused_encode:
+        if self.fused_encode or rays_require_grad(batch):  # (the ray gradient exists on the fused operator only)
             feats = encode_features_fused(self.encoder, batch, tdist, sample_n, sample_m, rand_deg=rand_deg, re_weights=cfg.re_weights)
         else:
             means, stds = cast_contract(batch, tdist, sample_n, sample_m, rand_deg=rand_deg)
@@ -531,8 +587,7 @@ class TrainableNerfLevel(torch.nn.Module):
         self._S = S
         params = self._mlp_params()
         assert sum(p.numel() for p in params) == self._plan.n_params
-        enc = torch.zeros(n, 32, device=feats.device)
-        enc[:, :cfg.dim_dir_enc] = _pos_enc(batch["viewdirs"].reshape(n, 3).float(), cfg.deg_view)
+        enc = torch.nn.functional.pad(_pos_enc(batch["viewdirs"].reshape(n, 3).float(), cfg.deg_view), (0, 32 - cfg.dim_dir_enc))
         density, rgb, sem, inten = _FusedMLP.apply(feats.reshape(n * S, -1), enc, self, *params)
         out = {"density": density.reshape(n, S), "rgb": rgb.reshape(3, n, S).permute(1, 2, 0)}
         if cfg.use_semantic:
@@ -585,7 +640,8 @@ class TrainablePropLevel(torch.nn.Module):
 
     def __init__(self, cfg, fused: bool = True):
         """fused: the density network through `nlr_prop_mlp_forward` / `_backward` instead of two library GEMMs with 6-8 wide
-        operands; same parameters, same gradients (fp32 both ways)."""
+        operands; same parameters, same gradients (fp32 both ways).  A batch whose ray tensors require a gradient takes the fused
+        encode either way (`rays_require_grad`)."""
         super().__init__()
         nn = torch.nn
         self.cfg, self.fused = cfg, bool(fused)
@@ -595,7 +651,7 @@ class TrainablePropLevel(torch.nn.Module):
     load_reference = TrainableNerfLevel.load_reference
 
     def forward(self, batch, tdist, sample_n: int = 7, sample_m: int = 3, rand_deg=None) -> Dict[str, torch.Tensor]:
-        if self.fused:
+        if self.fused or rays_require_grad(batch):  # (the ray gradient exists on the fused operator only)
             feats = encode_features_fused(self.encoder, batch, tdist, sample_n, sample_m, rand_deg=rand_deg, re_weights=self.cfg.re_weights)
         else:
             means, stds = cast_contract(batch, tdist, sample_n, sample_m, rand_deg=rand_deg)
@@ -811,6 +867,9 @@ class TrainableModel(torch.nn.Module):
         renderings, history = [], []
         n_levels = len(mc.level_samples())
         box = None
+        if self.instance_obj and rays_require_grad(batch):
+            raise NotImplementedError("ray tensors that require a gradient (pose refinement) with instance_obj=True: the box-frame path "
+                                      "of the dynamic-object branch is not wired to origins / directions / viewdirs")
         if self.instance_obj:
             if "timestamp" not in batch:
                 raise RuntimeError("batch['timestamp'] is missing (ZI/models.py:315)")
@@ -946,11 +1005,105 @@ def current_track(tracknet: Optional[TrackNet], step: Optional[int], track_start
     return None
 
 
+class PoseNet(torch.nn.Module):
+    """`LearnPose` (ZI/posenet_v2.py:78-121) with the reference's parameter names, so its `posenet_ckpt_*` files load: one
+    axis-angle rotation `r` and one translation `t` per pose, the `num_cams` camera poses first and the `num_lidars` LiDAR poses
+    behind them (`batch['glo_idx']` indexes this list), zeros at the start - the identity.  forward(ids) -> [len(ids), 4, 4], the
+    correction make_c2w(r, t * t_ratio) of each id, right-multiplied by `init_c2w[id]` when initial poses were given."""
+
+    def __init__(self, num_cams: int, num_lidars: int = 1, learn_R: bool = True, learn_t: bool = True, init_c2w=None, t_ratio: float = 1.0):
+        super().__init__()
+        self.num_cams, self.num_lidars, self.t_ratio = int(num_cams), int(num_lidars), t_ratio
+        n = self.num_cams + self.num_lidars
+        self.init_c2w = None
+        if init_c2w is not None:
+            self.init_c2w = torch.nn.Parameter(torch.as_tensor(init_c2w), requires_grad=False)
+        self.r = torch.nn.Parameter(torch.zeros(n, 3), requires_grad=bool(learn_R))
+        self.t = torch.nn.Parameter(torch.zeros(n, 3), requires_grad=bool(learn_t))
+
+    def rotations(self) -> torch.Tensor:
+        """Rodrigues' formula as posenet_v2.Exp writes it: I + sin|r| / |r| K + (1 - cos|r|) / |r|^2 K^2 with |r| + 1e-15."""
+        r = self.r
+        zero = torch.zeros_like(r[:, :1])
+        K = torch.stack([torch.cat([zero, -r[:, 2:3], r[:, 1:2]], 1), torch.cat([r[:, 2:3], zero, -r[:, 0:1]], 1),
+                         torch.cat([-r[:, 1:2], r[:, 0:1], zero], 1)], dim=1)
+        a = r.norm(dim=-1)[:, None, None] + 1e-15
+        return torch.eye(3, dtype=r.dtype, device=r.device)[None] + (torch.sin(a) / a) * K + ((1 - torch.cos(a)) / a ** 2) * (K @ K)
+
+    def forward(self, ids: torch.Tensor) -> torch.Tensor:
+        top = torch.cat([self.rotations(), (self.t * self.t_ratio).unsqueeze(2)], dim=2)             # [n, 3, 4]
+        bottom = torch.zeros_like(top[:, :1])
+        bottom[:, 0, 3] = 1.0
+        ids = ids.reshape(-1).long()
+        c2w = torch.cat([top, bottom], dim=1)[ids]
+        return c2w if self.init_c2w is None else c2w @ self.init_c2w[ids]
+
+
+def create_posenet(num_poses: int, num_lidars: int = 0, start_step: int = 10000, end_step: int = 20000, pn_lr_init: float = 4e-5,
+                   pn_lr_final: float = 2e-6, t_ratio: float = 0.25, learn_R: bool = True, learn_t: bool = True, lr_delay_steps: int = 5000,
+                   lr_delay_mult: float = 1e-8, adam_beta1: float = 0.9, adam_beta2: float = 0.99, adam_eps: float = 1e-15):
+    """train_utils.py:278-301 with the defaults of configs.py:151-161: the PoseNet, its Adam (betas and eps of `create_optimizer`)
+    and its learning-rate function, the main schedule shifted to the window: learning_rate_decay(step - start_step, max_steps =
+    end_step - start_step).  Returns (posenet, optimizer, lr_fn)."""
+    net = PoseNet(num_poses, num_lidars=num_lidars, learn_R=learn_R, learn_t=learn_t, t_ratio=t_ratio)
+    opt = torch.optim.Adam(net.parameters(), lr=pn_lr_init, betas=(adam_beta1, adam_beta2), eps=adam_eps)
+    return net, opt, (lambda step: learning_rate_decay(step - start_step, pn_lr_init, pn_lr_final, end_step - start_step, lr_delay_steps,
+                                                       lr_delay_mult))
+
+
+def refine_batch(batch: Dict[str, torch.Tensor], poses: torch.Tensor) -> Dict[str, torch.Tensor]:
+    """train.py:207-221: a copy of `batch` with `origins` translated by poses[:, :3, 3] and `directions`, `viewdirs`, `base_x`,
+    `base_y` (and `normals` when present) rotated by poses[:, :3, :3]; poses [N, 4, 4], one per ray.  The caller's dict and its
+    tensors stay as they are."""
+    n = batch["origins"].shape[:1]
+    out = dict(batch)
+    out["origins"] = batch["origins"] + poses[:, :3, 3].reshape(*n, 3)
+    for k in ("directions", "viewdirs", "base_x", "base_y", "normals"):
+        if k in batch:
+            out[k] = (batch[k].reshape(-1, 1, 3) * poses[:, :3, :3]).sum(-1).reshape(*n, 3)
+    return out
+
+
+def pose_phase(step: Optional[int], pose_window=(10000, 20000)) -> str:
+    """Where `step` lies relative to the window of train.py:201-243: 'refine' for start < step < end (refined batch with gradient),
+    'frozen' for step > end (refined batch under no_grad), 'before' otherwise.  (sic) step == start and step == end match none of
+    the reference's comparisons: the batch stays as it is."""
+    if step is None:
+        raise ValueError("pose refinement needs the step number (training_step(..., step=))")
+    start, end = pose_window
+    if start < step < end:
+        return "refine"
+    return "frozen" if step > end else "before"
+
+
+def loss_lambdas(step: int, pose_window=(10000, 20000), pose_refine: bool = True) -> Dict[str, float]:
+    """The weights of the depth and semantic terms over the run (train.py:331-333,404-405) as keywords of `losses.total_loss`:
+    0 while the poses settle (start < step < int(0.6 * end), only with pose refinement), the full 0.4 / 0.04 after the window,
+    0.1 / 0.01 otherwise."""
+    start, end = pose_window
+    if pose_refine and start < step < int(0.6 * end):
+        return {"depth_lam": 0.0, "sem_lam": 0.0}
+    return {"depth_lam": 0.4, "sem_lam": 0.04} if step > end else {"depth_lam": 0.1, "sem_lam": 0.01}
+
+
+def pose_batch(batch, posenet: Optional[PoseNet], step: Optional[int], pose_window=(10000, 20000)):
+    """The batch of train.py:199-243 for this step: itself before the window (and without a PoseNet), refined with gradient inside
+    it, refined without one after it.  `batch['glo_idx']` names every ray's pose."""
+    if posenet is None:
+        return batch
+    phase = pose_phase(step, pose_window)
+    if phase == "before":
+        return batch
+    with torch.enable_grad() if phase == "refine" else torch.no_grad():
+        return refine_batch(batch, posenet(batch["glo_idx"].reshape(-1).int()))
+
+
 def training_step(model: TrainableModel, optimizer: torch.optim.Optimizer, batch: Dict[str, torch.Tensor], train_frac: float = 1.0,
                   randomized: bool = True, hash_decay_mult: float = 0.1, tv_weight: float = 0.0, grad_max_norm: float = 0.0,
                   grad_max_val: float = 0.0, latent_reg: float = 0.001, as_tensors: bool = False, color_rays: Optional[int] = None,
                   check_color_rays: bool = False, tracknet: Optional[TrackNet] = None, tn_optimizer: Optional[torch.optim.Optimizer] = None,
-                  tn_lr_fn=None, step: Optional[int] = None, track_start_opt: int = 5000, **loss_kw):
+                  tn_lr_fn=None, step: Optional[int] = None, track_start_opt: int = 5000, posenet: Optional[PoseNet] = None,
+                  pn_optimizer: Optional[torch.optim.Optimizer] = None, pn_lr_fn=None, pose_window=(10000, 20000), **loss_kw):
     """One optimiser step as train.py:272-459 takes it: forward with random jitter, the loss dictionary (`losses.total_loss` +
     hash decay), backward through the HIP backward kernels, optional total-variation gradient on the tables (grid.py:176-198),
     gradient clipping incl. the unconditional nan_to_num_ (train_utils.clip_gradients), step.  Returns the loss terms as floats, or
@@ -964,7 +1117,12 @@ def training_step(model: TrainableModel, optimizer: torch.optim.Optimizer, batch
     the window (step <= track_start_opt) the model renders its recorded tracks; inside it the TrackNet's learning rate is set, its
     gradients are zeroed, the model renders the refined track with gradient and, after the model's own step, the TrackNet's
     gradients are clipped (the same `clip_gradients`) and its optimiser steps; after it the model renders the refined track under
-    no_grad.  Without a tracknet the step is the one described above."""
+    no_grad.  Without a tracknet the step is the one described above.
+    posenet / pn_optimizer / pn_lr_fn (`create_posenet`) with `step` and pose_window = (start_step, end_step): pose refinement as
+    train.py:199-243,463-466 runs it.  Before the window the batch is rendered as it is; inside it the PoseNet's learning rate is set,
+    its gradients are zeroed, the batch is refined with gradient (`refine_batch`; the caller's batch is not modified), the loss
+    reaches the PoseNet through the ray tensors and, after the model's own step, its gradients are clipped and its optimiser steps;
+    after it the batch is refined under no_grad.  The depth and semantic weights follow `loss_lambdas` unless given."""
     from . import losses as nlosses
     if check_color_rays and color_rays is not None:
         nlosses.check_colourless(batch, color_rays)
@@ -975,6 +1133,16 @@ def training_step(model: TrainableModel, optimizer: torch.optim.Optimizer, batch
         for group in tn_optimizer.param_groups:
             group["lr"] = tn_lr_fn(step)
         tn_optimizer.zero_grad()
+    posing = posenet is not None and pose_phase(step, pose_window) == "refine"
+    if posing:
+        if pn_optimizer is None or pn_lr_fn is None:
+            raise ValueError("pose refinement inside the window needs pn_optimizer and pn_lr_fn (create_posenet)")
+        for group in pn_optimizer.param_groups:
+            group["lr"] = pn_lr_fn(step)
+        pn_optimizer.zero_grad()
+    if posenet is not None:
+        batch = pose_batch(batch, posenet, step, pose_window)
+        loss_kw = {**loss_lambdas(step, pose_window), **loss_kw}
     optimizer.zero_grad(set_to_none=True)
     track_kw = {} if tracknet is None else {"curr_track": current_track(tracknet, step, track_start_opt)}
     renderings, history = model(batch, train_frac=train_frac, randomized=randomized, color_rays=color_rays, **track_kw)
@@ -993,6 +1161,9 @@ def training_step(model: TrainableModel, optimizer: torch.optim.Optimizer, batch
     if refining:
         clip_gradients(tracknet, grad_max_norm, grad_max_val)
         tn_optimizer.step()
+    if posing:
+        clip_gradients(posenet, grad_max_norm, grad_max_val)
+        pn_optimizer.step()
     out = {k: v.detach() for k, v in terms.items()}
     out["loss"] = loss.detach()
     return out if as_tensors else {k: float(v) for k, v in out.items()}
