@@ -290,6 +290,14 @@ int nlr_debug_get(uint32_t key);
  * serves it; host arithmetic only (offsets_host [L+1]). */
 int nlr_grid_fast_path(const int32_t *offsets_host, uint32_t L, uint32_t C, float S, uint32_t H, int table_dtype, uint32_t gridtype,
                        int align_corners, uint32_t interp);
+/* What the grid operator decides per level, host arithmetic only (offsets_host [L+1]; mode, step, lds_kind: [L] each, host).
+ *   mode: 0 the dense index x + y*step + z*step^2 without a modulo (taken only when it stays below the level's size for every corner a
+ *     point of [0,1]^3 can ask for), 1 hashed into a power-of-two table, 2 the generic stride walk + modulo;
+ *   step: resolution (+ 1 unless align_corners);
+ *   lds_kind: how nlr_grid_encode_backward accumulates the level's table gradient for a batch of B points: 1 in an LDS copy of the
+ *     level, 2 in the tagged LDS cache, 0 scattered (atomics, or the bins of nlr_grid_encode_backward_ws); all 0 below B * C = 2^18. */
+int nlr_grid_level_plan(const int32_t *offsets_host, uint32_t L, uint32_t C, float S, uint32_t H, uint32_t gridtype, int align_corners,
+                        uint32_t B, uint32_t *mode, uint32_t *step, uint32_t *lds_kind);
 
 /* Per-kernel timing with HIP events recorded on the SAME stream the kernels are launched on.
  * nlr_profile_begin arms the model: every launch made by nlr_render_rays / nlr_mlp_level is then

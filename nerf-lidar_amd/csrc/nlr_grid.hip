@@ -61,8 +61,13 @@ int nlr_fill_grid_params(GridParams *gp, const void *table, int table_dtype, con
         gp->step[l] = (uint32_t)step;
         const uint32_t hs = gp->hsize[l];
         const bool all3 = (step <= hs) && (step * step <= hs);  // the stride walk adds all three coordinates
-        if (all3 && step * step * step <= hs) gp->mode[l] = 0;                 // dense, index < hsize
-        else if (gridtype == 0 && (hs & (hs - 1)) == 0) gp->mode[l] = 1;       // hashed, power-of-two table
+        const bool walk = all3 && step * step * step <= hs;     // ... and the reference does not hash (gridencoder.cu:66-84)
+        // the largest corner coordinate a kernel can ask for: the upper corner of the cell of x = 1.  Without align_corners it is at most
+        // step - 1 and `walk` alone keeps the dense index below hsize; with align_corners and an integer scale it is `step`, one past the
+        // lattice, which the reference folds back with its modulo: such a level takes the generic walk (mode 2), not the bare formula.
+        const uint64_t cmax = (uint64_t)floorf(fmaf(1.0f, gp->scale[l], align_corners ? 0.0f : 0.5f)) + 1u;
+        if (walk && cmax * (1 + step + step * step) < hs) gp->mode[l] = 0;     // dense, every index < hsize
+        else if (!walk && gridtype == 0 && (hs & (hs - 1)) == 0) gp->mode[l] = 1;  // hashed, power-of-two table
         else gp->mode[l] = 2;
     }
     return NLR_OK;
@@ -652,6 +657,22 @@ extern "C" size_t nlr_grid_backward_workspace_bytes(uint32_t B, uint32_t C, uint
         return 0;
     BinArgs a;
     return nlr_bin_plan(gp, B, C, &a);
+}
+
+extern "C" int nlr_grid_level_plan(const int32_t *offsets_host, uint32_t L, uint32_t C, float S, uint32_t H, uint32_t gridtype, int align_corners,
+                                   uint32_t B, uint32_t *mode, uint32_t *step, uint32_t *lds_kind) {
+    NLR_CHECK_ARG(mode && step && lds_kind, "grid_level_plan: NULL output");
+    GridParams gp;
+    int rc = nlr_fill_grid_params(&gp, offsets_host /* only the level constants are read */, 0, offsets_host, L, C, S, H, gridtype, align_corners, 0);
+    if (rc) return rc;
+    const bool lds_levels = (size_t)B * C >= (1u << 18) && C <= 4;  // as nlr_grid_backward_impl decides
+    const int no_cache = nlr_debug_get(NLR_DBG_NO_SCATTER_CACHE);
+    for (uint32_t l = 0; l < L; ++l) {
+        mode[l] = gp.mode[l];
+        step[l] = gp.step[l];
+        lds_kind[l] = lds_levels ? (uint32_t)nlr_level_lds_kind(gp, l, C, no_cache) : 0u;
+    }
+    return NLR_OK;
 }
 
 static int nlr_grid_backward_impl(const float *grad, const float *inputs, const int32_t *offsets_host, float *grad_embeddings, uint32_t B,

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from conftest import GOLDEN, golden
+from grid_ref import _points
 from oracle import nlr_oracle as orc
 from nerflidar_hip import _lib, config as nconfig, lidar as nlidar, weights as nweights
 
@@ -83,16 +84,6 @@ def gate(name, got, ref, mean_tol, max_tol=None, thr=None, frac=0.0):
 # ------------------------------------------------------------------------------------------------
 # a-7 grid operator through gridencoder.GridEncoder / the C ABI
 # ------------------------------------------------------------------------------------------------
-def _points(n, seed):
-    rng = np.random.default_rng(seed)
-    x = rng.random((n, 3)).astype(np.float32)
-    x[:8] = np.array([[0, 0, 0], [1, 1, 1], [0.5, 0.5, 0.5], [0, 1, 0.25], [1, 0, 0], [0.999999, 0.5, 0.5],
-                      [1e-7, 1e-7, 1e-7], [0.25, 0.75, 1.0]], np.float32)
-    x[8:12, 0] = 1.0001   # out of range -> zeros (gridencoder.cu:110-135)
-    x[12:16, 2] = -1e-6
-    return x
-
-
 @pytest.mark.parametrize("which", ["nerf", "prop0", "prop1"])
 @pytest.mark.parametrize("log2_hashmap", [12, 21])
 def test_grid_forward_bit_exact(which, log2_hashmap):

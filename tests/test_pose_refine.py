@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from conftest import GOLDEN, golden
+from grid_ref import _grid_lookup, _level_table
 from oracle import nlr_oracle as orc
 from nerflidar_hip import checkpoints as nckpt, training as ntrain
 
@@ -225,58 +226,6 @@ def test_posenet_checkpoint_round_trip(tmp_path):
 
 
 # ---- the float64 reference of the kernel test (CPU, torch autograd) -----------------------------------------------------------
-def _level_table(enc):
-    """Per level: scale (float32 arithmetic of the kernel's host side), step, table rows, hashed or not (gridencoder.cu:66-84,138-139)."""
-    off = enc._offsets_host.numpy().astype(np.int64)
-    S = np.float32(np.log2(enc.per_level_scale))
-    out = []
-    for l in range(enc.num_levels):
-        scale = float(np.float32(np.exp2(np.float32(l) * S)) * np.float32(enc.base_resolution) - np.float32(1.0))
-        step = int(np.ceil(scale)) + 1 + (0 if enc.align_corners else 1)
-        hs = int(off[l + 1] - off[l])
-        stride, dims = 1, 0
-        while dims < 3 and stride <= hs:
-            stride *= step
-            dims += 1
-        out.append((scale, step, hs, int(off[l]), stride > hs))
-    return out
-
-
-def _grid_lookup(x01, table, enc):
-    """Differentiable (in x01) trilinear lookup on every level: [P, 3] -> [P, L, C] in x01's dtype; a point outside [0, 1]^3 gives
-    zeros.  The cell index is taken from the values (no gradient), the weights carry the gradient."""
-    P = x01.shape[0]
-    oob = ((x01 < 0) | (x01 > 1)).any(-1)
-    feats = []
-    for scale, step, hs, off, hashed in _level_table(enc):
-        pos = x01 * scale + (0.0 if enc.align_corners else 0.5)
-        pg = torch.floor(pos.detach())
-        fr = pos - pg
-        if enc.interp_id == 1:
-            fr = fr * fr * (3 - 2 * fr)
-        pg = pg.long().clamp_min(0)
-        acc = 0
-        for c8 in range(8):
-            w = torch.ones(P, dtype=x01.dtype)
-            pl = []
-            for d in range(3):
-                bit = (c8 >> d) & 1
-                w = w * (fr[:, d] if bit else 1 - fr[:, d])
-                pl.append(pg[:, d] + bit)
-            if hashed and enc.gridtype_id == 0:
-                idx = (pl[0] ^ ((pl[1] * 2654435761) & 0xFFFFFFFF) ^ ((pl[2] * 805459861) & 0xFFFFFFFF)) & 0xFFFFFFFF
-            else:
-                idx, stride = torch.zeros(P, dtype=torch.long), 1
-                for d in range(3):
-                    if stride <= hs:
-                        idx = idx + pl[d] * stride
-                        stride *= step
-            idx = torch.where(oob, torch.zeros_like(idx), idx % hs + off)
-            acc = acc + w[:, None] * table[idx]
-        feats.append(torch.where(oob[:, None], torch.zeros_like(acc), acc))
-    return torch.stack(feats, 1)
-
-
 def _ref_features(rays, tdist, rand_deg, table, enc, n, re_w, dtype, want_pos=False):
     """Features [N, S, L*C] of the fused operator in `dtype`, differentiable in rays = (o, d, bx, by): oracle cast_rays +
     contract_mean_std, / bound (2), the lookup above, the erf weight of models.py:976, the mean over the multisamples."""
@@ -473,13 +422,17 @@ def test_encode_ray_gradient_matches_float64_autograd(S, n, L, C):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("variant", ["smoothstep", "align_corners", "tiled"])
+@pytest.mark.parametrize("variant", ["smoothstep", "align_corners", "tiled", "level_dim_8"])
 def test_encode_ray_gradient_other_grids(variant):
-    """The envelope of the forward: smoothstep interpolation, align_corners, the tiled grid type; same gate."""
-    kw = dict(smoothstep=dict(interp="smoothstep"), align_corners=dict(align=True), tiled=dict(gridtype="tiled"))[variant]
-    k = dict(_kernel_case(33, 7, 3, 2, False, True, False, **kw), half=False)
+    """The envelope of the forward: smoothstep interpolation, align_corners, the tiled grid type, 8 features per level; same gate, and
+    the features themselves at the bound of test_encode_ray_gradient_matches_float64_autograd (derived there)."""
+    kw = dict(smoothstep=dict(interp="smoothstep"), align_corners=dict(align=True), tiled=dict(gridtype="tiled"), level_dim_8={})[variant]
+    k = dict(_kernel_case(33, 7, 3, 8 if variant == "level_dim_8" else 2, False, True, False, **kw), half=False)
     keep = ~k["near"]
-    _, grads, _ = _gpu_ray_grads(k, 7, True)
+    f, grads, _ = _gpu_ray_grads(k, 7, True)
+    ferr = float((f.cpu().double() - k["feats"]).abs().max())
+    _record(f"kernel {variant} features: err {ferr:.3e}")
+    assert f.shape == k["feats"].shape and ferr <= 9.2e-5, ("features", ferr)
     for name, got, want, f32 in zip(("d_origins", "d_directions", "d_base_x", "d_base_y"), grads, k["want"], k["f32"]):
         err, yard = float((got.cpu().double() - want)[keep].abs().max()), float((f32 - want)[keep].abs().max())
         _record(f"kernel {variant} {name}: err {err:.3e} f32-reference {yard:.3e} max|want| {float(want[keep].abs().max()):.3e}")
@@ -748,11 +701,17 @@ def test_rays_without_gradient_leave_the_step_bit_identical():
             assert torch.equal(la[k].detach(), lb[k].detach()), k
     p1 = {k: p.grad.clone() for k, p in tm.named_parameters() if p.grad is not None and "embeddings" not in k}
     assert set(p0) == set(p1) == set(p0b)
-    repeatable = [k for k in p0 if torch.equal(p0[k], p0b[k])]
-    print(f"{len(repeatable)} of {len(p0)} parameter gradients repeat bit for bit between two plain steps")
-    assert len(repeatable) > 0
+    # Which gradients have bits to be identical to is a property of the kernels, not of one pair of runs: the PropMLP parameter gradients
+    # are summed with float atomics (nlr_prop_mlp_bwd_param_kernel), in an order that changes from call to call - and a one-element
+    # gradient such as density_layer.2.bias still repeats by chance in a few runs of ten; every other parameter gradient is summed in
+    # a fixed order and must repeat
+    atomic = [k for k in p0 if k.startswith("prop_mlp_")]
+    repeatable = [k for k in p0 if k not in atomic]
+    print(f"{sum(torch.equal(p0[k], p0b[k]) for k in p0)} of {len(p0)} parameter gradients repeat bit for bit between two plain steps")
+    assert len(repeatable) > 0 and len(atomic) > 0
     for k in p0:
         if k in repeatable:
+            assert torch.equal(p0[k], p0b[k]), k
             assert torch.equal(p0[k], p1[k]), k
         else:  # summed in an order that changes from call to call: the gate of the f32 backward kernels
             assert float((p0[k] - p1[k]).abs().max()) <= 2e-5 * float(p0[k].abs().max()) + float((p0[k] - p0b[k]).abs().max()), k
