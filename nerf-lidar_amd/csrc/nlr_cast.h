@@ -11,6 +11,33 @@ struct CastTaps {
     bool contracted;
 };
 
+// What a kernel holds of a ray and of the interval [t0, t1] of its tdist row it works on: nlr_load_ray fills the first part, nlr_load_span
+// the second (a kernel that walks a ray's samples loads the ray once and the interval per sample).
+struct RayRegs {
+    float o[3], d[3], bx[3], by[3], radius, t0, t1;
+};
+__device__ __forceinline__ RayRegs nlr_load_ray(const CastParams &cp, uint32_t ray) {
+    RayRegs r;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        r.o[c] = cp.origins[(size_t)ray * 3 + c];
+        r.d[c] = cp.directions[(size_t)ray * 3 + c];
+        r.bx[c] = cp.base_x[(size_t)ray * 3 + c];
+        r.by[c] = cp.base_y[(size_t)ray * 3 + c];
+    }
+    r.radius = cp.radii[ray];
+    return r;
+}
+__device__ __forceinline__ void nlr_load_span(const CastParams &cp, uint32_t ray, uint32_t k, RayRegs &r) {
+    r.t0 = cp.tdist[(size_t)ray * (cp.S + 1) + k];
+    r.t1 = cp.tdist[(size_t)ray * (cp.S + 1) + k + 1];
+}
+__device__ __forceinline__ RayRegs nlr_load_ray(const CastParams &cp, uint32_t ray, uint32_t k) {
+    RayRegs r = nlr_load_ray(cp, ray);
+    nlr_load_span(cp, ray, k, r);
+    return r;
+}
+
 __device__ __forceinline__ Gauss nlr_cast_one(const CastParams &cp, uint32_t ray, uint32_t k, uint32_t j, float t0, float t1,
                                               const float *o, const float *d, const float *bx, const float *by, float radius,
                                               float *raw = nullptr, CastTaps *taps = nullptr) {
@@ -61,6 +88,10 @@ __device__ __forceinline__ Gauss nlr_cast_one(const CastParams &cp, uint32_t ray
     }
     return g;
 }
+__device__ __forceinline__ Gauss nlr_cast_one(const CastParams &cp, uint32_t ray, uint32_t k, uint32_t j, const RayRegs &rr, float *raw = nullptr,
+                                              CastTaps *taps = nullptr) {
+    return nlr_cast_one(cp, ray, k, j, rr.t0, rr.t1, rr.o, rr.d, rr.bx, rr.by, rr.radius, raw, taps);
+}
 
 // models.py:976: erf(1 / clamp(sqrt(8 * std^2 * G^2), min=1e-10))
 __device__ __forceinline__ float nlr_erf_weight(float zs, float gsize) {
@@ -71,4 +102,24 @@ __device__ __forceinline__ float nlr_erf_weight(float zs, float gsize) {
 // ulp of the erf ARGUMENT, i.e. <= 3e-7 of the weight; the clamp at 1e-10 maps to an argument cap of 1e10).
 __device__ __forceinline__ float nlr_erf_weight_fast(float inv_s8, float inv_g) {
     return erff(fminf(inv_s8 * inv_g, 1e10f));
+}
+
+// ---- host: kernel instance for a grid ------------------------------------------------------------------------------------------
+template <int V>
+struct NlrInt {
+    static constexpr int value = V;
+};
+// f(T{}, NlrInt<C>{}) with T the table's element type and C the features per level; a C outside {1, 2, 4} takes the 8-wide instance.
+template <typename F>
+static inline void nlr_dispatch_tc(const GridParams &gp, F &&f) {
+    auto with_c = [&](auto t) {
+        switch (gp.C) {
+            case 1: f(t, NlrInt<1>{}); break;
+            case 2: f(t, NlrInt<2>{}); break;
+            case 4: f(t, NlrInt<4>{}); break;
+            default: f(t, NlrInt<8>{}); break;
+        }
+    };
+    if (gp.table_dtype == 0) with_c(float{});
+    else with_c(__half{});
 }

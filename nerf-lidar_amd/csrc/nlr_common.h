@@ -130,4 +130,6 @@ __device__ __forceinline__ float nlr_nan0_clip01(float x) {
     if (x != x) x = 0.0f;
     return fminf(fmaxf(x, 0.0f), 1.0f);
 }
+// F.softplus (beta=1, threshold=20), models.py:1116
+__device__ __forceinline__ float nlr_softplus(float x) { return x > 20.0f ? x : log1pf(expf(x)); }
 #endif

@@ -28,22 +28,13 @@ __global__ void __launch_bounds__(256) nlr_encode_kernel(CastParams cp, GridPara
     if (m >= M) return;
     const uint32_t level = blockIdx.y;
     const uint32_t ray = m / cp.S, k = m - ray * cp.S;
-    float o[3], d[3], bx[3], by[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        o[c] = cp.origins[(size_t)ray * 3 + c];
-        d[c] = cp.directions[(size_t)ray * 3 + c];
-        bx[c] = cp.base_x[(size_t)ray * 3 + c];
-        by[c] = cp.base_y[(size_t)ray * 3 + c];
-    }
-    const float radius = cp.radii[ray];
-    const float t0 = cp.tdist[(size_t)ray * (cp.S + 1) + k], t1 = cp.tdist[(size_t)ray * (cp.S + 1) + k + 1];
+    const RayRegs rr = nlr_load_ray(cp, ray, k);
     const float gsize = gp.gsize[level];
     float acc[C];
 #pragma unroll
     for (int c = 0; c < C; ++c) acc[c] = 0.0f;
     for (uint32_t j = 0; j < cp.n; ++j) {
-        const Gauss g = nlr_cast_one(cp, ray, k, j, t0, t1, o, d, bx, by, radius);
+        const Gauss g = nlr_cast_one(cp, ray, k, j, rr);
         const float werf = re_weights ? nlr_erf_weight(g.zs, gsize) : 1.0f;
         nlr_level_accum<T, C>(gp, level, g, werf, acc);
     }
@@ -56,13 +47,6 @@ __global__ void __launch_bounds__(256) nlr_encode_kernel(CastParams cp, GridPara
 // Proposal level: one thread per sample does every grid level and the tiny density MLP
 // (L*C -> 64 -> 1, fp32 VALU with wave-uniform weights) and writes only density[M].
 // ---------------------------------------------------------------------------------------------
-struct PropMlpParams {
-    const float *w1, *b1;  // dev [64, F], [64]
-    const float *w2;       // dev [64]  (row 0 of density_layer.2)
-    float b2, density_bias;
-    uint32_t F;
-};
-
 template <typename T, int C, int LMAX>
 __global__ void __launch_bounds__(256) nlr_prop_kernel(CastParams cp, GridParams gp, PropMlpParams mp, int re_weights,
                                                        float *__restrict__ density, float *__restrict__ feat_out) {
@@ -70,21 +54,12 @@ __global__ void __launch_bounds__(256) nlr_prop_kernel(CastParams cp, GridParams
     const uint32_t M = cp.N * cp.S;
     if (m >= M) return;
     const uint32_t ray = m / cp.S, k = m - ray * cp.S;
-    float o[3], d[3], bx[3], by[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        o[c] = cp.origins[(size_t)ray * 3 + c];
-        d[c] = cp.directions[(size_t)ray * 3 + c];
-        bx[c] = cp.base_x[(size_t)ray * 3 + c];
-        by[c] = cp.base_y[(size_t)ray * 3 + c];
-    }
-    const float radius = cp.radii[ray];
-    const float t0 = cp.tdist[(size_t)ray * (cp.S + 1) + k], t1 = cp.tdist[(size_t)ray * (cp.S + 1) + k + 1];
+    const RayRegs rr = nlr_load_ray(cp, ray, k);
     float feat[LMAX * C];
 #pragma unroll
     for (int i = 0; i < LMAX * C; ++i) feat[i] = 0.0f;
     for (uint32_t j = 0; j < cp.n; ++j) {
-        const Gauss g = nlr_cast_one(cp, ray, k, j, t0, t1, o, d, bx, by, radius);
+        const Gauss g = nlr_cast_one(cp, ray, k, j, rr);
 #pragma unroll
         for (int l = 0; l < LMAX; ++l) {
             if (l < (int)gp.L) {
@@ -110,8 +85,7 @@ __global__ void __launch_bounds__(256) nlr_prop_kernel(CastParams cp, GridParams
             if (i < (int)mp.F) a = fmaf(mp.w1[h * mp.F + i], feat[i], a);
         raw = fmaf(mp.w2[h], fmaxf(a, 0.0f), raw);
     }
-    const float x = raw + mp.density_bias;
-    density[m] = x > 20.0f ? x : log1pf(expf(x));  // F.softplus (beta=1, threshold=20), models.py:1116
+    density[m] = nlr_softplus(raw + mp.density_bias);
 }
 
 // Slot -> sample.  The fused kernels give 8 lanes (one per multisample) to a SLOT and 8 consecutive slots to a wave; which sample a slot
@@ -186,8 +160,17 @@ __host__ __forceinline__ uint64_t nlr_slot_count(const CastParams &cp) {
 // Cone casting + contraction run ONCE per multisample (the (sample, level) mapping above repeats them per level),
 // every lane walks all grid levels with its 8*L gathers in flight, and the mean over the multisamples is a 3-step
 // butterfly inside each 8-lane group.  7/8 of the lanes are active for sample_n = 7.
+//
+// Two families.  nlr_encode8_kernel / nlr_prop8_kernel run the level body of nlr_level_fast.h (grids it covers: linear
+// interpolation, align_corners = False, every level dense or hashed with a power-of-two table - all grids of the path's
+// configurations); nlr_encode8g_kernel / nlr_prop8g_kernel run nlr_level_accum of nlr_grid_level.h for everything else.
+// Same lane mapping, same arithmetic per point, bit-identical features.  They stay two families because of the registers:
+// one kernel with the level body as a template argument gives the generic instances the fast kernels' frame (persistent
+// loop, XCD chunks, 106 SGPRs) and costs them 1 to 3 waves of occupancy, and the L = 16 proposal instance spills
+// (profiles/encode_refactor_isa.txt).
 // =============================================================================================================
-// Sum over the 8 lanes of a group, every lane gets it.  Three DPP adds (VALU) instead of three ds_bpermute round trips:
+// Sum over the 8 lanes of a group, every lane gets it (the ...8g kernels; the fast ones use the inline-asm form of
+// nlr_level_fast.h, which gives the same bits).  Three DPP adds (VALU) instead of three ds_bpermute round trips:
 // quad_perm [1,0,3,2] and [2,3,0,1] are the xor-1 / xor-2 butterfly steps; after them the four lanes of a quad hold the
 // same bits (a+b == b+a), so row_half_mirror (lane i <- lane 7-i of its 8-lane half row, i.e. some lane of the OTHER
 // quad) delivers exactly what the xor-4 step would: the result is bit-identical to the __shfl_xor butterfly.
@@ -225,17 +208,7 @@ __global__ void __launch_bounds__(256) nlr_encode8g_kernel(CastParams cp, GridPa
     const bool in = nlr_slot_sample(cp, gt >> 3, ray, k);
     const uint32_t m = ray * cp.S + k;
     const bool active = in && j < cp.n;
-    float o[3], d[3], bx[3], by[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        o[c] = cp.origins[(size_t)ray * 3 + c];
-        d[c] = cp.directions[(size_t)ray * 3 + c];
-        bx[c] = cp.base_x[(size_t)ray * 3 + c];
-        by[c] = cp.base_y[(size_t)ray * 3 + c];
-    }
-    const float radius = cp.radii[ray];
-    const float t0 = cp.tdist[(size_t)ray * (cp.S + 1) + k], t1 = cp.tdist[(size_t)ray * (cp.S + 1) + k + 1];
-    Gauss g = nlr_cast_one(cp, ray, k, active ? j : 0, t0, t1, o, d, bx, by, radius);
+    Gauss g = nlr_cast_one(cp, ray, k, active ? j : 0, nlr_load_ray(cp, ray, k));
     if (!active) g.x0 = -1.0f;  // out of range -> contributes zeros
     const float inv_s8 = __frsqrt_rn(8.0f * (g.zs * g.zs));  // v_rsq_f32 (1 ulp) for 1/sqrtf (30 instructions)
     const float inv_n = 1.0f / (float)cp.n;
@@ -280,17 +253,7 @@ __global__ void __launch_bounds__(256) nlr_prop8g_kernel(CastParams cp, GridPara
     const bool in = nlr_slot_sample(cp, gt >> 3, ray, k);
     const uint32_t m = ray * cp.S + k;
     const bool active = in && j < cp.n;
-    float o[3], d[3], bx[3], by[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        o[c] = cp.origins[(size_t)ray * 3 + c];
-        d[c] = cp.directions[(size_t)ray * 3 + c];
-        bx[c] = cp.base_x[(size_t)ray * 3 + c];
-        by[c] = cp.base_y[(size_t)ray * 3 + c];
-    }
-    const float radius = cp.radii[ray];
-    const float t0 = cp.tdist[(size_t)ray * (cp.S + 1) + k], t1 = cp.tdist[(size_t)ray * (cp.S + 1) + k + 1];
-    Gauss g = nlr_cast_one(cp, ray, k, active ? j : 0, t0, t1, o, d, bx, by, radius);
+    Gauss g = nlr_cast_one(cp, ray, k, active ? j : 0, nlr_load_ray(cp, ray, k));
     if (!active) g.x0 = -1.0f;
     const float inv_s8 = __frsqrt_rn(8.0f * (g.zs * g.zs));  // v_rsq_f32 (1 ulp) for 1/sqrtf (30 instructions)
     const float inv_n = 1.0f / (float)cp.n;
@@ -322,19 +285,9 @@ __global__ void __launch_bounds__(256) nlr_prop8g_kernel(CastParams cp, GridPara
         part = fmaf(sw[64 * mp.F + 64 + hu], fmaxf(a, 0.0f), part);
     }
     const float raw = nlr_group8_sum(part) + mp.b2;
-    if (in && j == 0) {
-        const float x = raw + mp.density_bias;
-        density[m] = x > 20.0f ? x : log1pf(expf(x));  // F.softplus (beta=1, threshold=20), models.py:1116
-    }
+    if (in && j == 0) density[m] = nlr_softplus(raw + mp.density_bias);
 }
 
-// =============================================================================================================
-// Round-3 forms of the two kernels above on the level body of nlr_level_fast.h (grids it covers: linear interpolation,
-// align_corners = False, every level dense or hashed with a power-of-two table - all grids of the path's configurations);
-// the ...8g kernels stay for everything else.  Same lane mapping, same arithmetic per point; what changed is the
-// instruction stream (see nlr_level_fast.h) and that a lane's validity (active multisample, point inside the unit cube) is decided
-// once instead of once per level.
-// =============================================================================================================
 // Workgroup order.  The hardware deals the workgroups of a launch to the 8 XCDs round-robin (workgroup b runs on XCD b mod 8) and every
 // XCD has its own 4 MiB L2.  Consecutive workgroups here are consecutive 32-sample pieces of one ray and then of its neighbour in the batch
 // (for a LiDAR sweep or an image: the next azimuth column / pixel), whose fine-level cells overlap; dealt round-robin, the lines they share
@@ -374,24 +327,6 @@ __device__ __forceinline__ uint32_t nlr_dbg_ray(uint32_t po) {
 #define NLR_DBG_RAY(r) (r)
 #endif
 
-struct RayRegs {
-    float o[3], d[3], bx[3], by[3], radius, t0, t1;
-};
-__device__ __forceinline__ RayRegs nlr_load_ray(const CastParams &cp, uint32_t ray, uint32_t k) {
-    RayRegs r;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        r.o[c] = cp.origins[(size_t)ray * 3 + c];
-        r.d[c] = cp.directions[(size_t)ray * 3 + c];
-        r.bx[c] = cp.base_x[(size_t)ray * 3 + c];
-        r.by[c] = cp.base_y[(size_t)ray * 3 + c];
-    }
-    r.radius = cp.radii[ray];
-    r.t0 = cp.tdist[(size_t)ray * (cp.S + 1) + k];
-    r.t1 = cp.tdist[(size_t)ray * (cp.S + 1) + k + 1];
-    return r;
-}
-
 template <typename T, int C>
 __device__ __forceinline__ void nlr_encode8_block(const CastParams &cp, const GridParams &gp, int re_weights, float *__restrict__ feat,
                                                   int piece_major, uint32_t block) {
@@ -404,7 +339,7 @@ __device__ __forceinline__ void nlr_encode8_block(const CastParams &cp, const Gr
     const uint32_t m = ray * cp.S + k;
     const bool active = in && j < cp.n;
     const RayRegs rr = nlr_load_ray(cp, ray, k);
-    const Gauss g = nlr_cast_one(cp, ray, k, active ? j : 0, rr.t0, rr.t1, rr.o, rr.d, rr.bx, rr.by, rr.radius);
+    const Gauss g = nlr_cast_one(cp, ray, k, active ? j : 0, rr);
     // gridencoder.cu:124-135: a point outside [0,1]^3 encodes as zeros on every level
     const bool valid = active && !((g.x0 < 0 || g.x0 > 1) || (g.x1 < 0 || g.x1 > 1) || (g.x2 < 0 || g.x2 > 1));
     const float inv_s8 = __frsqrt_rn(8.0f * (g.zs * g.zs));  // v_rsq_f32 (1 ulp) for 1/sqrtf (30 instructions)
@@ -420,7 +355,7 @@ __device__ __forceinline__ void nlr_encode8_block(const CastParams &cp, const Gr
         }
         float a[C];
         nlr_group8_sum_to(r, a);
-        if (in && j == (l & 7)) {  // spread the row stores over the lanes of the group (layouts: see nlr_encode8g_kernel)
+        if (in && j == (l & 7)) {  // spread the row stores over the lanes of the group (layouts: nlr_feat_ptr)
             if constexpr (C == 8) {  // two pieces per level
                 float *f0 = nlr_feat_ptr<4>(feat, piece_major, M, m, 2 * l, 2 * gp.L), *f1 = nlr_feat_ptr<4>(feat, piece_major, M, m, 2 * l + 1, 2 * gp.L);
 #pragma unroll
@@ -469,7 +404,7 @@ __global__ void __launch_bounds__(256) nlr_prop8_kernel(CastParams cp, GridParam
     const uint32_t m = ray * cp.S + k;
     const bool active = in && j < cp.n;
     const RayRegs rr = nlr_load_ray(cp, ray, k);
-    const Gauss g = nlr_cast_one(cp, ray, k, active ? j : 0, rr.t0, rr.t1, rr.o, rr.d, rr.bx, rr.by, rr.radius);
+    const Gauss g = nlr_cast_one(cp, ray, k, active ? j : 0, rr);
     const bool valid = active && !((g.x0 < 0 || g.x0 > 1) || (g.x1 < 0 || g.x1 > 1) || (g.x2 < 0 || g.x2 > 1));
     const float inv_s8 = __frsqrt_rn(8.0f * (g.zs * g.zs));
     const float inv_n = 1.0f / (float)cp.n;
@@ -515,7 +450,7 @@ __global__ void __launch_bounds__(256) nlr_prop8_kernel(CastParams cp, GridParam
     nlr_group8_sum_n(praw);
     if (in && j == 0) {
         const float x = (praw[0] + mp.b2) + mp.density_bias;
-        density[m] = x > 20.0f ? x : log1pf(expf(x));  // F.softplus (beta=1, threshold=20), models.py:1116
+        density[m] = nlr_softplus(x);
     }
   }
 }
@@ -528,10 +463,6 @@ __global__ void __launch_bounds__(256) nlr_prop8_kernel(CastParams cp, GridParam
 // measured 3-4x slower than the two-kernel form: it loses the LDS accumulation of the hot dense levels and half of the run
 // lengths (an inactive 8th lane in every group of multisamples).
 // ---------------------------------------------------------------------------------------------
-int nlr_fill_cast_params(CastParams *cp, const NlrRays *rays, const float *tdist, const float *rand_deg, uint32_t N,
-                         uint32_t S, uint32_t n, uint32_t mloops, float std_scale);
-int nlr_launch_encode(const CastParams &cp, const GridParams &gp, int re_weights, float *feat, int piece_major, hipStream_t st);
-
 __global__ void __launch_bounds__(256) nlr_encode_expand_kernel(CastParams cp, GridParams gp, int re_weights, const float *__restrict__ d_feat,
                                                                float *__restrict__ x01, float *__restrict__ g_pts) {
     const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -539,16 +470,7 @@ __global__ void __launch_bounds__(256) nlr_encode_expand_kernel(CastParams cp, G
     if (t >= M * cp.n) return;
     const uint32_t m = (uint32_t)(t / cp.n), j = (uint32_t)(t - (size_t)m * cp.n);
     const uint32_t ray = m / cp.S, k = m - ray * cp.S;
-    float o[3], d[3], bx[3], by[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        o[c] = cp.origins[(size_t)ray * 3 + c];
-        d[c] = cp.directions[(size_t)ray * 3 + c];
-        bx[c] = cp.base_x[(size_t)ray * 3 + c];
-        by[c] = cp.base_y[(size_t)ray * 3 + c];
-    }
-    const float t0 = cp.tdist[(size_t)ray * (cp.S + 1) + k], t1 = cp.tdist[(size_t)ray * (cp.S + 1) + k + 1];
-    const Gauss g = nlr_cast_one(cp, ray, k, j, t0, t1, o, d, bx, by, cp.radii[ray]);
+    const Gauss g = nlr_cast_one(cp, ray, k, j, nlr_load_ray(cp, ray, k));
     x01[t * 3 + 0] = g.x0;
     x01[t * 3 + 1] = g.x1;
     x01[t * 3 + 2] = g.x2;
@@ -563,60 +485,6 @@ __global__ void __launch_bounds__(256) nlr_encode_expand_kernel(CastParams cp, G
     }
 }
 
-static int encode_features_args(CastParams *cp, GridParams *gp, const NlrRays *rays, const float *tdist, uint32_t N, uint32_t S, uint32_t sample_n,
-                                uint32_t sample_m, float std_scale, const float *rand_deg, const NlrGridDesc *grid) {
-    NLR_CHECK_ARG(grid && grid->table && grid->offsets && tdist, "encode_features: NULL argument");
-    int rc = nlr_fill_cast_params(cp, rays, tdist, rand_deg, N, S, sample_n, sample_m, std_scale);
-    if (rc) return rc;
-    return nlr_fill_grid_params(gp, grid->table, grid->table_dtype, grid->offsets, grid->num_levels, grid->level_dim, grid->log2_per_level_scale,
-                                grid->base_resolution, grid->gridtype, (int)grid->align_corners, grid->interp);
-}
-
-extern "C" int nlr_encode_features_forward(const NlrRays *rays, const float *tdist, uint32_t N, uint32_t S, uint32_t sample_n, uint32_t sample_m,
-                                           float std_scale, const float *rand_deg, const NlrGridDesc *grid, uint32_t re_weights, float *features,
-                                           void *stream) {
-    if (N == 0 || S == 0) return NLR_OK;
-    NLR_CHECK_ARG(features, "encode_features_forward: NULL output");
-    CastParams cp;
-    GridParams gp;
-    int rc = encode_features_args(&cp, &gp, rays, tdist, N, S, sample_n, sample_m, std_scale, rand_deg, grid);
-    if (rc) return rc;
-    return nlr_launch_encode(cp, gp, (int)re_weights, features, 0, (hipStream_t)stream);
-}
-
-extern "C" int nlr_encode_features_backward_ws(const NlrRays *rays, const float *tdist, uint32_t N, uint32_t S, uint32_t sample_n, uint32_t sample_m,
-                                               float std_scale, const float *rand_deg, const NlrGridDesc *grid, uint32_t re_weights,
-                                               const float *d_features, float *points_tmp, float *grad_tmp, float *grad_table, void *workspace,
-                                               size_t workspace_bytes, void *stream);
-
-extern "C" int nlr_encode_features_backward(const NlrRays *rays, const float *tdist, uint32_t N, uint32_t S, uint32_t sample_n, uint32_t sample_m,
-                                            float std_scale, const float *rand_deg, const NlrGridDesc *grid, uint32_t re_weights,
-                                            const float *d_features, float *points_tmp, float *grad_tmp, float *grad_table, void *stream) {
-    return nlr_encode_features_backward_ws(rays, tdist, N, S, sample_n, sample_m, std_scale, rand_deg, grid, re_weights, d_features, points_tmp,
-                                           grad_tmp, grad_table, nullptr, 0, stream);
-}
-
-extern "C" int nlr_encode_features_backward_ws(const NlrRays *rays, const float *tdist, uint32_t N, uint32_t S, uint32_t sample_n, uint32_t sample_m,
-                                               float std_scale, const float *rand_deg, const NlrGridDesc *grid, uint32_t re_weights,
-                                               const float *d_features, float *points_tmp, float *grad_tmp, float *grad_table, void *workspace,
-                                               size_t workspace_bytes, void *stream) {
-    if (N == 0 || S == 0) return NLR_OK;
-    NLR_CHECK_ARG(d_features && grad_table && points_tmp && grad_tmp, "encode_features_backward: NULL tensor");
-    CastParams cp;
-    GridParams gp;
-    int rc = encode_features_args(&cp, &gp, rays, tdist, N, S, sample_n, sample_m, std_scale, rand_deg, grid);
-    if (rc) return rc;
-    const size_t B = (size_t)N * S * sample_n;
-    NLR_CHECK_ARG(B < (1ull << 32), "encode_features_backward: %zu multisample points do not fit the 32-bit point index", B);
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(nlr_encode_expand_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, cp, gp, (int)re_weights, d_features, points_tmp,
-                       grad_tmp);
-    NLR_LAUNCH_CHECK("nlr_encode_expand_kernel");
-    return nlr_grid_encode_backward_ws(grad_tmp, points_tmp, grid->offsets, grad_table, (uint32_t)B, 3, grid->level_dim, grid->num_levels,
-                                       grid->log2_per_level_scale, grid->base_resolution, nullptr, nullptr, grid->gridtype, (int)grid->align_corners,
-                                       grid->interp, 1, workspace, workspace_bytes, stream);
-}
-
 // ---------------------------------------------------------------------------------------------
 // Rows a-5 / a-6 alone (training path, nerflidar_hip/training.py): the contracted multisample means / bound and stds / bound
 // that MLP.predict_density hands to the GridEncoder (ZI/models.py:965-973), one thread per (sample, multisample).
@@ -627,37 +495,12 @@ __global__ void __launch_bounds__(256) nlr_cast_contract_kernel(CastParams cp, f
     if (t >= M * cp.n) return;
     const uint32_t m = (uint32_t)(t / cp.n), j = (uint32_t)(t - (size_t)m * cp.n);
     const uint32_t ray = m / cp.S, k = m - ray * cp.S;
-    float o[3], d[3], bx[3], by[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        o[c] = cp.origins[(size_t)ray * 3 + c];
-        d[c] = cp.directions[(size_t)ray * 3 + c];
-        bx[c] = cp.base_x[(size_t)ray * 3 + c];
-        by[c] = cp.base_y[(size_t)ray * 3 + c];
-    }
-    const float t0 = cp.tdist[(size_t)ray * (cp.S + 1) + k], t1 = cp.tdist[(size_t)ray * (cp.S + 1) + k + 1];
     float raw[3];
-    const Gauss g = nlr_cast_one(cp, ray, k, j, t0, t1, o, d, bx, by, cp.radii[ray], raw);
+    const Gauss g = nlr_cast_one(cp, ray, k, j, nlr_load_ray(cp, ray, k), raw);
     means[t * 3 + 0] = raw[0];
     means[t * 3 + 1] = raw[1];
     means[t * 3 + 2] = raw[2];
     stds[t] = g.zs;
-}
-
-int nlr_fill_cast_params(CastParams *cp, const NlrRays *rays, const float *tdist, const float *rand_deg, uint32_t N,
-                         uint32_t S, uint32_t n, uint32_t mloops, float std_scale);
-
-extern "C" int nlr_cast_contract(const NlrRays *rays, const float *tdist, uint32_t N, uint32_t S, uint32_t sample_n,
-                                 uint32_t sample_m, float std_scale, const float *rand_deg, float *means, float *stds, void *stream) {
-    NLR_CHECK_ARG(tdist && means && stds, "cast_contract: NULL tensor");
-    if (N == 0 || S == 0) return NLR_OK;
-    CastParams cp;
-    int rc = nlr_fill_cast_params(&cp, rays, tdist, rand_deg, N, S, sample_n, sample_m, std_scale);
-    if (rc) return rc;
-    const size_t total = (size_t)N * S * sample_n;
-    hipLaunchKernelGGL(nlr_cast_contract_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, cp, means, stds);
-    NLR_LAUNCH_CHECK("nlr_cast_contract_kernel");
-    return NLR_OK;
 }
 
 // ---- host side ---------------------------------------------------------------------------------
@@ -724,66 +567,62 @@ static void nlr_dbg_upload(hipStream_t st) {
 }
 #endif
 
-int nlr_launch_encode(const CastParams &cp, const GridParams &gp, int re_weights, float *feat, int piece_major, hipStream_t st) {
+// Launch geometry of the 8-lane kernels: `nblocks` workgroups of 32 slots.  The ...8g kernels run one each; the fast ones walk them in
+// XCD chunks from `grid` workgroups (= nblocks unless a diagnostic build asks for a persistent grid).
+struct Launch8 {
+    bool fast;
+    uint32_t nblocks, chunk;
+    dim3 grid;
+};
+static Launch8 nlr_launch8(const CastParams &cp, const GridParams &gp, hipStream_t st) {
+    Launch8 g;
+    g.fast = nlr_level_fast_ok(gp) && !nlr_force_generic();
+    g.nblocks = (uint32_t)((nlr_slot_count(cp) * 8 + 255) / 256);
+    g.chunk = NLR_XCD_CHUNK;
+    g.grid = dim3(g.nblocks);
 #ifdef NLR_DBG_ENV
     nlr_dbg_upload(st);
+    if (const char *e = getenv("NLR_ENC_CHUNK")) g.chunk = (uint32_t)atoi(e);
+    if (const char *e = getenv("NLR_ENC_PERSIST")) g.grid.x = (uint32_t)atoi(e) * 256u < g.nblocks ? (uint32_t)atoi(e) * 256u : g.nblocks;
 #endif
+    return g;
+}
+
+int nlr_launch_encode(const CastParams &cp, const GridParams &gp, int re_weights, float *feat, int piece_major, hipStream_t st) {
     // 8 lanes per sample with a 32-bit lane index (the kernels compute N * S in 32 bits)
     NLR_CHECK_ARG(nlr_slot_count(cp) * 8 < (1ull << 32), "encode: N * S = %llu samples do not fit the 32-bit lane index (chunk the rays)",
                   (unsigned long long)cp.N * cp.S);
-    const uint32_t M = cp.N * cp.S;
     if (cp.n <= 8) {  // multisample-parallel mapping
-        dim3 grid8((uint32_t)((nlr_slot_count(cp) * 8 + 255) / 256)), block8(256);
-        const bool fast = nlr_level_fast_ok(gp) && !nlr_force_generic();
-        uint32_t chunk = NLR_XCD_CHUNK;
-        dim3 gridp = grid8;
-#ifdef NLR_DBG_ENV
-        if (const char *e = getenv("NLR_ENC_CHUNK")) chunk = (uint32_t)atoi(e);
-        if (const char *e = getenv("NLR_ENC_PERSIST")) gridp.x = (uint32_t)atoi(e) * 256u < grid8.x ? (uint32_t)atoi(e) * 256u : grid8.x;
-#endif
-#define NLR_ENC8(T, C)                                                                                                               \
-    do {                                                                                                                             \
-        if (fast) hipLaunchKernelGGL((nlr_encode8_kernel<T, C>), gridp, block8, 0, st, cp, gp, re_weights, feat, piece_major, grid8.x, chunk); \
-        else hipLaunchKernelGGL((nlr_encode8g_kernel<T, C>), grid8, block8, 0, st, cp, gp, re_weights, feat, piece_major);           \
-    } while (0)
-        if (gp.table_dtype == 0) {
-            switch (gp.C) {
-                case 1: NLR_ENC8(float, 1); break;
-                case 2: NLR_ENC8(float, 2); break;
-                case 4: NLR_ENC8(float, 4); break;
-                default: NLR_ENC8(float, 8); break;
-            }
-        } else {
-            switch (gp.C) {
-                case 1: NLR_ENC8(__half, 1); break;
-                case 2: NLR_ENC8(__half, 2); break;
-                case 4: NLR_ENC8(__half, 4); break;
-                default: NLR_ENC8(__half, 8); break;
-            }
-        }
-#undef NLR_ENC8
+        const Launch8 g = nlr_launch8(cp, gp, st);
+        nlr_dispatch_tc(gp, [&](auto t, auto c) {
+            using T = decltype(t);
+            constexpr int C = decltype(c)::value;
+            if (g.fast) hipLaunchKernelGGL((nlr_encode8_kernel<T, C>), g.grid, dim3(256), 0, st, cp, gp, re_weights, feat, piece_major, g.nblocks, g.chunk);
+            else hipLaunchKernelGGL((nlr_encode8g_kernel<T, C>), dim3(g.nblocks), dim3(256), 0, st, cp, gp, re_weights, feat, piece_major);
+        });
         NLR_LAUNCH_CHECK("nlr_encode8_kernel");
         return NLR_OK;
     }
-    dim3 grid((M + 255) / 256, gp.L), block(256);
-#define NLR_ENC(T, C) hipLaunchKernelGGL((nlr_encode_kernel<T, C>), grid, block, 0, st, cp, gp, re_weights, feat)
-    if (gp.table_dtype == 0) {
-        switch (gp.C) {
-            case 1: NLR_ENC(float, 1); break;
-            case 2: NLR_ENC(float, 2); break;
-            case 4: NLR_ENC(float, 4); break;
-            default: NLR_ENC(float, 8); break;
-        }
-    } else {
-        switch (gp.C) {
-            case 1: NLR_ENC(__half, 1); break;
-            case 2: NLR_ENC(__half, 2); break;
-            case 4: NLR_ENC(__half, 4); break;
-            default: NLR_ENC(__half, 8); break;
-        }
-    }
-#undef NLR_ENC
+    const dim3 grid((cp.N * cp.S + 255) / 256, gp.L);
+    nlr_dispatch_tc(gp, [&](auto t, auto c) {
+        hipLaunchKernelGGL((nlr_encode_kernel<decltype(t), decltype(c)::value>), grid, dim3(256), 0, st, cp, gp, re_weights, feat);
+    });
     NLR_LAUNCH_CHECK("nlr_encode_kernel");
+    return NLR_OK;
+}
+
+// f(T{}, NlrInt<C>{}, NlrInt<LMAX>{}) for the grids the proposal kernels have instances for
+template <typename F>
+static int nlr_dispatch_prop(const GridParams &gp, F &&f) {
+    auto with_t = [&](auto c, auto lmax) {
+        if (gp.table_dtype == 0) f(float{}, c, lmax);
+        else f(__half{}, c, lmax);
+    };
+    if (gp.C == 1 && gp.L <= 8) with_t(NlrInt<1>{}, NlrInt<8>{});
+    else if (gp.C == 1) with_t(NlrInt<1>{}, NlrInt<16>{});
+    else if (gp.C == 2) with_t(NlrInt<2>{}, NlrInt<8>{});
+    else if (gp.C == 4 && gp.L <= 4) with_t(NlrInt<4>{}, NlrInt<4>{});
+    else NLR_FAIL(NLR_ERR_UNSUPPORTED, "proposal MLP: grid L=%u C=%u not supported by the fused proposal kernel", gp.L, gp.C);
     return NLR_OK;
 }
 
@@ -791,10 +630,6 @@ int nlr_launch_prop(const CastParams &cp, const GridParams &gp, const float *w1,
                     float density_bias, int re_weights, float *density, float *feat_out, hipStream_t st) {
     NLR_CHECK_ARG(nlr_slot_count(cp) * 8 < (1ull << 32), "proposal level: N * S = %llu samples do not fit the 32-bit lane index (chunk the rays)",
                   (unsigned long long)cp.N * cp.S);
-    const uint32_t M = cp.N * cp.S;
-#ifdef NLR_DBG_ENV
-    nlr_dbg_upload(st);
-#endif
     PropMlpParams mp;
     mp.w1 = w1;
     mp.b1 = b1;
@@ -804,38 +639,87 @@ int nlr_launch_prop(const CastParams &cp, const GridParams &gp, const float *w1,
     mp.F = gp.L * gp.C;
     NLR_CHECK_ARG(mp.F <= 16, "proposal MLP: L*C = %u > 16 features is outside the fused proposal kernel", mp.F);
     if (cp.n <= 8) {
-        dim3 grid8((uint32_t)((nlr_slot_count(cp) * 8 + 255) / 256)), block8(256);
-        const bool fast = nlr_level_fast_ok(gp) && !nlr_force_generic();
-        uint32_t chunk = NLR_XCD_CHUNK;
-        dim3 gridp = grid8;
-#ifdef NLR_DBG_ENV
-        if (const char *e = getenv("NLR_ENC_CHUNK")) chunk = (uint32_t)atoi(e);
-        if (const char *e = getenv("NLR_ENC_PERSIST")) gridp.x = (uint32_t)atoi(e) * 256u < grid8.x ? (uint32_t)atoi(e) * 256u : grid8.x;
-#endif
-#define NLR_PROP8(T, C, LM)                                                                                                                    \
-    do {                                                                                                                                       \
-        if (fast) hipLaunchKernelGGL((nlr_prop8_kernel<T, C, LM>), gridp, block8, 0, st, cp, gp, mp, re_weights, density, feat_out, grid8.x, chunk); \
-        else hipLaunchKernelGGL((nlr_prop8g_kernel<T, C, LM>), grid8, block8, 0, st, cp, gp, mp, re_weights, density, feat_out);               \
-    } while (0)
-        const bool f32t = gp.table_dtype == 0;
-        if (gp.C == 1 && gp.L <= 8) { if (f32t) NLR_PROP8(float, 1, 8); else NLR_PROP8(__half, 1, 8); }
-        else if (gp.C == 1) { if (f32t) NLR_PROP8(float, 1, 16); else NLR_PROP8(__half, 1, 16); }
-        else if (gp.C == 2) { if (f32t) NLR_PROP8(float, 2, 8); else NLR_PROP8(__half, 2, 8); }
-        else if (gp.C == 4 && gp.L <= 4) { if (f32t) NLR_PROP8(float, 4, 4); else NLR_PROP8(__half, 4, 4); }
-        else NLR_FAIL(NLR_ERR_UNSUPPORTED, "proposal MLP: grid L=%u C=%u not supported by the fused proposal kernel", gp.L, gp.C);
-#undef NLR_PROP8
+        const Launch8 g = nlr_launch8(cp, gp, st);
+        const int rc = nlr_dispatch_prop(gp, [&](auto t, auto c, auto lmax) {
+            using T = decltype(t);
+            constexpr int C = decltype(c)::value, LM = decltype(lmax)::value;
+            if (g.fast) hipLaunchKernelGGL((nlr_prop8_kernel<T, C, LM>), g.grid, dim3(256), 0, st, cp, gp, mp, re_weights, density, feat_out, g.nblocks, g.chunk);
+            else hipLaunchKernelGGL((nlr_prop8g_kernel<T, C, LM>), dim3(g.nblocks), dim3(256), 0, st, cp, gp, mp, re_weights, density, feat_out);
+        });
+        if (rc) return rc;
         NLR_LAUNCH_CHECK("nlr_prop8_kernel");
         return NLR_OK;
     }
-    dim3 grid((M + 255) / 256), block(256);
-#define NLR_PROP(T, C, LM) hipLaunchKernelGGL((nlr_prop_kernel<T, C, LM>), grid, block, 0, st, cp, gp, mp, re_weights, density, feat_out)
-    const bool f32 = gp.table_dtype == 0;
-    if (gp.C == 1 && gp.L <= 8) { if (f32) NLR_PROP(float, 1, 8); else NLR_PROP(__half, 1, 8); }
-    else if (gp.C == 1) { if (f32) NLR_PROP(float, 1, 16); else NLR_PROP(__half, 1, 16); }
-    else if (gp.C == 2) { if (f32) NLR_PROP(float, 2, 8); else NLR_PROP(__half, 2, 8); }
-    else if (gp.C == 4 && gp.L <= 4) { if (f32) NLR_PROP(float, 4, 4); else NLR_PROP(__half, 4, 4); }
-    else NLR_FAIL(NLR_ERR_UNSUPPORTED, "proposal MLP: grid L=%u C=%u not supported by the fused proposal kernel", gp.L, gp.C);
-#undef NLR_PROP
+    const dim3 grid((cp.N * cp.S + 255) / 256);
+    const int rc = nlr_dispatch_prop(gp, [&](auto t, auto c, auto lmax) {
+        hipLaunchKernelGGL((nlr_prop_kernel<decltype(t), decltype(c)::value, decltype(lmax)::value>), grid, dim3(256), 0, st, cp, gp, mp, re_weights,
+                           density, feat_out);
+    });
+    if (rc) return rc;
     NLR_LAUNCH_CHECK("nlr_prop_kernel");
     return NLR_OK;
 }
+
+// ---- entry points --------------------------------------------------------------------------------
+int nlr_encode_features_args(CastParams *cp, GridParams *gp, const NlrRays *rays, const float *tdist, uint32_t N, uint32_t S, uint32_t sample_n,
+                             uint32_t sample_m, float std_scale, const float *rand_deg, const NlrGridDesc *grid) {
+    NLR_CHECK_ARG(grid && grid->table && grid->offsets && tdist, "encode_features: NULL argument");
+    int rc = nlr_fill_cast_params(cp, rays, tdist, rand_deg, N, S, sample_n, sample_m, std_scale);
+    if (rc) return rc;
+    return nlr_fill_grid_params(gp, grid->table, grid->table_dtype, grid->offsets, grid->num_levels, grid->level_dim, grid->log2_per_level_scale,
+                                grid->base_resolution, grid->gridtype, (int)grid->align_corners, grid->interp);
+}
+
+extern "C" int nlr_encode_features_forward(const NlrRays *rays, const float *tdist, uint32_t N, uint32_t S, uint32_t sample_n, uint32_t sample_m,
+                                           float std_scale, const float *rand_deg, const NlrGridDesc *grid, uint32_t re_weights, float *features,
+                                           void *stream) {
+    if (N == 0 || S == 0) return NLR_OK;
+    NLR_CHECK_ARG(features, "encode_features_forward: NULL output");
+    CastParams cp;
+    GridParams gp;
+    int rc = nlr_encode_features_args(&cp, &gp, rays, tdist, N, S, sample_n, sample_m, std_scale, rand_deg, grid);
+    if (rc) return rc;
+    return nlr_launch_encode(cp, gp, (int)re_weights, features, 0, (hipStream_t)stream);
+}
+
+extern "C" int nlr_encode_features_backward_ws(const NlrRays *rays, const float *tdist, uint32_t N, uint32_t S, uint32_t sample_n, uint32_t sample_m,
+                                               float std_scale, const float *rand_deg, const NlrGridDesc *grid, uint32_t re_weights,
+                                               const float *d_features, float *points_tmp, float *grad_tmp, float *grad_table, void *workspace,
+                                               size_t workspace_bytes, void *stream) {
+    if (N == 0 || S == 0) return NLR_OK;
+    NLR_CHECK_ARG(d_features && grad_table && points_tmp && grad_tmp, "encode_features_backward: NULL tensor");
+    CastParams cp;
+    GridParams gp;
+    int rc = nlr_encode_features_args(&cp, &gp, rays, tdist, N, S, sample_n, sample_m, std_scale, rand_deg, grid);
+    if (rc) return rc;
+    const size_t B = (size_t)N * S * sample_n;
+    NLR_CHECK_ARG(B < (1ull << 32), "encode_features_backward: %zu multisample points do not fit the 32-bit point index", B);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(nlr_encode_expand_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, cp, gp, (int)re_weights, d_features, points_tmp,
+                       grad_tmp);
+    NLR_LAUNCH_CHECK("nlr_encode_expand_kernel");
+    return nlr_grid_encode_backward_ws(grad_tmp, points_tmp, grid->offsets, grad_table, (uint32_t)B, 3, grid->level_dim, grid->num_levels,
+                                       grid->log2_per_level_scale, grid->base_resolution, nullptr, nullptr, grid->gridtype, (int)grid->align_corners,
+                                       grid->interp, 1, workspace, workspace_bytes, stream);
+}
+
+extern "C" int nlr_encode_features_backward(const NlrRays *rays, const float *tdist, uint32_t N, uint32_t S, uint32_t sample_n, uint32_t sample_m,
+                                            float std_scale, const float *rand_deg, const NlrGridDesc *grid, uint32_t re_weights,
+                                            const float *d_features, float *points_tmp, float *grad_tmp, float *grad_table, void *stream) {
+    return nlr_encode_features_backward_ws(rays, tdist, N, S, sample_n, sample_m, std_scale, rand_deg, grid, re_weights, d_features, points_tmp,
+                                           grad_tmp, grad_table, nullptr, 0, stream);
+}
+
+extern "C" int nlr_cast_contract(const NlrRays *rays, const float *tdist, uint32_t N, uint32_t S, uint32_t sample_n,
+                                 uint32_t sample_m, float std_scale, const float *rand_deg, float *means, float *stds, void *stream) {
+    NLR_CHECK_ARG(tdist && means && stds, "cast_contract: NULL tensor");
+    if (N == 0 || S == 0) return NLR_OK;
+    CastParams cp;
+    int rc = nlr_fill_cast_params(&cp, rays, tdist, rand_deg, N, S, sample_n, sample_m, std_scale);
+    if (rc) return rc;
+    const size_t total = (size_t)N * S * sample_n;
+    hipLaunchKernelGGL(nlr_cast_contract_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, cp, means, stds);
+    NLR_LAUNCH_CHECK("nlr_cast_contract_kernel");
+    return NLR_OK;
+}
+

@@ -71,15 +71,7 @@ __global__ void __launch_bounds__(256) nlr_encode_rays_kernel(CastParams cp, Gri
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t ray = blockIdx.x * NLR_RAYS_PER_BLOCK + (threadIdx.x >> 6);
     if (ray >= cp.N) return;  // (a whole wave: the kernel has no barrier)
-    float o[3], d[3], bx[3], by[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        o[c] = cp.origins[(size_t)ray * 3 + c];
-        d[c] = cp.directions[(size_t)ray * 3 + c];
-        bx[c] = cp.base_x[(size_t)ray * 3 + c];
-        by[c] = cp.base_y[(size_t)ray * 3 + c];
-    }
-    const float radius = cp.radii[ray];
+    RayRegs rr = nlr_load_ray(cp, ray);
     const float inv_n = 1.0f / (float)cp.n;
     const uint32_t LC = gp.L * C;
     float acc[12];  // d_o | d_d | d_bx | d_by
@@ -88,9 +80,9 @@ __global__ void __launch_bounds__(256) nlr_encode_rays_kernel(CastParams cp, Gri
     const uint32_t items = cp.S * cp.n;
     for (uint32_t it = lane; it < items; it += 64u) {
         const uint32_t k = it / cp.n, j = it - k * cp.n;
-        const float t0 = cp.tdist[(size_t)ray * (cp.S + 1) + k], t1 = cp.tdist[(size_t)ray * (cp.S + 1) + k + 1];
         CastTaps tp;
-        const Gauss g = nlr_cast_one(cp, ray, k, j, t0, t1, o, d, bx, by, radius, nullptr, &tp);
+        nlr_load_span(cp, ray, k, rr);
+        const Gauss g = nlr_cast_one(cp, ray, k, j, rr, nullptr, &tp);
         if (nlr_outside_unit_cube(g)) continue;  // encodes as zeros on every level: no gradient
         const float inv_s8 = __frsqrt_rn(8.0f * (g.zs * g.zs));
         const bool footprint = re_weights && tp.contracted;  // zs depends on the position only through the contraction
@@ -168,34 +160,17 @@ extern "C" int nlr_encode_features_backward_rays(const NlrRays *rays, const floa
                  (int)grid->table_dtype);
     CastParams cp;
     GridParams gp;
-    int rc = nlr_fill_cast_params(&cp, rays, tdist, rand_deg, N, S, sample_n, sample_m, std_scale);
-    if (rc) return rc;
-    rc = nlr_fill_grid_params(&gp, grid->table, grid->table_dtype, grid->offsets, grid->num_levels, grid->level_dim, grid->log2_per_level_scale,
-                              grid->base_resolution, grid->gridtype, (int)grid->align_corners, grid->interp);
+    int rc = nlr_encode_features_args(&cp, &gp, rays, tdist, N, S, sample_n, sample_m, std_scale, rand_deg, grid);
     if (rc) return rc;
     // (a lane's pair counter advances by 64 past the last pair before it stops)
     NLR_CHECK_ARG((uint64_t)S * sample_n + 64 < (1ull << 32), "encode_features_backward_rays: S * sample_n = %llu does not fit the 32-bit pair counter",
                   (unsigned long long)S * sample_n);
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid_dim((N + NLR_RAYS_PER_BLOCK - 1) / NLR_RAYS_PER_BLOCK), block(64 * NLR_RAYS_PER_BLOCK);
-#define NLR_RAYS(T, C) \
-    hipLaunchKernelGGL((nlr_encode_rays_kernel<T, C>), grid_dim, block, 0, st, cp, gp, (int)re_weights, d_features, d_origins, d_directions, d_base_x, d_base_y)
-    if (gp.table_dtype == 0) {
-        switch (gp.C) {
-            case 1: NLR_RAYS(float, 1); break;
-            case 2: NLR_RAYS(float, 2); break;
-            case 4: NLR_RAYS(float, 4); break;
-            default: NLR_RAYS(float, 8); break;
-        }
-    } else {
-        switch (gp.C) {
-            case 1: NLR_RAYS(__half, 1); break;
-            case 2: NLR_RAYS(__half, 2); break;
-            case 4: NLR_RAYS(__half, 4); break;
-            default: NLR_RAYS(__half, 8); break;
-        }
-    }
-#undef NLR_RAYS
+    nlr_dispatch_tc(gp, [&](auto t, auto c) {
+        hipLaunchKernelGGL((nlr_encode_rays_kernel<decltype(t), decltype(c)::value>), grid_dim, block, 0, st, cp, gp, (int)re_weights, d_features,
+                           d_origins, d_directions, d_base_x, d_base_y);
+    });
     NLR_LAUNCH_CHECK("nlr_encode_rays_kernel");
     return NLR_OK;
 }

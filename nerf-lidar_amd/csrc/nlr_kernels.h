@@ -19,6 +19,13 @@ struct CastParams {
     float degj[NLR_MAX_MULTI];                       // the angles themselves (rand path)
 };
 
+struct PropMlpParams {  // the density MLP of a proposal level (L*C -> 64 -> 1)
+    const float *w1, *b1;  // dev [64, F], [64]
+    const float *w2;       // dev [64]  (row 0 of density_layer.2)
+    float b2, density_bias;
+    uint32_t F;
+};
+
 struct CompositeParams {
     const float *density, *tdist, *dirs, *rgb, *sem, *inten, *far, *origins;
     uint32_t N, S, K;
@@ -84,7 +91,10 @@ int nlr_launch_resample(const float *prev_sdist, const float *prev_weights, uint
                         const float *far, float lam, uint32_t N, float *sdist, float *tdist, hipStream_t st);
 int nlr_fill_cast_params(CastParams *cp, const NlrRays *rays, const float *tdist, const float *rand_deg, uint32_t N,
                          uint32_t S, uint32_t n, uint32_t mloops, float std_scale);
-// piece_major: features as [F/4][M][4] (only honoured by the 8-lane kernel with C == 4; see nlr_encode8_kernel)
+// the cast and grid parameter blocks of the nlr_encode_features_* entry points
+int nlr_encode_features_args(CastParams *cp, GridParams *gp, const NlrRays *rays, const float *tdist, uint32_t N, uint32_t S, uint32_t sample_n,
+                             uint32_t sample_m, float std_scale, const float *rand_deg, const NlrGridDesc *grid);
+// piece_major: features as [F/4][M][4] (8-lane kernels, sample_n <= 8, every C: nlr_feat_ptr), otherwise row-major [M, F]
 int nlr_launch_encode(const CastParams &cp, const GridParams &gp, int re_weights, float *feat, int piece_major, hipStream_t st);
 int nlr_launch_ray_vote(const float *tdist, uint32_t N, uint32_t S, uint32_t *votes, hipStream_t st);
 int nlr_launch_prop(const CastParams &cp, const GridParams &gp, const float *w1, const float *b1, const float *w2, float b2,
