@@ -8,6 +8,7 @@
 
 #include <stdlib.h>
 #include "nlr_objects.h"
+#include "nlr_tape.h"
 
 
 static thread_local char g_err[512] = "";
@@ -48,7 +49,13 @@ struct ProfScope {  // RAII bracket around one launch
 };
 
 // ---- model ------------------------------------------------------------------------------------------
-struct LevelModel {
+struct MlpShape {  // the scalars of one NerfMLP (matrix cores)
+    uint32_t W = 0, WB = 0, D = 0, HT = 0, K = 0, int_row = 0xffffffffu, deg = 0, E = 0;
+    bool use_int = false;
+    uint32_t prec = NLR_PREC_MIXED;
+    float rgb_premul = 1.0f, rgb_bias = 0.0f, rgb_padding = 0.001f;
+};
+struct LevelModel : MlpShape {
     bool is_prop = false;
     GridParams gp;
     uint32_t F = 0, S = 0;
@@ -57,15 +64,11 @@ struct LevelModel {
     // proposal MLP (fp32 VALU)
     float *p_w1 = nullptr, *p_b1 = nullptr, *p_w2 = nullptr;
     float p_b2 = 0.0f;
-    // NerfMLP (matrix cores)
-    uint32_t W = 0, WB = 0, D = 0, HT = 0, K = 0, int_row = 0xffffffffu, deg = 0, E = 0;
-    bool use_int = false;
-    uint32_t prec = NLR_PREC_MIXED;
+    // NerfMLP: what mlp_assemble built, on the device
     void *tape = nullptr;
     uint32_t tape_chunks = 0;
     void *tape_lidar = nullptr;  // LiDAR-only tile program [T | T] (NLR_PREC_FAST): trunk + heads of both halves, no view layers
     uint32_t tape_lidar_chunks = 0;
-    float rgb_premul = 1.0f, rgb_bias = 0.0f, rgb_padding = 0.001f;
     float *bias_all = nullptr;
     uint32_t bias_count = 0;
     float *u_det = nullptr, *u_rand = nullptr;                            // sample positions [S]
@@ -104,15 +107,9 @@ static uint16_t f32_to_bf16(float f) {
     return (uint16_t)(u >> 16);
 }
 
-// Dense row-major matrix view used while fusing / slicing the reference's Linear layers.
-struct Mat {
-    std::vector<float> a;
-    uint32_t rows = 0, cols = 0;
-    Mat() {}
-    Mat(uint32_t r, uint32_t c) : a((size_t)r * c, 0.0f), rows(r), cols(c) {}
-    float &at(uint32_t r, uint32_t c) { return a[(size_t)r * cols + c]; }
-    float get(uint32_t r, uint32_t c) const { return (r < rows && c < cols) ? a[(size_t)r * cols + c] : 0.0f; }
-};
+// the reference's Linear layers while they are fused / sliced / stacked (nlr_tape.h)
+typedef TapeMat<float, 0> Mat;
+typedef TapeLinear<float, 0> Lin;
 
 // The fold of density_layer.2 into a consumer of the bottleneck (NLR_PREC_FAST, nlr_mlp_kernel.h: FOLD): a layer that computes
 // A.b + c from the bottleneck b = W2.h + c2 computes (A.W2).h + (c + A.c2) from the trunk's hidden vector h.  `a` holds A in its
@@ -133,77 +130,188 @@ static Mat fold_w2(const Mat &a, uint32_t col0, const NlrLinear &w2, std::vector
     return out;
 }
 
-static Mat mat_from(const NlrLinear &l, uint32_t col0, uint32_t ncols) {
-    Mat m(l.out_features, ncols);
-    for (uint32_t r = 0; r < l.out_features; ++r)
-        for (uint32_t c = 0; c < ncols; ++c) m.at(r, c) = l.weight[(size_t)r * l.in_features + col0 + c];
-    return m;
+static Lin lin_from(const NlrLinear &l) {
+    Lin x;
+    x.w = Mat(l.out_features, l.in_features);
+    x.w.a.assign(l.weight, l.weight + (size_t)l.out_features * l.in_features);
+    x.b.assign(l.bias, l.bias + l.out_features);
+    return x;
 }
 
-// ---- weight fragments (layouts: nlr_mlp_kernel.h).  One fragment = 1 KiB = 64 lanes x 16 B, the A operand of one MFMA
-// step for 16 output rows; lane = (m = lane & 15, q = lane >> 4).
-//   bf16  (v_mfma_f32_16x16x32_bf16): rows 16R + m, k-block g (32 input features): element j = W[16R + m][32g + 16(j>>2) + 4q + (j&3)]
-//         - the k order in which two 16-row accumulator tiles of the previous layer, converted pairwise, form the B operand
-//   f32   (v_mfma_f32_16x16x4_f32, 4 k-steps per fragment): rows 16R + m, input row block J (16 features): element e = W[16R + m][16J + 4q + e]
-// GEMM order on the tape: output unit o (32 rows) -> k-group g -> row block j (R = 2o + j; RH = 1: R = o, only the first 16 rows
-// of the unit exist) [-> hi, lo fragment of the split-bf16 form].
+// ---- weight tapes in bytes (fragment layout, GEMM order, chunk padding and slack: nlr_tape.h).  One walk per GEMM; a fragment goes out
+// as f32, as bf16, or as the hi, lo pair of the split-bf16 form (W = hi + lo).
 enum { TAPE_F32 = 0, TAPE_BF16 = 1, TAPE_X3 = 2 };
-#define NLR_TAPE_CHUNK 32768
 struct TapeBuilder {
     std::vector<uint8_t> bytes;
-    size_t frags() const { return bytes.size() / 1024; }
-    void frag_bf16(const Mat &w, uint32_t R, uint32_t g, bool lo_part) {
-        uint16_t f[64 * 8];
-        for (uint32_t lane = 0; lane < 64; ++lane)
-            for (uint32_t j = 0; j < 8; ++j) {
-                const float v = w.get(16 * R + (lane & 15), 32 * g + 16 * (j >> 2) + 4 * (lane >> 4) + (j & 3));
-                const uint16_t hi = f32_to_bf16(v);
-                if (!lo_part) {
-                    f[lane * 8 + j] = hi;
-                } else {  // W = hi + lo
-                    uint32_t hb = (uint32_t)hi << 16;
-                    float hf;
-                    memcpy(&hf, &hb, 4);
-                    f[lane * 8 + j] = f32_to_bf16(v - hf);
-                }
-            }
-        bytes.insert(bytes.end(), (const uint8_t *)f, (const uint8_t *)f + sizeof(f));
-    }
-    void frag_f32(const Mat &w, uint32_t R, uint32_t J) {
-        float f[64 * 4];
-        for (uint32_t lane = 0; lane < 64; ++lane)
-            for (uint32_t e = 0; e < 4; ++e) f[lane * 4 + e] = w.get(16 * R + (lane & 15), 16 * J + 4 * (lane >> 4) + e);
-        bytes.insert(bytes.end(), (const uint8_t *)f, (const uint8_t *)f + sizeof(f));
-    }
-    // out_pad: rows padded to whole units of 32 (RH = 2) or to 16 (RH = 1, a single unit); in_pad: input features padded to 32
+    size_t frags() const { return bytes.size() / NLR_FRAG_BYTES; }
+    void append(const void *p, size_t n) { bytes.insert(bytes.end(), (const uint8_t *)p, (const uint8_t *)p + n); }
+    void append(const TapeBuilder &x) { append(x.bytes.data(), x.bytes.size()); }
     void add(const Mat &w, uint32_t out_pad, uint32_t in_pad, int kind, uint32_t RH = 2) {
-        const uint32_t OT = RH == 2 ? out_pad / 32 : 1;
-        const uint32_t KG = kind == TAPE_F32 ? in_pad / 16 : in_pad / 32;
-        for (uint32_t o = 0; o < OT; ++o)
-            for (uint32_t g = 0; g < KG; ++g)
-                for (uint32_t j = 0; j < RH; ++j) {
-                    const uint32_t R = RH == 2 ? 2 * o + j : o;
-                    if (kind == TAPE_F32) {
-                        frag_f32(w, R, g);
-                    } else {
-                        frag_bf16(w, R, g, false);
-                        if (kind == TAPE_X3) frag_bf16(w, R, g, true);
-                    }
-                }
+        nlr_tape_walk(w, out_pad, in_pad, kind == TAPE_F32 ? 16 : 32, RH, [&](const float *v, uint32_t n) {
+            if (kind == TAPE_F32) return append(v, n * sizeof(float));
+            uint16_t hi[64 * 8], lo[64 * 8];
+            for (uint32_t i = 0; i < n; ++i) {
+                hi[i] = f32_to_bf16(v[i]);
+                const uint32_t hb = (uint32_t)hi[i] << 16;
+                float hf;
+                memcpy(&hf, &hb, 4);
+                lo[i] = f32_to_bf16(v[i] - hf);
+            }
+            append(hi, n * sizeof(uint16_t));
+            if (kind == TAPE_X3) append(lo, n * sizeof(uint16_t));
+        });
     }
-    void pad_to_chunk() { bytes.resize((bytes.size() + NLR_TAPE_CHUNK - 1) / NLR_TAPE_CHUNK * NLR_TAPE_CHUNK, 0); }
+    // the end of a tile's program: zeros to the chunk boundary and the slack the kernel prefetches into; returns the program's chunks
+    uint32_t finish() {
+        const size_t chunks = (bytes.size() + NLR_CHUNK_BYTES - 1) / NLR_CHUNK_BYTES;
+        bytes.resize((chunks + NLR_TAPE_SLACK_CHUNKS) * NLR_CHUNK_BYTES, 0);
+        return (uint32_t)chunks;
+    }
 };
-
-static int upload_bias(NlrModel *m, const float *b, uint32_t n, uint32_t pad, float **out) {
-    std::vector<float> v(pad, 0.0f);
-    for (uint32_t i = 0; i < n; ++i) v[i] = b[i];
-    return dev_upload(m, v.data(), pad * sizeof(float), (void **)out);
-}
 
 static int check_linear(const NlrLinear &l, uint32_t out_f, uint32_t in_f, const char *name) {
     NLR_CHECK_ARG(l.weight && l.bias, "%s: weight/bias is NULL", name);
     NLR_CHECK_ARG(l.out_features == out_f && l.in_features == in_f, "%s: expected [%u,%u], got [%u,%u]", name, out_f, in_f,
                   l.out_features, l.in_features);
+    return NLR_OK;
+}
+
+// Everything of a NerfMLP level that needs no device: the scalars, the bias block and the weight tapes as the kernel reads them.
+struct MlpTapes : MlpShape {
+    std::vector<float> bias;
+    std::vector<uint8_t> tape, tape_lidar;  // tape_lidar: NLR_PREC_FAST only
+    uint32_t tape_chunks = 0, tape_lidar_chunks = 0;
+};
+static int mlp_assemble(const NlrMlpDesc &d, uint32_t F, uint32_t prec, MlpTapes &a) {
+    int rc;
+    if ((rc = check_linear(d.density0, 64, F, "density_layer.0"))) return rc;
+    a.W = d.net_width_viewdirs;
+    a.WB = d.bottleneck_width;
+    a.D = d.net_depth_viewdirs;
+    a.deg = d.deg_view;
+    a.E = 3 + 6 * d.deg_view;
+    a.rgb_premul = d.rgb_premultiplier;
+    a.rgb_bias = d.rgb_bias;
+    a.rgb_padding = d.rgb_padding;
+    if (a.D < 2 || d.skip_layer_dir != 0 || a.D > NLR_MAX_VIEW_DEPTH)
+        NLR_FAIL(NLR_ERR_UNSUPPORTED, "view MLP: fused path needs net_depth_viewdirs in [2,%d] and skip_layer_dir = 0 (got %u, %u)",
+                 NLR_MAX_VIEW_DEPTH, a.D, d.skip_layer_dir);
+    if (a.W % 32 || a.WB % 32) NLR_FAIL(NLR_ERR_UNSUPPORTED, "view MLP: widths must be multiples of 32");
+    if (F % 4) NLR_FAIL(NLR_ERR_UNSUPPORTED, "NerfMLP: L*C = %u must be a multiple of 4", F);
+    if ((rc = check_linear(d.density2, a.WB, 64, "density_layer.2"))) return rc;
+    // use_semantic with no_sem_layer (models.py:1133): the logits are channels [1, 1+K) of the bottleneck.  They reach the
+    // softmax through the same two head GEMMs as a learned sem_layer, with pass-through weights that are exact in the
+    // split-bf16 / f32 arithmetic: hidden rows c and 32 + c hold relu(+x_{1+c}) and relu(-x_{1+c}), output row c their difference.
+    const bool sem_layer = d.use_semantic && !d.no_sem_layer;
+    const bool sem_pass = d.use_semantic && d.no_sem_layer;
+    if (sem_pass) NLR_CHECK_ARG(d.class_num <= 32 && 1 + d.class_num <= d.bottleneck_width, "no_sem_layer: class_num %u does not fit", d.class_num);
+    a.K = d.use_semantic ? d.class_num : 0;
+    a.use_int = d.use_intensity != 0;
+    a.HT = (d.use_semantic ? 2 : 0) + (a.use_int ? 2 : 0);
+    NLR_CHECK_ARG(a.K + (a.use_int ? 1 : 0) <= 32, "class_num %u (+intensity) exceeds one 32-row output tile", a.K);
+
+    a.prec = prec;
+    const int crit = (prec == NLR_PREC_FAST) ? TAPE_X3 : TAPE_F32;   // density trunk + heads
+    const int view = (prec == NLR_PREC_F32) ? TAPE_F32 : TAPE_BF16;  // view MLP
+    // NLR_PREC_FAST: density_layer.2 is multiplied into the layers that read the bottleneck (fold_w2), which then read the 64-wide
+    // hidden vector of the trunk; D2 keeps its first unit (row 0 = the raw density).  The other two precisions are the exact-parity
+    // modes and keep the reference's layers as they are.
+    const bool fold = prec == NLR_PREC_FAST;
+    auto push_bias = [&](const float *b, uint32_t n, uint32_t pad) {  // each block padded to whole units of 32 (order: nlr_tape.h)
+        for (uint32_t i = 0; i < pad; ++i) a.bias.push_back(i < n ? b[i] : 0.0f);
+    };
+    // the kernel instances take two 32-feature k-blocks of grid features: up to 64, fewer are zero-padded (16 levels x 2 = 32 features,
+    // the GridEncoder's own default, Z/gridencoder/grid.py:96-110, included)
+    const uint32_t Fp32 = F <= 64 ? 64 : ((F + 31) / 32) * 32;
+    const Lin d0 = lin_from(d.density0), d2 = lin_from(d.density2);
+    TapeBuilder trunk;
+    // density trunk
+    trunk.add(d0.w, 64, Fp32, crit);
+    push_bias(d.density0.bias, 64, 64);
+    trunk.add(d2.w, fold ? 32 : a.WB, 64, crit);
+    push_bias(d.density2.bias, fold ? 32 : a.WB, fold ? 32 : a.WB);
+    // heads (nlr_tape_heads); the pass-through weights of no_sem_layer go into the rows of the semantic head
+    Lin s0, s2, i0, i2;
+    if (sem_layer) {
+        if ((rc = check_linear(d.sem0, 64, a.WB, "sem_layer.0"))) return rc;
+        if ((rc = check_linear(d.sem2, d.class_num, 64, "sem_layer.2"))) return rc;
+        s0 = lin_from(d.sem0), s2 = lin_from(d.sem2);
+    }
+    if (a.use_int) {
+        if ((rc = check_linear(d.int0, 64, a.WB, "intensity_layer.0"))) return rc;
+        if ((rc = check_linear(d.int2, 1, 64, "intensity_layer.2"))) return rc;
+        a.int_row = a.K;
+        i0 = lin_from(d.int0), i2 = lin_from(d.int2);
+    }
+    TapeHeads<float, 0> hd = nlr_tape_heads<float, 0>(a.WB, a.K, d.use_semantic ? &s0 : nullptr, &s2, a.use_int ? &i0 : nullptr, &i2);
+    if (sem_pass)
+        for (uint32_t c = 0; c < d.class_num; ++c) {
+            hd.h1.at(c, 1 + c) = 1.0f;
+            hd.h1.at(32 + c, 1 + c) = -1.0f;
+            hd.h2.at(c, c) = 1.0f;
+            hd.h2.at(c, 32 + c) = -1.0f;
+        }
+    if (a.HT) {
+        const uint32_t HH = a.HT * 32;
+        if (fold) trunk.add(fold_w2(hd.h1, 0, d.density2, hd.b1), HH, 64, crit);
+        else trunk.add(hd.h1, HH, a.WB, crit);
+        trunk.add(hd.h2, 32, HH, crit);
+    }
+    push_bias(hd.b1.data(), a.HT * 32, a.HT * 32);
+    push_bias(hd.b2.data(), 32, 32);
+    // view MLP.  Input of layer 0 = [bottleneck (WB) | dir_enc (E)]; of layer 1 = [x (W) | bottleneck | dir_enc]
+    // (models.py:1223-1228).  The E dir-encoding columns are zero-padded to one 32-feature k-block.
+    const uint32_t in0 = a.WB + a.E, in1 = a.W + in0;
+    if ((rc = check_linear(d.view[0], a.W, in0, "lin_second_stage_0"))) return rc;
+    if ((rc = check_linear(d.view[1], a.W, in1, "lin_second_stage_1"))) return rc;
+    NLR_CHECK_ARG(a.E <= 32, "deg_view %u gives %u > 32 direction features -- no fused path", a.deg, a.E);
+    const Lin v0 = lin_from(d.view[0]), v1 = lin_from(d.view[1]);
+    TapeBuilder v01;
+    if (fold) {  // layer 0 over [h | dir_enc], layer 1 over [x | h | dir_enc]
+        std::vector<float> c0 = v0.b, c1 = v1.b;
+        Mat f0(a.W, 64 + a.E), f1(a.W, a.W + 64 + a.E);
+        f0.paste(0, 0, fold_w2(v0.w, 0, d.density2, c0));
+        f0.paste(0, 64, v0.w.slice(0, a.W, a.WB, a.E));
+        f1.paste(0, 0, v1.w.slice(0, a.W, 0, a.W));
+        f1.paste(0, a.W, fold_w2(v1.w, a.W, d.density2, c1));
+        f1.paste(0, a.W + 64, v1.w.slice(0, a.W, a.W + a.WB, a.E));
+        v01.add(f0, a.W, 64 + 32, view);
+        push_bias(c0.data(), a.W, a.W);
+        v01.add(f1, a.W, a.W + 64 + 32, view);
+        push_bias(c1.data(), a.W, a.W);
+    } else {
+        v01.add(v0.w, a.W, a.WB + 32, view);
+        push_bias(d.view[0].bias, a.W, a.W);
+        v01.add(v1.w, a.W, a.W + a.WB + 32, view);
+        push_bias(d.view[1].bias, a.W, a.W);
+    }
+    TapeBuilder tb;
+    for (int half = 0; half < (prec == NLR_PREC_F32 ? 1 : 2); ++half) tb.append(trunk), tb.append(v01);
+    for (uint32_t l = 2; l < a.D; ++l) {
+        char nm[64];
+        snprintf(nm, sizeof(nm), "lin_second_stage_%u", l);
+        if ((rc = check_linear(d.view[l], a.W, a.W, nm))) return rc;
+        tb.add(lin_from(d.view[l]).w, a.W, a.W, view);
+        push_bias(d.view[l].bias, a.W, a.W);
+    }
+    if ((rc = check_linear(d.rgb_layer, 3, a.W, "rgb_layer"))) return rc;
+    tb.add(lin_from(d.rgb_layer).w, 16, a.W, view, 1);
+    push_bias(d.rgb_layer.bias, 3, 32);
+    NLR_CHECK_ARG(a.bias.size() <= 3072, "bias block of %zu floats exceeds the 3072-float LDS reservation (view MLP too deep / wide)", a.bias.size());
+    // what was built against what the kernel will consume
+    const MlpProgram PG = nlr_mlp_program(a.W / 32, a.WB / 32, Fp32 / 32, a.HT, prec, 0);
+    if ((rc = nlr_tape_check("NerfMLP bias block (floats)", a.bias.size(), PG.bias_end(a.D)))) return rc;
+    if ((rc = nlr_tape_check("NerfMLP tape (fragments)", tb.frags(), PG.frags(a.D)))) return rc;
+    a.tape_chunks = tb.finish();
+    a.tape.swap(tb.bytes);
+    if (prec == NLR_PREC_FAST) {  // the LiDAR-only instances' tape (nlr_mlp_kernel.h, CM = 2): same fragments, same slack
+        TapeBuilder tl;
+        tl.append(trunk), tl.append(trunk);
+        const MlpProgram PL = nlr_mlp_program(a.W / 32, a.WB / 32, Fp32 / 32, a.HT, prec, 2);
+        if ((rc = nlr_tape_check("NerfMLP LiDAR-only tape (fragments)", tl.frags(), PL.frags(a.D)))) return rc;
+        a.tape_lidar_chunks = tl.finish();
+        a.tape_lidar.swap(tl.bytes);
+    }
     return NLR_OK;
 }
 
@@ -228,8 +336,8 @@ static int build_level(NlrModel *m, LevelModel &lv, const NlrMlpDesc &d, uint32_
         lv.max_jitter = mj;
         if ((rc = dev_upload(m, u.data(), S * sizeof(float), (void **)&lv.u_rand))) return rc;
     }
-    if ((rc = check_linear(d.density0, 64, lv.F, "density_layer.0"))) return rc;
     if (lv.is_prop) {
+        if ((rc = check_linear(d.density0, 64, lv.F, "density_layer.0"))) return rc;
         if ((rc = check_linear(d.density2, 1, 64, "density_layer.2 (PropMLP)"))) return rc;
         if ((rc = dev_upload(m, d.density0.weight, (size_t)64 * lv.F * 4, (void **)&lv.p_w1))) return rc;
         if ((rc = dev_upload(m, d.density0.bias, 64 * 4, (void **)&lv.p_b1))) return rc;
@@ -237,165 +345,16 @@ static int build_level(NlrModel *m, LevelModel &lv, const NlrMlpDesc &d, uint32_
         lv.p_b2 = d.density2.bias[0];
         return NLR_OK;
     }
-    // ---- NerfMLP
-    lv.W = d.net_width_viewdirs;
-    lv.WB = d.bottleneck_width;
-    lv.D = d.net_depth_viewdirs;
-    lv.deg = d.deg_view;
-    lv.E = 3 + 6 * d.deg_view;
-    lv.rgb_premul = d.rgb_premultiplier;
-    lv.rgb_bias = d.rgb_bias;
-    lv.rgb_padding = d.rgb_padding;
-    if (lv.D < 2 || d.skip_layer_dir != 0 || lv.D > NLR_MAX_VIEW_DEPTH)
-        NLR_FAIL(NLR_ERR_UNSUPPORTED, "view MLP: fused path needs net_depth_viewdirs in [2,%d] and skip_layer_dir = 0 (got %u, %u)",
-                 NLR_MAX_VIEW_DEPTH, lv.D, d.skip_layer_dir);
-    if (lv.W % 32 || lv.WB % 32) NLR_FAIL(NLR_ERR_UNSUPPORTED, "view MLP: widths must be multiples of 32");
-    if (lv.F % 4) NLR_FAIL(NLR_ERR_UNSUPPORTED, "NerfMLP: L*C = %u must be a multiple of 4", lv.F);
-    if ((rc = check_linear(d.density2, lv.WB, 64, "density_layer.2"))) return rc;
-    // use_semantic with no_sem_layer (models.py:1133): the logits are channels [1, 1+K) of the bottleneck.  They reach the
-    // softmax through the same two head GEMMs as a learned sem_layer, with pass-through weights that are exact in the
-    // split-bf16 / f32 arithmetic: hidden rows c and 32 + c hold relu(+x_{1+c}) and relu(-x_{1+c}), output row c their difference.
-    const bool sem_layer = d.use_semantic && !d.no_sem_layer;
-    const bool sem_pass = d.use_semantic && d.no_sem_layer;
-    if (sem_pass) NLR_CHECK_ARG(d.class_num <= 32 && 1 + d.class_num <= d.bottleneck_width, "no_sem_layer: class_num %u does not fit", d.class_num);
-    lv.K = d.use_semantic ? d.class_num : 0;
-    lv.use_int = d.use_intensity != 0;
-    lv.HT = (d.use_semantic ? 2 : 0) + (lv.use_int ? 2 : 0);
-    NLR_CHECK_ARG(lv.K + (lv.use_int ? 1 : 0) <= 32, "class_num %u (+intensity) exceeds one 32-row output tile", lv.K);
-
-    lv.prec = prec;
-    const int crit = (prec == NLR_PREC_FAST) ? TAPE_X3 : TAPE_F32;   // density trunk + heads
-    const int view = (prec == NLR_PREC_F32) ? TAPE_F32 : TAPE_BF16;  // view MLP
-    // NLR_PREC_FAST: density_layer.2 is multiplied into the layers that read the bottleneck (fold_w2), which then read the 64-wide
-    // hidden vector of the trunk; D2 keeps its first unit (row 0 = the raw density).  The other two precisions are the exact-parity
-    // modes and keep the reference's layers as they are.
-    const bool fold = prec == NLR_PREC_FAST;
-    // The tile's program (nlr_mlp_kernel.h): bf16 view MLP: [T V0 V1 | T V0 V1 | hidden.. | RGB] (the trunk + heads T and view
-    // layers 0/1 run once per 32-sample half); exact-f32 chain: [T V0 V1 | hidden.. | RGB], consumed once per half.
-    std::vector<float> bias;  // b_d0 | b_d2 (fold: its first 32 rows) | b_h1 | b_h2 | view0 | view1 | view2.. | rgb, each padded to whole units of 32
-    auto push_bias = [&](const float *b, uint32_t n, uint32_t pad) {
-        for (uint32_t i = 0; i < pad; ++i) bias.push_back(i < n ? b[i] : 0.0f);
-    };
-    // the kernel instances take two 32-feature k-blocks of grid features: up to 64, fewer are zero-padded (16 levels x 2 = 32 features,
-    // the GridEncoder's own default, Z/gridencoder/grid.py:96-110, included)
-    const uint32_t Fp32 = lv.F <= 64 ? 64 : ((lv.F + 31) / 32) * 32;
-    TapeBuilder trunk;
-    // density trunk
-    trunk.add(mat_from(d.density0, 0, lv.F), 64, Fp32, crit);
-    push_bias(d.density0.bias, 64, 64);
-    trunk.add(mat_from(d.density2, 0, 64), fold ? 32 : lv.WB, 64, crit);
-    push_bias(d.density2.bias, fold ? 32 : lv.WB, fold ? 32 : lv.WB);
-    // heads: [sem0 ; int0] stacked, then a block-diagonal [sem2 | 0 ; 0 | int2] into one 32-row unit
-    if (lv.HT) {
-        const uint32_t HH = lv.HT * 32;
-        Mat h1(HH, lv.WB), h2(32, HH);
-        std::vector<float> b1(HH, 0.0f), b2(32, 0.0f);
-        uint32_t r0 = 0;
-        if (sem_layer) {
-            if ((rc = check_linear(d.sem0, 64, lv.WB, "sem_layer.0"))) return rc;
-            if ((rc = check_linear(d.sem2, d.class_num, 64, "sem_layer.2"))) return rc;
-            for (uint32_t r = 0; r < 64; ++r) {
-                for (uint32_t c = 0; c < lv.WB; ++c) h1.at(r0 + r, c) = d.sem0.weight[(size_t)r * lv.WB + c];
-                b1[r0 + r] = d.sem0.bias[r];
-            }
-            for (uint32_t r = 0; r < d.class_num; ++r) {
-                for (uint32_t c = 0; c < 64; ++c) h2.at(r, r0 + c) = d.sem2.weight[(size_t)r * 64 + c];
-                b2[r] = d.sem2.bias[r];
-            }
-            r0 += 64;
-        }
-        if (sem_pass) {
-            for (uint32_t c = 0; c < d.class_num; ++c) {
-                h1.at(r0 + c, 1 + c) = 1.0f;
-                h1.at(r0 + 32 + c, 1 + c) = -1.0f;
-                h2.at(c, r0 + c) = 1.0f;
-                h2.at(c, r0 + 32 + c) = -1.0f;
-            }
-            r0 += 64;
-        }
-        if (lv.use_int) {
-            if ((rc = check_linear(d.int0, 64, lv.WB, "intensity_layer.0"))) return rc;
-            if ((rc = check_linear(d.int2, 1, 64, "intensity_layer.2"))) return rc;
-            lv.int_row = lv.K;
-            for (uint32_t r = 0; r < 64; ++r) {
-                for (uint32_t c = 0; c < lv.WB; ++c) h1.at(r0 + r, c) = d.int0.weight[(size_t)r * lv.WB + c];
-                b1[r0 + r] = d.int0.bias[r];
-            }
-            for (uint32_t c = 0; c < 64; ++c) h2.at(lv.int_row, r0 + c) = d.int2.weight[c];
-            b2[lv.int_row] = d.int2.bias[0];
-        }
-        if (fold) trunk.add(fold_w2(h1, 0, d.density2, b1), HH, 64, crit);
-        else trunk.add(h1, HH, lv.WB, crit);
-        push_bias(b1.data(), HH, HH);
-        trunk.add(h2, 32, HH, crit);
-        push_bias(b2.data(), 32, 32);
-    } else {
-        push_bias(nullptr, 0, 32);  // keeps the block layout of the kernel (OB_H2 slot)
-    }
-    // view MLP.  Input of layer 0 = [bottleneck (WB) | dir_enc (E)]; of layer 1 = [x (W) | bottleneck | dir_enc]
-    // (models.py:1223-1228).  The E dir-encoding columns are zero-padded to one 32-feature k-block.
-    const uint32_t in0 = lv.WB + lv.E, in1 = lv.W + in0;
-    if ((rc = check_linear(d.view[0], lv.W, in0, "lin_second_stage_0"))) return rc;
-    if ((rc = check_linear(d.view[1], lv.W, in1, "lin_second_stage_1"))) return rc;
-    NLR_CHECK_ARG(lv.E <= 32, "deg_view %u gives %u > 32 direction features -- no fused path", lv.deg, lv.E);
-    TapeBuilder v01;
-    if (fold) {  // layer 0 over [h | dir_enc], layer 1 over [x | h | dir_enc]
-        const Mat v0 = mat_from(d.view[0], 0, in0), v1 = mat_from(d.view[1], 0, in1);
-        std::vector<float> c0(d.view[0].bias, d.view[0].bias + lv.W), c1(d.view[1].bias, d.view[1].bias + lv.W);
-        const Mat a0 = fold_w2(v0, 0, d.density2, c0), a1 = fold_w2(v1, lv.W, d.density2, c1);
-        Mat f0(lv.W, 64 + lv.E), f1(lv.W, lv.W + 64 + lv.E);
-        for (uint32_t r = 0; r < lv.W; ++r) {
-            for (uint32_t c = 0; c < 64; ++c) f0.at(r, c) = a0.get(r, c), f1.at(r, lv.W + c) = a1.get(r, c);
-            for (uint32_t c = 0; c < lv.E; ++c) f0.at(r, 64 + c) = v0.get(r, lv.WB + c), f1.at(r, lv.W + 64 + c) = v1.get(r, lv.W + lv.WB + c);
-            for (uint32_t c = 0; c < lv.W; ++c) f1.at(r, c) = v1.get(r, c);
-        }
-        v01.add(f0, lv.W, 64 + 32, view);
-        push_bias(c0.data(), lv.W, lv.W);
-        v01.add(f1, lv.W, lv.W + 64 + 32, view);
-        push_bias(c1.data(), lv.W, lv.W);
-    } else {
-        v01.add(mat_from(d.view[0], 0, in0), lv.W, lv.WB + 32, view);
-        push_bias(d.view[0].bias, lv.W, lv.W);
-        v01.add(mat_from(d.view[1], 0, in1), lv.W, lv.W + lv.WB + 32, view);
-        push_bias(d.view[1].bias, lv.W, lv.W);
-    }
-    TapeBuilder tb;
-    auto append = [&](const TapeBuilder &x) { tb.bytes.insert(tb.bytes.end(), x.bytes.begin(), x.bytes.end()); };
-    if (prec == NLR_PREC_F32) {
-        append(trunk);
-        append(v01);
-    } else {
-        append(trunk);
-        append(v01);
-        append(trunk);
-        append(v01);
-    }
-    for (uint32_t l = 2; l < lv.D; ++l) {
-        char nm[64];
-        snprintf(nm, sizeof(nm), "lin_second_stage_%u", l);
-        if ((rc = check_linear(d.view[l], lv.W, lv.W, nm))) return rc;
-        tb.add(mat_from(d.view[l], 0, lv.W), lv.W, lv.W, view);
-        push_bias(d.view[l].bias, lv.W, lv.W);
-    }
-    if ((rc = check_linear(d.rgb_layer, 3, lv.W, "rgb_layer"))) return rc;
-    tb.add(mat_from(d.rgb_layer, 0, lv.W), 16, lv.W, view, 1);
-    push_bias(d.rgb_layer.bias, 3, 32);
-    tb.pad_to_chunk();
-    lv.bias_count = (uint32_t)bias.size();
-    NLR_CHECK_ARG(lv.bias_count <= 3072, "bias block of %u floats exceeds the 3072-float LDS reservation (view MLP too deep / wide)", lv.bias_count);
-    if ((rc = dev_upload(m, bias.data(), bias.size() * 4, (void **)&lv.bias_all))) return rc;
-    lv.tape_chunks = (uint32_t)(tb.bytes.size() / NLR_TAPE_CHUNK);
-    tb.bytes.resize(tb.bytes.size() + 3 * NLR_TAPE_CHUNK, 0);  // slack: the kernel prefetches up to 3 chunks past the end
-    if ((rc = dev_upload(m, tb.bytes.data(), tb.bytes.size(), &lv.tape))) return rc;
-    if (prec == NLR_PREC_FAST) {  // the LiDAR-only instances' tape (nlr_mlp_kernel.h, CM = 2): same fragments, same 3-chunk slack
-        TapeBuilder tl;
-        tl.bytes.insert(tl.bytes.end(), trunk.bytes.begin(), trunk.bytes.end());
-        tl.bytes.insert(tl.bytes.end(), trunk.bytes.begin(), trunk.bytes.end());
-        tl.pad_to_chunk();
-        lv.tape_lidar_chunks = (uint32_t)(tl.bytes.size() / NLR_TAPE_CHUNK);
-        tl.bytes.resize(tl.bytes.size() + 3 * NLR_TAPE_CHUNK, 0);
-        if ((rc = dev_upload(m, tl.bytes.data(), tl.bytes.size(), &lv.tape_lidar))) return rc;
-    }
+    // ---- NerfMLP: assemble on the host, upload
+    MlpTapes a;
+    if ((rc = mlp_assemble(d, lv.F, prec, a))) return rc;
+    static_cast<MlpShape &>(lv) = a;
+    lv.bias_count = (uint32_t)a.bias.size();
+    lv.tape_chunks = a.tape_chunks;
+    lv.tape_lidar_chunks = a.tape_lidar_chunks;
+    if ((rc = dev_upload(m, a.bias.data(), a.bias.size() * 4, (void **)&lv.bias_all))) return rc;
+    if ((rc = dev_upload(m, a.tape.data(), a.tape.size(), &lv.tape))) return rc;
+    if (prec == NLR_PREC_FAST && (rc = dev_upload(m, a.tape_lidar.data(), a.tape_lidar.size(), &lv.tape_lidar))) return rc;
     return NLR_OK;
 }
 

@@ -7,6 +7,7 @@
 #include <string.h>
 
 #include "../../include/nerflidar_hip.h"
+#include "nlr_tape.h"
 
 #define NLR_EPS 1.1920928955078125e-07f  // torch.finfo(float32).eps
 #define NLR_WAVE 64
@@ -34,6 +35,12 @@ void nlr_set_error(const char *fmt, ...);
         if (e_ != hipSuccess)                                                              \
             NLR_FAIL(NLR_ERR_HIP, "launch of %s failed: %s", name, hipGetErrorString(e_)); \
     } while (0)
+// what a host builder made of a weight tape or bias block against what the kernel's program (nlr_tape.h) will consume
+static inline int nlr_tape_check(const char *what, size_t built, size_t program) {
+    char msg[256];
+    if (!nlr_tape_matches(what, built, program, msg, sizeof(msg))) NLR_FAIL(NLR_ERR_UNSUPPORTED, "%s", msg);
+    return NLR_OK;
+}
 
 // ---- per-level grid constants passed by value as kernel arguments --------------------------
 struct GridParams {

@@ -37,6 +37,7 @@
 //     (the whole chain at half width, twice per tile).
 #pragma once
 #include "nlr_kernels.h"
+#include "nlr_tape.h"  // NLR_CHUNK_FRAGS, the tile programs
 
 #include <type_traits>
 
@@ -54,7 +55,6 @@
 //            these requests run into chunk c+1, so no LDS latency is exposed at a chunk boundary.
 // GEMMs follow each other on the tape without padding: a GEMM that starts at position F0 of a chunk simply continues the
 // position count (all GEMM sizes are compile-time); only the end of a tile's program is padded to a chunk boundary.
-#define NLR_CHUNK_FRAGS 32                       // fragments (1 KiB each) per chunk
 #define NLR_CHUNK_SLOTS (NLR_CHUNK_FRAGS * 64)   // uint4 slots per chunk
 #define NLR_NBUF 3
 #ifndef NLR_SIG_F
@@ -514,34 +514,21 @@ __global__ void __launch_bounds__(256, 1) nlr_mlp_kernel(MlpParams P) {
     // FOLD (NLR_PREC_FAST): density_layer.2 has no activation behind it, so the bottleneck b = W2.h + c2 is linear in the trunk's hidden
     // vector h = relu(W0.f + c0), and every consumer of b is linear in b in front of its own ReLU.  build_level multiplies W2 into the
     // head layer H1, view layer 0 and the skip columns of view layer 1 once per model; the kernel never forms the bottleneck: those
-    // three GEMMs read the KB = 2 k-blocks of h, and D2 keeps the one output unit that holds row 0, the raw density (same fragments,
-    // same MFMA order as the unfolded unit 0: density and everything derived from it keep their bits).
-    constexpr bool FOLD = X3;
-    constexpr int KB = FOLD ? 2 : BW;    // k-blocks of the vector the heads and the view layers read: h (folded) or the bottleneck
-    constexpr int D2U = FOLD ? 1 : BW;   // output units of D2
-    // bias block offsets (floats)
-    constexpr int OB_D0 = 0, OB_D2 = 64, OB_H1 = OB_D2 + D2U * 32, OB_H2 = OB_H1 + HT * 32, OB_V0 = OB_H2 + 32;
-    constexpr int OB_V1 = OB_V0 + WT * 32, OB_VL = OB_V1 + WT * 32;
-    // ---- the tile's program on the tape (fragments; must match build_level in nlr_api.hip)
-    constexpr int TF = X3 ? 2 : 1;                        // fragments per step in the trunk / heads
-    constexpr int TK = X3 ? 1 : 2;                        // k-groups per 32 input features in the trunk / heads
-    constexpr int VK = VIEW_F32 ? 2 : 1;                  // ... in the view MLP
-    constexpr int FR_D0 = 2 * (FT * TK) * 2 * TF, FR_D2 = D2U * (2 * TK) * 2 * TF;
-    constexpr int FR_H1 = HT * (KB * TK) * 2 * TF, FR_H2 = HT > 0 ? (HT * TK) * 2 * TF : 0;
-    constexpr int FR_T = FR_D0 + FR_D2 + FR_H1 + FR_H2;   // trunk + heads, one half
-    constexpr int FR_V0 = WT * ((KB + 1) * VK) * 2, FR_V1 = WT * ((WT + KB + 1) * VK) * 2;
-    constexpr int FR_HL = WT * (WT * VK) * 2, FR_RGB = (WT * VK);
-    static_assert(FR_HL % NLR_CHUNK_FRAGS == 0, "hidden view layers must cover whole chunks (width 128 or 256)");
-    // bf16 view MLP: [T V0 V1 | T V0 V1 | hidden x (depth-2) | RGB];  f32 view MLP: [T V0 V1 | hidden | RGB] once per half
-    constexpr int FR_HALF = LIDAR ? FR_T : FR_T + FR_V0 + FR_V1;
-    constexpr int F_HID = VIEW_F32 ? FR_HALF : 2 * FR_HALF;
-    constexpr int F_END = F_HID + FR_RGB;                 // (+ hidden layers: whole chunks)
+    // three GEMMs read the PG.KB = 2 k-blocks of h, and D2 keeps the one output unit (PG.D2U = 1) that holds row 0, the raw density (same
+    // fragments, same MFMA order as the unfolded unit 0: density and everything derived from it keep their bits).
+    // PG: the tile's program on the tape and the offsets of the bias block (nlr_tape.h; the host checks what it built against the same table)
+    constexpr MlpProgram PG = nlr_mlp_program(WT, BW, FT, HT, PREC, CM);
+    // (named as plain constants: used through PG inside the GEMM lambdas, 14 instances came out with another register allocation)
+    constexpr int KB = PG.KB, FR_D0 = PG.FR_D0, FR_D2 = PG.FR_D2, FR_H1 = PG.FR_H1, FR_T = PG.FR_T, FR_V0 = PG.FR_V0, FR_V1 = PG.FR_V1;
+    constexpr int FR_HALF = PG.FR_HALF, F_HID = PG.F_HID, F_END = PG.F_END;
+    constexpr int OB_D0 = PG.OB_D0, OB_D2 = PG.OB_D2, OB_H1 = PG.OB_H1, OB_H2 = PG.OB_H2, OB_V0 = PG.OB_V0, OB_V1 = PG.OB_V1, OB_VL = PG.OB_VL;
+    static_assert(PG.FR_HL % NLR_CHUNK_FRAGS == 0, "hidden view layers must cover whole chunks (width 128 or 256)");
     // The next tile's inputs are requested by LDS-DMA at tape position STAGE_AT of the tile's program and read at the start of the next
     // tile with no wait of their own: a signal() of the tape (position NLR_SIG_F of every chunk, s_waitcnt vmcnt(0): it retires every
     // load of the wave) has to lie between the request and the end of the program, padding steps included.  SIG_AT is the first one.
     // The hidden view layers are whole chunks, so with at least one of them the condition holds; without one (view depth 2) and for
     // the LiDAR-only program it depends on where the request falls in its chunk, and a tile that has no such signal waits itself.
-    constexpr int STAGE_AT = LIDAR ? FR_T : F_HID, PROG_END = nlr_ceil_div(LIDAR ? 2 * FR_T : F_END, NLR_CHUNK_FRAGS) * NLR_CHUNK_FRAGS;
+    constexpr int STAGE_AT = LIDAR ? FR_T : F_HID, PROG_END = nlr_ceil_div(PG.frags(2), NLR_CHUNK_FRAGS) * NLR_CHUNK_FRAGS;
     constexpr int SIG_AT = STAGE_AT <= NLR_SIG_F ? NLR_SIG_F : nlr_ceil_div(STAGE_AT - NLR_SIG_F, NLR_CHUNK_FRAGS) * NLR_CHUNK_FRAGS + NLR_SIG_F;
     constexpr bool STAGE_SIG = SIG_AT < PROG_END;         // (without hidden layers)
     static_assert(!LIDAR || STAGE_SIG, "LiDAR-only: no tape signal between the request of the next tile's inputs and their first read");
@@ -697,8 +684,7 @@ __global__ void __launch_bounds__(256, 1) nlr_mlp_kernel(MlpParams P) {
             const uint32_t smp = base + (2 * h + n) * 16 + col;
             const bool valid = smp < P.M;
             if (q == 0 && valid) {
-                const float x = raw[n] + P.density_bias;
-                P.density[smp] = x > 20.0f ? x : log1pf(expf(x));  // F.softplus (beta=1, threshold=20), models.py:1116
+                P.density[smp] = nlr_softplus(raw[n] + P.density_bias);
             }
             if constexpr (HT > 0) {
                 if (P.K > 0) {  // softmax over rows [0,K): 8 rows in this lane, the rest in the 3 other lanes of the column

@@ -101,25 +101,14 @@ __global__ void __launch_bounds__(256, 1) nlr_mlp_train_kernel(TrainParams P) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int col = lane & 15, q = lane >> 4;
     constexpr int HTA = HT > 0 ? HT : 1;
-    constexpr int OB_D0 = 0, OB_D2 = 64, OB_H1 = OB_D2 + BW * 32, OB_H2 = OB_H1 + HT * 32, OB_V0 = OB_H2 + 32;
-    constexpr int OB_V1 = OB_V0 + WT * 32, OB_VL = OB_V1 + WT * 32;
+    // the forward and backward programs on the tapes and the offsets of the bias block (nlr_tape.h; plan_build checks against the same table)
+    constexpr TrainProgram PG = nlr_train_program(WT, BW, FT, HT, VIEW);
+    constexpr int VW = VIEW ? WT : 0;  // k-blocks of view gradients in BIG
+    static_assert(PG.FR_HL % NLR_CHUNK_FRAGS == 0, "hidden view layers must cover whole chunks");
     // columns of acts / gacts (the depth is a run-time value: the two blocks behind the view layers are placed from P.act_w)
     constexpr TrainCols CC = nlr_train_cols(WT * 32, BW * 32, HT, 0);
     constexpr uint32_t C_HID = CC.c_hid, C_HBE = CC.c_hbe, C_Q = CC.c_q, C_X = CC.c_x;
     const uint32_t W = WT * 32, ld = P.act_w, gld = P.act_w + 64, C_LO = P.act_w, C_O = P.act_w + 32;
-    // forward program (fragments)
-    constexpr int FR_D0 = 2 * FT * 2, FR_D2 = BW * 2 * 2, FR_H1 = HT * BW * 2, FR_H2 = HT > 0 ? HT * 2 : 0;
-    constexpr int FR_T = FR_D0 + FR_D2 + FR_H1 + FR_H2;
-    constexpr int FR_V0 = WT * (BW + 1) * 2, FR_V1 = WT * (WT + BW + 1) * 2, FR_HL = WT * WT * 2, FR_RGB = WT;
-    static_assert(FR_HL % NLR_CHUNK_FRAGS == 0, "hidden view layers must cover whole chunks");
-    constexpr int FF_HID = FR_T + FR_V0 + FR_V1, FF_END = FF_HID + FR_RGB;
-    // backward program: RGB^T (WT units x 1 k-block), hidden^T, V1a^T (WT x WT), H2^T (HT x 1), BIG (BW x (2 WT + HT + 1)), D2^T (2 x BW), D0^T (FT x 2)
-    // (VW = 0 without the view MLP: the program starts at H2^T and BIG shrinks to [H1^T | e_0])
-    constexpr int VW = VIEW ? WT : 0;
-    constexpr int BR_RGB = VW * 1 * 2, BR_V1A = VW * VW * 2, BR_H2 = HT * 1 * 2, BR_BIG = BW * (2 * VW + HT + 1) * 2, BR_D2 = 2 * BW * 2,
-                  BR_D0 = FT * 2 * 2;
-    constexpr int BF_V1A = BR_RGB, BF_H2 = BF_V1A + BR_V1A, BF_BIG = BF_H2 + BR_H2, BF_D2 = BF_BIG + BR_BIG, BF_D0 = BF_D2 + BR_D2,
-                  BF_END = BF_D0 + BR_D0;  // (+ hidden layers between RGB^T and V1a^T: whole chunks)
 
     const uint32_t ntiles = (P.M - P.row0 + 127) / 128;
     if (!BWD)
@@ -186,7 +175,7 @@ __global__ void __launch_bounds__(256, 1) nlr_mlp_train_kernel(TrainParams P) {
             }
             BT<2> hidb[2];
             nlr_gemm<2, FT, 2, 2, 1, 0, 9>(
-                tp, bias_at(ic<OB_D0>{}),
+                tp, bias_at(ic<PG.OB_D0>{}),
                 chain(fb),
                 [&](auto o, auto p, const Unit<2> &u) {
                     constexpr int O = decltype(o)::value, Pc = decltype(p)::value;
@@ -194,8 +183,8 @@ __global__ void __launch_bounds__(256, 1) nlr_mlp_train_kernel(TrainParams P) {
                     else nlr_store_bt(P.acts, ld, s0, P.M, col, q, C_HID + 32 * O, hidb[O]);
                 });
             float raw[2] = {0.0f, 0.0f};
-            nlr_gemm<BW, 2, 2, 2, 1, FR_D0, 9>(
-                tp, bias_at(ic<OB_D2>{}),
+            nlr_gemm<BW, 2, 2, 2, 1, PG.FR_D0, 9>(
+                tp, bias_at(ic<PG.OB_D2>{}),
                 chain(hidb),
                 [&](auto o, auto p, const Unit<2> &u) {
                     constexpr int O = decltype(o)::value, Pc = decltype(p)::value;
@@ -210,16 +199,16 @@ __global__ void __launch_bounds__(256, 1) nlr_mlp_train_kernel(TrainParams P) {
             nlr_zero(lo);
             if constexpr (HT > 0) {
                 BT<2> qb[HTA];
-                nlr_gemm<HT, BW, 2, 2, 1, FR_D0 + FR_D2, 9>(
-                    tp, bias_at(ic<OB_H1>{}),
+                nlr_gemm<HT, BW, 2, 2, 1, PG.FR_D0 + PG.FR_D2, 9>(
+                    tp, bias_at(ic<PG.OB_H1>{}),
                     chain(hbe),
                     [&](auto o, auto p, const Unit<2> &u) {
                         constexpr int O = decltype(o)::value, Pc = decltype(p)::value;
                         if constexpr (Pc < 8) nlr_pack_piece<true, Pc, 0>(qb[O], u);
                         else nlr_store_bt(P.acts, ld, s0, P.M, col, q, C_Q + 32 * O, qb[O]);
                     });
-                nlr_gemm<1, HT, 2, 2, 1, FR_D0 + FR_D2 + FR_H1, 1>(
-                    tp, bias_at(ic<OB_H2>{}),
+                nlr_gemm<1, HT, 2, 2, 1, PG.FR_D0 + PG.FR_D2 + PG.FR_H1, 1>(
+                    tp, bias_at(ic<PG.OB_H2>{}),
                     chain(qb),
                     [&](auto, auto, const Unit<2> &u) { lo = u; });
             }
@@ -229,8 +218,7 @@ __global__ void __launch_bounds__(256, 1) nlr_mlp_train_kernel(TrainParams P) {
                 const uint32_t smp = s0 + 16 * n + col;
                 const bool valid = smp < P.M;
                 if (q == 0 && valid) {
-                    const float x = raw[n] + P.density_bias;
-                    P.density[smp] = x > 20.0f ? x : log1pf(expf(x));
+                    P.density[smp] = nlr_softplus(raw[n] + P.density_bias);
                 }
                 if constexpr (HT > 0) {
                     if (P.K > 0) {
@@ -280,20 +268,20 @@ __global__ void __launch_bounds__(256, 1) nlr_mlp_train_kernel(TrainParams P) {
                         }
                     }
                 }
-                nlr_pad<FR_T % NLR_CHUNK_FRAGS>(tp);
+                nlr_pad<PG.FR_T % NLR_CHUNK_FRAGS>(tp);
             } else {
                 // view MLP
                 BT<2> x[WT], y[WT];
-                nlr_gemm<WT, BW + 1, 2, 2, 1, FR_T, 9>(
-                    tp, bias_at(ic<OB_V0>{}),
+                nlr_gemm<WT, BW + 1, 2, 2, 1, PG.FR_T, 9>(
+                    tp, bias_at(ic<PG.OB_V0>{}),
                     chain(hbe),
                     [&](auto o, auto p, const Unit<2> &u) {
                         constexpr int O = decltype(o)::value, Pc = decltype(p)::value;
                         if constexpr (Pc < 8) nlr_pack_piece<true, Pc, 0>(x[O], u);
                         else nlr_store_bt(P.acts, ld, s0, P.M, col, q, C_X + 32 * O, x[O]);
                     });
-                nlr_gemm<WT, WT + BW + 1, 2, 2, 1, FR_T + FR_V0, 9>(
-                    tp, bias_at(ic<OB_V1>{}),
+                nlr_gemm<WT, WT + BW + 1, 2, 2, 1, PG.FR_T + PG.FR_V0, 9>(
+                    tp, bias_at(ic<PG.OB_V1>{}),
                     [&](Unit<2> &u, auto g, auto j, const uint4 &f0, const uint4 &, const f32x4 &bj) {
                         constexpr int G = decltype(g)::value, J = decltype(j)::value;
                         if constexpr (G < WT) nlr_mma_bf16<G == 0, 0>(u.a[J], bj, f0, x[G]);
@@ -305,9 +293,9 @@ __global__ void __launch_bounds__(256, 1) nlr_mlp_train_kernel(TrainParams P) {
                         else nlr_store_bt(P.acts, ld, s0, P.M, col, q, C_X + W + 32 * O, y[O]);
                     });
                 for (uint32_t l = 2; l < P.depth; ++l) {
-                    const float *bl = lds_bias + OB_VL + (l - 2) * (WT * 32);
+                    const float *bl = lds_bias + PG.OB_VL + (l - 2) * (WT * 32);
                     const uint32_t cl = C_X + l * W;
-                    nlr_gemm<WT, WT, 2, 2, 1, FF_HID, 9>(
+                    nlr_gemm<WT, WT, 2, 2, 1, PG.FF_HID, 9>(
                         tp, [&](auto o, f32x4(&b)[2]) { bias_rows(bl + 32 * decltype(o)::value, b); },
                         chain(y),
                         [&](auto o, auto p, const Unit<2> &u) {
@@ -319,8 +307,8 @@ __global__ void __launch_bounds__(256, 1) nlr_mlp_train_kernel(TrainParams P) {
                     for (int t = 0; t < WT; ++t) y[t] = x[t];
                 }
                 Unit<2> out1;
-                nlr_gemm<1, WT, 1, 2, 1, FF_HID, 1>(
-                    tp, [&](auto, f32x4(&b)[2]) { bias_rows(lds_bias + OB_VL + (P.depth - 2) * (WT * 32), b); },
+                nlr_gemm<1, WT, 1, 2, 1, PG.FF_HID, 1>(
+                    tp, [&](auto, f32x4(&b)[2]) { bias_rows(lds_bias + PG.OB_VL + (P.depth - 2) * (WT * 32), b); },
                     chain(y),
                     [&](auto, auto, const Unit<2> &u) { out1 = u; });
                 if (q == 0) {
@@ -337,7 +325,7 @@ __global__ void __launch_bounds__(256, 1) nlr_mlp_train_kernel(TrainParams P) {
                         }
                     }
                 }
-                nlr_pad<FF_END % NLR_CHUNK_FRAGS>(tp);
+                nlr_pad<PG.FF_END % NLR_CHUNK_FRAGS>(tp);
             }
         } else {
             // ======================================================= backward ======================================================
@@ -383,7 +371,7 @@ __global__ void __launch_bounds__(256, 1) nlr_mlp_train_kernel(TrainParams P) {
                 }
                 for (uint32_t l = P.depth - 1; l >= 2; --l) {  // hidden layers, transposed: d z_{l-1} = mask(x_{l-1}) W_l^T d z_l
                     const uint32_t cl = C_X + (l - 1) * W;
-                    nlr_gemm<WT, WT, 2, 2, 1, BR_RGB, 9>(
+                    nlr_gemm<WT, WT, 2, 2, 1, PG.BR_RGB, 9>(
                         tp, no_bias,
                         chain(g),
                         mask_store(h, cl));
@@ -391,7 +379,7 @@ __global__ void __launch_bounds__(256, 1) nlr_mlp_train_kernel(TrainParams P) {
                     for (int t = 0; t < WT; ++t) g[t] = h[t];
                 }
                 // g = d z_1.  V1a^T: d z_0 = mask(x_0) W1[:, :W]^T d z_1
-                nlr_gemm<WT, WT, 2, 2, 1, BF_V1A, 9>(
+                nlr_gemm<WT, WT, 2, 2, 1, PG.BF_V1A, 9>(
                     tp, no_bias,
                     chain(g),
                     mask_store(h, C_X));
@@ -449,14 +437,14 @@ __global__ void __launch_bounds__(256, 1) nlr_mlp_train_kernel(TrainParams P) {
                 nlr_pack_all<false, 0>(aux, da);
             }
             if constexpr (HT > 0) {  // H2^T: d (head hidden pre-activation)
-                nlr_gemm<HT, 1, 2, 2, 1, BF_H2, 9>(
+                nlr_gemm<HT, 1, 2, 2, 1, PG.BF_H2, 9>(
                     tp, no_bias,
                     chain(&gin),
                     mask_store(gq, C_Q));
             }
             // BIG: d bottleneck = W1[:, W:W+WB]^T d z_1 + W0[:, :WB]^T d z_0 + H1^T d q + e_0 d raw (without the view MLP: the last two)
             BT<2> gb[BW];
-            nlr_gemm<BW, 2 * VW + HT + 1, 2, 2, 1, BF_BIG, 9>(
+            nlr_gemm<BW, 2 * VW + HT + 1, 2, 2, 1, PG.BF_BIG, 9>(
                 tp, no_bias,
                 [&](Unit<2> &u, auto gg, auto j, const uint4 &f0, const uint4 &, const f32x4 &bj) {
                     constexpr int G = decltype(gg)::value, J = decltype(j)::value;
@@ -472,12 +460,12 @@ __global__ void __launch_bounds__(256, 1) nlr_mlp_train_kernel(TrainParams P) {
                 });
             // D2^T: d (trunk hidden pre-activation)
             BT<2> gh[2];
-            nlr_gemm<2, BW, 2, 2, 1, BF_D2, 9>(
+            nlr_gemm<2, BW, 2, 2, 1, PG.BF_D2, 9>(
                 tp, no_bias,
                 chain(gb),
                 mask_store(gh, C_HID));
             // D0^T: gradient of the grid features, f32 out
-            nlr_gemm<FT, 2, 2, 2, 1, BF_D0, 1>(
+            nlr_gemm<FT, 2, 2, 2, 1, PG.BF_D0, 1>(
                 tp, no_bias,
                 chain(gh),
                 [&](auto o, auto, const Unit<2> &u) {
@@ -492,7 +480,7 @@ __global__ void __launch_bounds__(256, 1) nlr_mlp_train_kernel(TrainParams P) {
                         }
                     }
                 });
-            nlr_pad<BF_END % NLR_CHUNK_FRAGS>(tp);
+            nlr_pad<PG.BF_END % NLR_CHUNK_FRAGS>(tp);
         }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -514,44 +502,19 @@ __global__ void __launch_bounds__(256) nlr_train_pack_kernel(const float *__rest
 }
 
 // ---- plan: shapes, parameter order, index maps ----------------------------------------------------------------------------------
-struct IMat {  // matrix of flat-parameter indices (-1 = structural zero)
-    std::vector<int32_t> a;
-    uint32_t rows = 0, cols = 0;
-    IMat() {}
-    IMat(uint32_t r, uint32_t c) : a((size_t)r * c, -1), rows(r), cols(c) {}
-    int32_t &at(uint32_t r, uint32_t c) { return a[(size_t)r * cols + c]; }
-    int32_t get(uint32_t r, uint32_t c) const { return (r < rows && c < cols) ? a[(size_t)r * cols + c] : -1; }
-};
+typedef TapeMat<int32_t, -1> IMat;  // matrix of flat-parameter indices (-1 = structural zero)
+typedef TapeLinear<int32_t, -1> ILin;
+// one GEMM on an index tape: the walk of the weight tapes (nlr_tape.h) over indices, bf16 k-groups
 static void tape_add(std::vector<int32_t> &t, const IMat &w, uint32_t out_pad, uint32_t in_pad, uint32_t RH = 2) {
-    const uint32_t OT = RH == 2 ? out_pad / 32 : 1, KG = in_pad / 32;
-    for (uint32_t o = 0; o < OT; ++o)
-        for (uint32_t g = 0; g < KG; ++g)
-            for (uint32_t j = 0; j < RH; ++j) {
-                const uint32_t R = RH == 2 ? 2 * o + j : o;
-                for (uint32_t lane = 0; lane < 64; ++lane)
-                    for (uint32_t e = 0; e < 8; ++e) t.push_back(w.get(16 * R + (lane & 15), 32 * g + 16 * (e >> 2) + 4 * (lane >> 4) + (e & 3)));
-            }
+    nlr_tape_walk(w, out_pad, in_pad, 32, RH, [&](const int32_t *v, uint32_t n) { t.insert(t.end(), v, v + n); });
 }
-static void tape_pad(std::vector<int32_t> &t) { t.resize((t.size() + 16383) / 16384 * 16384, -1); }  // 32 KiB of bf16
-
-static IMat lin(uint32_t off, uint32_t rows, uint32_t cols) {
-    IMat m(rows, cols);
-    for (uint32_t r = 0; r < rows; ++r)
-        for (uint32_t c = 0; c < cols; ++c) m.at(r, c) = (int32_t)(off + r * cols + c);
-    return m;
-}
-static IMat transpose(const IMat &w) {
-    IMat t(w.cols, w.rows);
-    for (uint32_t r = 0; r < w.rows; ++r)
-        for (uint32_t c = 0; c < w.cols; ++c) t.at(c, r) = w.a[(size_t)r * w.cols + c];
-    return t;
-}
+static void tape_pad(std::vector<int32_t> &t) { t.resize((t.size() + NLR_CHUNK_BF16 - 1) / NLR_CHUNK_BF16 * NLR_CHUNK_BF16, -1); }
 
 // Everything of a plan that needs no device: the scalars, the layer table and the index maps of the two tapes and of the bias block.
 // Flat parameter order (weights row-major [out, in], then bias), one TrainLinear each:
 //   density_layer.0, density_layer.2, [sem_layer.0, sem_layer.2], [intensity_layer.0, intensity_layer.2], lin_second_stage_0..D-1, rgb_layer
-static void plan_build(NlrTrainPlan *p, uint32_t F, uint32_t W, uint32_t WB, uint32_t D, uint32_t deg_view, uint32_t class_num,
-                       int use_semantic, int use_intensity, std::vector<int32_t> &ft, std::vector<int32_t> &bt, std::vector<int32_t> &bb) {
+static int plan_build(NlrTrainPlan *p, uint32_t F, uint32_t W, uint32_t WB, uint32_t D, uint32_t deg_view, uint32_t class_num,
+                      int use_semantic, int use_intensity, std::vector<int32_t> &ft, std::vector<int32_t> &bt, std::vector<int32_t> &bb) {
     const uint32_t E = 3 + 6 * deg_view;
     p->F = F, p->W = W, p->WB = WB, p->D = D, p->E = E, p->sem = use_semantic != 0, p->inten = use_intensity != 0;
     const uint32_t K = p->K = p->sem ? class_num : 0;
@@ -561,128 +524,108 @@ static void plan_build(NlrTrainPlan *p, uint32_t F, uint32_t W, uint32_t WB, uin
     p->act_w = c.c_lo;
     // ---- the layer table; each entry takes its weight and bias from the flat buffer
     uint32_t off = 0;
-    auto add = [&](uint32_t g_col, uint32_t o_off, uint32_t n_out, uint32_t color, std::initializer_list<TrainBlock> in, uint32_t &b) {
+    auto add = [&](uint32_t g_col, uint32_t o_off, uint32_t n_out, uint32_t color, std::initializer_list<TrainBlock> in) {
         TrainLinear l = {};
         l.g_col = g_col, l.o_off = o_off, l.n_out = n_out, l.color = color;
         uint32_t cols = 0;
         for (const TrainBlock &k : in) l.in[l.n_in++] = k, cols += k.n;
-        l.w_off = off, l.b_off = b = off + n_out * cols;
+        l.w_off = off, l.b_off = off + n_out * cols;
         off = l.b_off + n_out;
         p->linears.push_back(l);
-        return lin(l.w_off, n_out, cols);
+        ILin x;
+        x.w = IMat(n_out, cols);
+        for (size_t i = 0; i < x.w.a.size(); ++i) x.w.a[i] = (int32_t)(l.w_off + i);
+        for (uint32_t i = 0; i < n_out; ++i) x.b.push_back((int32_t)(l.b_off + i));
+        return x;
     };
     const TrainBlock hbe = {NLR_TRAIN_SRC_ACTS, c.c_hbe, WB}, encb = {NLR_TRAIN_SRC_ENC, 0, E};
     auto acts = [](uint32_t col, uint32_t n) { return TrainBlock{NLR_TRAIN_SRC_ACTS, col, n}; };
-    IMat s0, s2, i0, i2;
-    std::vector<IMat> v(D);
-    uint32_t bd0, bd2, bs0 = 0, bs2 = 0, bi0 = 0, bi2 = 0, brgb;
-    std::vector<uint32_t> bv(D);
-    const IMat d0 = add(c.c_hid, 0, 64, 0, {{NLR_TRAIN_SRC_FEATURES, 0, F}}, bd0);
-    const IMat d2 = add(c.c_hbe, 0, WB, 0, {acts(c.c_hid, 64)}, bd2);
+    ILin s0, s2, i0, i2;
+    std::vector<ILin> v(D);
+    const ILin d0 = add(c.c_hid, 0, 64, 0, {{NLR_TRAIN_SRC_FEATURES, 0, F}});
+    const ILin d2 = add(c.c_hbe, 0, WB, 0, {acts(c.c_hid, 64)});
     uint32_t r0 = 0;  // head hidden units: [sem 64][intensity 64]
     if (p->sem) {
-        s0 = add(c.c_q, 0, 64, 0, {hbe}, bs0);
-        s2 = add(c.c_lo, 0, K, 0, {acts(c.c_q, 64)}, bs2);
+        s0 = add(c.c_q, 0, 64, 0, {hbe});
+        s2 = add(c.c_lo, 0, K, 0, {acts(c.c_q, 64)});
         r0 = 64;
     }
     if (p->inten) {
-        i0 = add(c.c_q + r0, 0, 64, 0, {hbe}, bi0);
-        i2 = add(c.c_lo + K, K, 1, 0, {acts(c.c_q + r0, 64)}, bi2);
+        i0 = add(c.c_q + r0, 0, 64, 0, {hbe});
+        i2 = add(c.c_lo + K, K, 1, 0, {acts(c.c_q + r0, 64)});
     }
-    v[0] = add(c.c_x, 0, W, 1, {hbe, encb}, bv[0]);
-    v[1] = add(c.c_x + W, 0, W, 1, {acts(c.c_x, W), hbe, encb}, bv[1]);  // the skip concatenation
-    for (uint32_t l = 2; l < D; ++l) v[l] = add(c.c_x + l * W, 0, W, 1, {acts(c.c_x + (l - 1) * W, W)}, bv[l]);
-    const IMat rgbw = add(c.c_o, 0, 3, 1, {acts(c.c_x + (D - 1) * W, W)}, brgb);
+    v[0] = add(c.c_x, 0, W, 1, {hbe, encb});
+    v[1] = add(c.c_x + W, 0, W, 1, {acts(c.c_x, W), hbe, encb});  // the skip concatenation
+    for (uint32_t l = 2; l < D; ++l) v[l] = add(c.c_x + l * W, 0, W, 1, {acts(c.c_x + (l - 1) * W, W)});
+    const ILin rgb = add(c.c_o, 0, 3, 1, {acts(c.c_x + (D - 1) * W, W)});
     p->n_params = off;
-    // heads as two stacked GEMMs (as the inference path): h1 = [sem0 ; int0], h2 block-diagonal into one 32-row unit
-    const uint32_t HH = p->HT * 32;
-    IMat h1(HH ? HH : 1, WB), h2(32, HH ? HH : 1);
-    std::vector<int32_t> b1(HH, -1), b2(32, -1);
-    if (p->sem) {
-        for (uint32_t r = 0; r < 64; ++r) {
-            for (uint32_t c = 0; c < WB; ++c) h1.at(r, c) = s0.a[(size_t)r * WB + c];
-            b1[r] = (int32_t)(bs0 + r);
-        }
-        for (uint32_t r = 0; r < K; ++r) {
-            for (uint32_t c = 0; c < 64; ++c) h2.at(r, c) = s2.a[(size_t)r * 64 + c];
-            b2[r] = (int32_t)(bs2 + r);
-        }
-    }
-    if (p->inten) {
-        for (uint32_t r = 0; r < 64; ++r) {
-            for (uint32_t c = 0; c < WB; ++c) h1.at(r0 + r, c) = i0.a[(size_t)r * WB + c];
-            b1[r0 + r] = (int32_t)(bi0 + r);
-        }
-        for (uint32_t c = 0; c < 64; ++c) h2.at(p->int_row, r0 + c) = i2.a[c];
-        b2[p->int_row] = (int32_t)bi2;
-    }
+    // heads as two stacked GEMMs, as the inference path
+    const TapeHeads<int32_t, -1> hd = nlr_tape_heads<int32_t, -1>(WB, K, p->sem ? &s0 : nullptr, &s2, p->inten ? &i0 : nullptr, &i2);
+    const uint32_t HH = p->HT * 32, Fp = 64;  // (grid features padded to two k-blocks)
     // view layers with the direction-encoding columns padded to one 32-feature k-block
-    auto pad_enc = [&](const IMat &w, uint32_t lead) {  // [.., lead + E] -> [.., lead + 32]
-        IMat m(w.rows, lead + 32);
-        for (uint32_t r = 0; r < w.rows; ++r)
-            for (uint32_t c = 0; c < w.cols; ++c) m.at(r, c) = w.a[(size_t)r * w.cols + c];
-        return m;
-    };
-    const IMat v0p = pad_enc(v[0], WB), v1p = pad_enc(v[1], W + WB);
-    IMat d0t(64, 64);
-    for (uint32_t r = 0; r < F; ++r)
-        for (uint32_t c = 0; c < 64; ++c) d0t.at(r, c) = d0.a[(size_t)c * F + r];
+    const IMat v0p = v[0].w.slice(0, W, 0, WB + 32), v1p = v[1].w.slice(0, W, 0, W + WB + 32);
     // ---- the tapes: forward D0 D2 [H1 H2] (V0 V1 L2.. RGB), backward (RGB^T L^T.. V1a^T) H2^T BIG D2^T D0^T; the parts in brackets
-    //      with the view MLP only
-    auto build_tapes = [&](bool view) {
-        tape_add(ft, d0, 64, 64);
-        tape_add(ft, d2, WB, 64);
+    //      with the view MLP only.  Each program's length is checked against the kernel's (nlr_train_program).
+    auto build_tapes = [&](bool view) -> int {
+        const TrainProgram PG = nlr_train_program(W / 32, WB / 32, Fp / 32, p->HT, view);
+        const size_t f_start = ft.size(), b_start = bt.size(), frag = NLR_FRAG_BYTES / 2;  // (bf16 elements per fragment)
+        tape_add(ft, d0.w, 64, Fp);
+        tape_add(ft, d2.w, WB, 64);
         if (HH) {
-            tape_add(ft, h1, HH, WB);
-            tape_add(ft, h2, 32, HH);
+            tape_add(ft, hd.h1, HH, WB);
+            tape_add(ft, hd.h2, 32, HH);
         }
         if (view) {
             tape_add(ft, v0p, W, WB + 32);
             tape_add(ft, v1p, W, W + WB + 32);
-            for (uint32_t l = 2; l < D; ++l) tape_add(ft, v[l], W, W);
-            tape_add(ft, rgbw, 16, W, 1);
+            for (uint32_t l = 2; l < D; ++l) tape_add(ft, v[l].w, W, W);
+            tape_add(ft, rgb.w, 16, W, 1);
         }
+        if (const int rc = nlr_tape_check(view ? "training forward tape (fragments)" : "training forward tape, trunk and heads (fragments)",
+                                          (ft.size() - f_start) / frag, PG.fwd_frags(D)))
+            return rc;
         tape_pad(ft);
         const uint32_t VW = view ? W : 0;
         if (view) {
-            tape_add(bt, transpose(rgbw), W, 32);  // rows = view features, k = the 3 (of 32) rgb rows
-            for (uint32_t l = D - 1; l >= 2; --l) tape_add(bt, transpose(v[l]), W, W);
-            IMat v1a(W, W);  // d z_0 <- d z_1 through W1[:, :W]
-            for (uint32_t r = 0; r < W; ++r)
-                for (uint32_t c = 0; c < W; ++c) v1a.at(r, c) = v1p.a[(size_t)c * v1p.cols + r];
-            tape_add(bt, v1a, W, W);
+            tape_add(bt, rgb.w.t(), W, 32);  // rows = view features, k = the 3 (of 32) rgb rows
+            for (uint32_t l = D - 1; l >= 2; --l) tape_add(bt, v[l].w.t(), W, W);
+            tape_add(bt, v[1].w.slice(0, W, 0, W).t(), W, W);  // V1a^T: d z_0 <- d z_1 through W1[:, :W]
         }
-        if (HH) tape_add(bt, transpose(h2), HH, 32);
+        if (HH) tape_add(bt, hd.h2.t(), HH, 32);
         IMat big(WB, 2 * VW + HH + 32);
-        for (uint32_t r = 0; r < WB; ++r) {
-            for (uint32_t c = 0; c < VW; ++c) big.at(r, c) = v1p.a[(size_t)c * v1p.cols + W + r];   // skip concat of layer 1
-            for (uint32_t c = 0; c < VW; ++c) big.at(r, VW + c) = v0p.a[(size_t)c * v0p.cols + r];  // layer 0
-            for (uint32_t c = 0; c < HH; ++c) big.at(r, 2 * VW + c) = h1.a[(size_t)c * WB + r];     // heads
-        }
+        big.paste(0, 0, v[1].w.slice(0, VW, W, WB).t());  // skip concat of layer 1
+        big.paste(0, VW, v[0].w.slice(0, VW, 0, WB).t());  // layer 0
+        big.paste(0, 2 * VW, hd.h1.t());                   // heads
         big.at(0, 2 * VW + HH + 0) = -2;  // unit weights: raw-density gradient (hi, lo) onto bottleneck row 0
         big.at(0, 2 * VW + HH + 1) = -2;
         tape_add(bt, big, WB, 2 * VW + HH + 32);
-        tape_add(bt, transpose(d2), 64, WB);
-        tape_add(bt, d0t, 64, 64);
+        tape_add(bt, d2.w.t(), 64, WB);
+        tape_add(bt, d0.w.t(), Fp, 64);
+        if (const int rc = nlr_tape_check(view ? "training backward tape (fragments)" : "training backward tape, trunk and heads (fragments)",
+                                          (bt.size() - b_start) / frag, PG.bwd_frags(D)))
+            return rc;
         tape_pad(bt);
+        return NLR_OK;
     };
-    build_tapes(true);
+    if (const int rc = build_tapes(true)) return rc;
     // the tapes of rows without colour supervision (nlr_mlp_train_*_split) behind the full ones, so that one gather packs both
     p->f0n = p->f1 = (uint32_t)ft.size(), p->b0n = p->b1 = (uint32_t)bt.size();
-    build_tapes(false);
+    if (const int rc = build_tapes(false)) return rc;
     p->fn = (uint32_t)ft.size(), p->bn = (uint32_t)bt.size();
     p->f1n = p->fn - p->f1, p->b1n = p->bn - p->b1;
-    // ---- bias block of the forward kernel
-    auto pushb = [&](uint32_t b, uint32_t n, uint32_t pad) {
-        for (uint32_t i = 0; i < pad; ++i) bb.push_back(i < n ? (int32_t)(b + i) : -1);
+    // ---- bias block of the forward kernel (order: nlr_tape.h)
+    auto pushb = [&](const std::vector<int32_t> &b, uint32_t pad) {
+        bb.insert(bb.end(), b.begin(), b.end());
+        bb.resize(bb.size() + pad - b.size(), -1);
     };
-    pushb(bd0, 64, 64);
-    pushb(bd2, WB, WB);
-    bb.insert(bb.end(), b1.begin(), b1.end());
-    bb.insert(bb.end(), b2.begin(), b2.end());
-    for (uint32_t l = 0; l < D; ++l) pushb(bv[l], W, W);
-    pushb(brgb, 3, 32);
+    pushb(d0.b, 64);
+    pushb(d2.b, WB);
+    pushb(hd.b1, HH);
+    pushb(hd.b2, 32);
+    for (uint32_t l = 0; l < D; ++l) pushb(v[l].b, W);
+    pushb(rgb.b, 32);
     p->biasn = (uint32_t)bb.size();
+    return nlr_tape_check("training bias block (floats)", bb.size(), nlr_train_program(W / 32, WB / 32, Fp / 32, p->HT, true).bias_end(D));
 }
 
 // the device side of a plan; on failure the caller destroys the plan with what it owns by then
@@ -699,7 +642,7 @@ static int plan_upload(NlrTrainPlan *p, const std::vector<int32_t> &ft, const st
     };
     int rc;
     if ((rc = up(ft, &p->fidx)) || (rc = up(bt, &p->bidx)) || (rc = up(bb, &p->biasidx))) return rc;
-    const size_t slack = 3 * 16384;  // the kernel prefetches up to 3 chunks past the end
+    const size_t slack = NLR_TAPE_SLACK_CHUNKS * NLR_CHUNK_BF16;  // the kernel prefetches past the end
     NLR_HIP(hipMalloc((void **)&p->ftape, (ft.size() + slack) * 2));
     NLR_HIP(hipMalloc((void **)&p->btape, (bt.size() + slack) * 2));
     NLR_HIP(hipMemset(p->ftape, 0, (ft.size() + slack) * 2));
@@ -724,8 +667,9 @@ extern "C" int nlr_train_plan_create(uint32_t F, uint32_t W, uint32_t WB, uint32
     NlrTrainPlan *p = new NlrTrainPlan();
     p->density_bias = density_bias, p->rgb_premul = rgb_premultiplier, p->rgb_bias = rgb_bias, p->rgb_padding = rgb_padding;
     std::vector<int32_t> ft, bt, bb;
-    plan_build(p, F, W, WB, D, deg_view, class_num, use_semantic, use_intensity, ft, bt, bb);
-    if (const int rc = plan_upload(p, ft, bt, bb)) {
+    int rc = plan_build(p, F, W, WB, D, deg_view, class_num, use_semantic, use_intensity, ft, bt, bb);
+    if (!rc) rc = plan_upload(p, ft, bt, bb);
+    if (rc) {
         nlr_train_plan_destroy(p);
         return rc;
     }
@@ -803,12 +747,12 @@ static int launch_rows(const NlrTrainPlan *p, TrainParams &P, uint32_t M, uint32
     note_route(BWD, M, M_color);
     if (M_color > 0) {
         P.row0 = 0, P.M = M_color;
-        P.tape = (const uint4 *)tape, P.tape_chunks = n0 / 16384;
+        P.tape = (const uint4 *)tape, P.tape_chunks = n0 / NLR_CHUNK_BF16;
         if (const int rc = launch_train<BWD, true>(p, P, st)) return rc;
     }
     if (M_color < M) {
         P.row0 = M_color, P.M = M;
-        P.tape = (const uint4 *)(tape + t1), P.tape_chunks = n1 / 16384;
+        P.tape = (const uint4 *)(tape + t1), P.tape_chunks = n1 / NLR_CHUNK_BF16;
         if (const int rc = launch_train<BWD, false>(p, P, st)) return rc;
     }
     return NLR_OK;
