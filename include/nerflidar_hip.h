@@ -517,6 +517,27 @@ int nlr_obj_frame_backward(const float *tracks, const float *timestamps, const f
                            const int32_t *ray_idx, const int32_t *sample_idx, const int32_t *track_idx, uint32_t K, const float *g_pts,
                            const float *g_dirs, float *g_tracks, void *workspace, size_t workspace_bytes, void *stream);
 
+/* (7d) Pose refinement with dynamic objects (train.py:199-243 with Config.instance_obj): the adjoint of "rays -> box-frame points and
+ *      view directions of the owned samples", i.e. of world2object (ZI/obj_utils.py:116-181) by the ray, as the last level of
+ *      ZI/models.py:401-446 feeds them to the ObjMLPs.  The sibling of 7c: the same map, the other argument.
+ *
+ * nlr_obj_frame_backward_rays: the forward being differentiated is p = scale * (rot(t_mid * d + o) + t_w_o), dir =
+ *      normalize(scale * rot(viewdir)) with t_mid = (tdist[k] + tdist[k+1]) / 2 and rot with the reference's yaw quirk.  box_params
+ *      [N, n_obj, 8] (as nlr_track_box_params writes it; 16-byte aligned), tdist and the owner list are data: the owner map is
+ *      detached in the reference (obj_utils.py:212) and sample positions carry no gradient.  The K owned samples come as in 7c:
+ *      three parallel int32 lists sorted by (ray, sample); g_pts / g_dirs [K, 3] are the cotangents of p and dir.
+ *      d_origins, d_directions, d_viewdirs [N, 3] f32 are OVERWRITTEN; each may be NULL and is then neither computed nor written
+ *      (g_pts is read for the first two, g_dirs and viewdirs for the third).  A ray without owned samples gets an exact zero row;
+ *      K = 0 gives zeros.  An entry with sample_idx outside [0,S) or track_idx outside [0,n_obj) contributes nothing.
+ *      base_x / base_y receive nothing from this path: the object branch has no multisamples (models.py:422).
+ *      No atomics and no workspace: a ray's owned samples are one contiguous stretch of the list, which the ray's 16 lanes find by
+ *      search in ray_idx and sum in an order that depends on the list alone - two runs give the same bits, and an output has the
+ *      same bits whichever of the other two are requested. */
+int nlr_obj_frame_backward_rays(const float *box_params, const float *viewdirs, const float *tdist, uint32_t N, uint32_t S, uint32_t n_obj,
+                                const int32_t *ray_idx, const int32_t *sample_idx, const int32_t *track_idx, uint32_t K,
+                                const float *g_pts, const float *g_dirs, float *d_origins, float *d_directions, float *d_viewdirs,
+                                void *stream);
+
 typedef struct NlrObjClassDesc {
     NlrMlpDesc mlp;
     uint32_t latent_size, split_latent;  /* Config.latent_size (0 = none), MLP.split_latent (models.py:881-885,924-925) */

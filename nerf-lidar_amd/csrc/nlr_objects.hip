@@ -1,5 +1,6 @@
 // Dynamic-object branch (scope row f-1, header section 7b): pose blend -> owner of every sample + per-class compaction ->
-// object networks, and the adjoint of the box-frame map for track refinement.  All of it on the device.
+// object networks, and the adjoints of the box-frame map: by the track (track refinement) and by the ray (pose refinement).  All of
+// it on the device.
 //
 //   ZI/models.py:401-477 loops over tracks and lets every later track overwrite the samples of earlier ones, so a sample
 //   belongs to the LAST track whose box contains its interval midpoint.  ZI/obj_utils.py:203-216 (box_pts) decides "inside"
@@ -350,6 +351,167 @@ extern "C" int nlr_obj_frame_backward(const float *tracks, const float *timestam
         hipLaunchKernelGGL(nlr_obj_frame_bwd_kernel<0>, dim3(nb), dim3(256), 0, st, a, g_tracks);
         NLR_LAUNCH_CHECK("nlr_obj_frame_bwd_kernel");
     }
+    return NLR_OK;
+}
+
+// ---- adjoint of "rays -> box-frame points and directions of the owned samples" (pose refinement with objects) -----------------
+// The sibling of nlr_obj_frame_bwd_kernel: the same map (nlr_box_coords / nlr_box_dir), differentiated by the ray instead of the
+// track.  Here the box record of every (ray, track) is data (box_params), and the result is per RAY: a ray's owned samples are one
+// contiguous stretch of the (ray, sample)-sorted list, so each output row is the sum of one stretch and nothing is shared between
+// rays - no atomics, no workspace, and an order of additions that the list alone decides.
+//   Lanes: one 16-lane DPP row per ray, 16 rays per workgroup.  A stretch is at most S <= 128 entries and most rays own none: a
+//   whole wave per ray would idle 48 of its lanes on a typical stretch (and 64 on an empty one), a lane per ray would walk its
+//   stretch alone with its neighbours reading far-apart parts of the list.  The row finds its stretch itself - two 17-ary searches
+//   in ray_idx, the 16 lanes probing 16 split points per step (6 steps for 1.5 M entries, against 21 of a binary search) - walks it
+//   16 entries per trip (lane r takes entries r, r + 16, ... of the stretch: adjacent lanes read adjacent entries) and adds the 16
+//   partial sums with the DPP butterfly of the row.
+template <int CTRL>
+__device__ __forceinline__ float nlr_obj_dpp(float v) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
+}
+// sum over the 16 lanes of a row, every lane gets the same bits (a + b == b + a at every step)
+__device__ __forceinline__ float nlr_obj_row_sum(float v) {
+    v += nlr_obj_dpp<0xB1>(v);   // quad_perm [1,0,3,2]
+    v += nlr_obj_dpp<0x4E>(v);   // quad_perm [2,3,0,1]
+    v += nlr_obj_dpp<0x141>(v);  // row_half_mirror
+    v += nlr_obj_dpp<0x140>(v);  // row_mirror
+    return v;
+}
+// First index in the sorted ray_idx[lo, hi) whose entry is not below `key`, found by the 16 lanes r of a row together (`shift` = the
+// row's first lane in the wave).  Every probe lies inside [lo, hi); the range shrinks at every step whatever the list holds.
+__device__ __forceinline__ uint32_t nlr_obj_row_lower_bound(const int32_t *__restrict__ ray_idx, uint32_t lo, uint32_t hi, int32_t key,
+                                                            uint32_t r, uint32_t shift) {
+    while (lo < hi) {
+        const uint32_t len = hi - lo, step = len / 17 + 1;
+        auto probe = [&](uint32_t j) {  // split point j = 0..15, non-decreasing in j
+            const uint32_t d = step * (j + 1) - 1;
+            return lo + (d < len - 1 ? d : len - 1);
+        };
+        const bool below = ray_idx[probe(r)] < key;
+        const uint32_t c = (uint32_t)__popc((uint32_t)(__ballot(below) >> shift) & 0xffffu);  // probes below the key: the first c
+        const uint32_t nlo = c ? probe(c - 1) + 1 : lo, nhi = c < 16 ? probe(c) : hi;
+        lo = nlo;
+        hi = nhi;
+    }
+    return lo;
+}
+
+struct ObjFrameBwdRays {
+    const float *box, *viewdirs, *tdist;
+    uint32_t N, S, n_obj;
+    const int32_t *ray_idx, *sample_idx, *track_idx;
+    uint32_t K;
+    const float *g_pts, *g_dirs;
+    float *d_origins, *d_dirs, *d_viewdirs;
+};
+
+__global__ void __launch_bounds__(256) nlr_obj_frame_bwd_rays_kernel(ObjFrameBwdRays a) {
+    const uint32_t r = threadIdx.x & 15, shift = threadIdx.x & 48;
+    const uint32_t ray = blockIdx.x * 16 + (threadIdx.x >> 4);
+    if (ray >= a.N) return;  // (whole rows)
+    // the ray's stretch [lo, hi) of the list
+    uint32_t lo = nlr_obj_row_lower_bound(a.ray_idx, 0, a.K, (int32_t)ray, r, shift), hi = lo;
+    if (lo < a.K && a.ray_idx[lo] == (int32_t)ray) {
+        uint32_t cap = lo + a.S < a.K ? lo + a.S : a.K;  // a ray owns at most S samples: the stretch ends inside [lo, lo + S] ...
+        if (cap < a.K && a.ray_idx[cap] <= (int32_t)ray) cap = a.K;  // ... of a list made by nonzero(); any other list: search to its end
+        hi = nlr_obj_row_lower_bound(a.ray_idx, lo + 1, cap, (int32_t)ray + 1, r, shift);
+    }
+    const bool want_p = a.d_origins || a.d_dirs, want_v = a.d_viewdirs != nullptr;
+    float go[3] = {0.0f, 0.0f, 0.0f}, gd_[3] = {0.0f, 0.0f, 0.0f}, gv[3] = {0.0f, 0.0f, 0.0f};
+    float vd[3] = {0.0f, 0.0f, 0.0f};
+    if (want_v && lo < hi) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) vd[c] = a.viewdirs[(size_t)ray * 3 + c];
+    }
+    for (uint32_t k = lo + r; k < hi; k += 16) {
+        const uint32_t smp = (uint32_t)a.sample_idx[k], o = (uint32_t)a.track_idx[k];
+        if (smp >= a.S || o >= a.n_obj) continue;  // an index outside the batch contributes nothing
+        const f32x4 *b = reinterpret_cast<const f32x4 *>(a.box + ((size_t)ray * a.n_obj + o) * 8);  // (32-byte records of a float array)
+        const f32x4 b0 = b[0], b1 = b[1];
+        const float cs = b0[0], sn = b0[1], sc[3] = {b1[1], b1[2], b1[3]};
+        if (want_p) {  // p = scale * (rot(t_mid d + o) + t_w_o)
+            const float t0 = a.tdist[(size_t)ray * (a.S + 1) + smp], t1 = a.tdist[(size_t)ray * (a.S + 1) + smp + 1];
+            const float tm = 0.5f * (t0 + t1);
+            float gp[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) gp[c] = a.g_pts[(size_t)k * 3 + c];
+            const float gy = gp[1] * sc[1], gx = gp[0] * sc[0] + sn * gy;
+            const float gq[3] = {cs * gx, cs * gy - sn * gx, gp[2] * sc[2]};
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                go[c] += gq[c];
+                gd_[c] += tm * gq[c];
+            }
+        }
+        if (want_v) {  // dir = e / |e|, e = scale * rot(v)
+            float g[3], vx, vy;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) g[c] = a.g_dirs[(size_t)k * 3 + c];
+            nlr_rotate_yaw(cs, sn, vd[0], vd[1], vx, vy);
+            const float e[3] = {sc[0] * vx, sc[1] * vy, sc[2] * vd[2]};
+            const float inv = 1.0f / sqrtf((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
+            const float n[3] = {e[0] * inv, e[1] * inv, e[2] * inv};
+            const float dot = (n[0] * g[0] + n[1] * g[1]) + n[2] * g[2];
+            float ge[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) ge[c] = (g[c] - n[c] * dot) * inv;
+            const float hy = ge[1] * sc[1], hx = ge[0] * sc[0] + sn * hy;
+            gv[0] += cs * hx;
+            gv[1] += cs * hy - sn * hx;
+            gv[2] += ge[2] * sc[2];
+        }
+    }
+    // the row's sums (whole rows arrive here together: ray, lo and hi are the same in the 16 lanes); lane c < 3 writes component c
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        go[c] = nlr_obj_row_sum(go[c]);
+        gd_[c] = nlr_obj_row_sum(gd_[c]);
+        gv[c] = nlr_obj_row_sum(gv[c]);
+    }
+    if (r < 3) {
+        const size_t i = (size_t)ray * 3 + r;
+        if (a.d_origins) a.d_origins[i] = r == 0 ? go[0] : r == 1 ? go[1] : go[2];
+        if (a.d_dirs) a.d_dirs[i] = r == 0 ? gd_[0] : r == 1 ? gd_[1] : gd_[2];
+        if (a.d_viewdirs) a.d_viewdirs[i] = r == 0 ? gv[0] : r == 1 ? gv[1] : gv[2];
+    }
+}
+
+extern "C" int nlr_obj_frame_backward_rays(const float *box_params, const float *viewdirs, const float *tdist, uint32_t N, uint32_t S,
+                                           uint32_t n_obj, const int32_t *ray_idx, const int32_t *sample_idx, const int32_t *track_idx,
+                                           uint32_t K, const float *g_pts, const float *g_dirs, float *d_origins, float *d_directions,
+                                           float *d_viewdirs, void *stream) {
+    if (N == 0 || (!d_origins && !d_directions && !d_viewdirs)) return NLR_OK;
+    hipStream_t st = (hipStream_t)stream;
+    NLR_CHECK_ARG((size_t)N * 3 < (1ull << 32), "obj_frame_backward_rays: N = %u rays do not fit the 32-bit row index", N);
+    if (K == 0) {
+        for (float *d : {d_origins, d_directions, d_viewdirs})
+            if (d) NLR_HIP(hipMemsetAsync(d, 0, (size_t)N * 3 * sizeof(float), st));
+        return NLR_OK;
+    }
+    NLR_CHECK_ARG(box_params && tdist && ray_idx && sample_idx && track_idx, "obj_frame_backward_rays: NULL tensor");
+    NLR_CHECK_ARG(((uintptr_t)box_params & 15) == 0, "obj_frame_backward_rays: box_params must be 16-byte aligned");
+    NLR_CHECK_ARG(g_pts || (!d_origins && !d_directions), "obj_frame_backward_rays: g_pts is NULL");
+    NLR_CHECK_ARG((g_dirs && viewdirs) || !d_viewdirs, "obj_frame_backward_rays: d_viewdirs needs g_dirs and viewdirs");
+    NLR_CHECK_ARG(S >= 1 && n_obj >= 1, "obj_frame_backward_rays: %u owned samples of an empty batch (S = %u, n_obj = %u)", K, S, n_obj);
+    NLR_CHECK_ARG(K < (1u << 31) - 2 * S, "obj_frame_backward_rays: K = %u owned samples do not fit the 32-bit list index", K);
+    ObjFrameBwdRays a;
+    a.box = box_params;
+    a.viewdirs = viewdirs;
+    a.tdist = tdist;
+    a.N = N;
+    a.S = S;
+    a.n_obj = n_obj;
+    a.ray_idx = ray_idx;
+    a.sample_idx = sample_idx;
+    a.track_idx = track_idx;
+    a.K = K;
+    a.g_pts = g_pts;
+    a.g_dirs = g_dirs;
+    a.d_origins = d_origins;
+    a.d_dirs = d_directions;
+    a.d_viewdirs = d_viewdirs;
+    hipLaunchKernelGGL(nlr_obj_frame_bwd_rays_kernel, dim3((N + 15) / 16), dim3(256), 0, st, a);
+    NLR_LAUNCH_CHECK("nlr_obj_frame_bwd_rays_kernel");
     return NLR_OK;
 }
 

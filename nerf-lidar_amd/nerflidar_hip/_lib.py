@@ -90,7 +90,8 @@ EXPORTS = ["nlr_last_error", "nlr_version", "nlr_build_sha", "nlr_debug_set", "n
            "nlr_train_pack",
            "nlr_mlp_train_forward", "nlr_mlp_train_backward", "nlr_mlp_train_wgrad_workspace_bytes", "nlr_mlp_train_wgrad",
            "nlr_mlp_train_forward_split", "nlr_mlp_train_backward_split", "nlr_mlp_train_wgrad_split",
-           "nlr_render_lidar", "nlr_render_lidar_dynamic", "nlr_obj_frame_backward_workspace_bytes", "nlr_obj_frame_backward"]
+           "nlr_render_lidar", "nlr_render_lidar_dynamic", "nlr_obj_frame_backward_workspace_bytes", "nlr_obj_frame_backward",
+           "nlr_obj_frame_backward_rays"]
 NLR_K_COUNT = 6
 DBG_FORCE_GENERIC, DBG_MLP_WORKGROUPS, DBG_BINNED_C4, DBG_NO_XPAIR_SCATTER, DBG_SCATTER_LEVELS, DBG_NO_SCATTER_CACHE, DBG_RAY_GROUPS = 0, 1, 2, 3, 4, 5, 6
 DBG_LAST_ROUTE = 7  # read-back (nlr_debug_get): how the last level of the most recent render ran
@@ -162,6 +163,7 @@ def lib():
         L.nlr_obj_frame_backward_workspace_bytes.restype = C.c_size_t
         L.nlr_obj_frame_backward_workspace_bytes.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
         L.nlr_obj_frame_backward.argtypes = [c_fp] * 6 + [C.c_uint32] * 4 + [c_fp] * 3 + [C.c_uint32] + [c_fp] * 4 + [C.c_size_t, c_fp]
+        L.nlr_obj_frame_backward_rays.argtypes = [c_fp] * 3 + [C.c_uint32] * 3 + [c_fp] * 3 + [C.c_uint32] + [c_fp] * 6
         L.nlr_objects_create.argtypes = [C.POINTER(NlrObjectsDesc), C.POINTER(c_fp), c_fp]
         L.nlr_objects_destroy.restype = None
         L.nlr_objects_destroy.argtypes = [c_fp]

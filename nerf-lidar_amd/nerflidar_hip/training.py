@@ -699,21 +699,27 @@ class TrainableObjMLP(torch.nn.Module):
 
 
 class _ObjFrame(torch.autograd.Function):
-    """tracks [n_obj, T, 9] -> (box-frame points, box-frame view directions) of the owned samples.  forward = `objects.box_frame` on the
-    constants `nlr_track_box_params` made of the same tracks (the values of the path without gradient, bit for bit); backward =
-    `nlr_obj_frame_backward`, one reduction kernel instead of the gather / index_put chain autograd would walk.  Only the tracks
-    receive a gradient: ray origins and directions are data here (no pose refinement)."""
+    """(tracks [n_obj, T, 9], origins, directions, viewdirs [N, 3]) -> (box-frame points, box-frame view directions) of the owned
+    samples.  forward = `objects.box_frame` on the constants `nlr_track_box_params` made of the same tracks (the values of the path
+    without gradient, bit for bit).  backward builds only what `ctx.needs_input_grad` asks for: the track gradient from
+    `nlr_obj_frame_backward` (track refinement), the three ray gradients from `nlr_obj_frame_backward_rays` (pose refinement) - one
+    reduction kernel each instead of the gather / index_put chain autograd would walk.  Either kind of input may be plain data."""
 
     @staticmethod
     def forward(ctx, tracks, ts, origins, dirs, viewdirs, td, box, ri, si, tr):
-        ctx.save_for_backward(tracks.detach().contiguous(), ts, origins, dirs, viewdirs, td, ri.int().contiguous(), si.int().contiguous(),
-                              tr.int().contiguous())
+        ctx.save_for_backward(tracks.detach().contiguous(), ts, origins, dirs, viewdirs, td, box, ri.int().contiguous(),
+                              si.int().contiguous(), tr.int().contiguous())
         return box_frame(origins, dirs, viewdirs, td, box, ri, si, tr)
 
     @staticmethod
     def backward(ctx, g_p, g_d):
-        tracks, ts, origins, dirs, viewdirs, td, ri, si, tr = ctx.saved_tensors
-        return (obj_frame_backward(tracks, ts, origins, dirs, viewdirs, td, ri, si, tr, g_p, g_d),) + (None,) * 9
+        tracks, ts, origins, dirs, viewdirs, td, box, ri, si, tr = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        g_tracks = obj_frame_backward(tracks, ts, origins, dirs, viewdirs, td, ri, si, tr, g_p, g_d) if need[0] else None
+        g_rays = (None, None, None)
+        if any(need[2:5]):
+            g_rays = obj_frame_backward_rays(box, viewdirs, td, ri, si, tr, g_p, g_d, want=tuple(need[2:5]))
+        return (g_tracks, None) + tuple(g_rays) + (None,) * 5
 
 
 def obj_frame_backward(tracks, ts, origins, dirs, viewdirs, td, ri, si, tr, g_pts, g_dirs) -> torch.Tensor:
@@ -731,6 +737,21 @@ def obj_frame_backward(tracks, ts, origins, dirs, viewdirs, td, ri, si, tr, g_pt
                                             n, S, n_obj, T, _lib.ptr(ri), _lib.ptr(si), _lib.ptr(tr), K, _lib.ptr(g_pts), _lib.ptr(g_dirs),
                                             _lib.ptr(out), _lib.ptr(ws), need, _lib.current_stream()), "nlr_obj_frame_backward")
     return out
+
+
+def obj_frame_backward_rays(box, viewdirs, td, ri, si, tr, g_pts, g_dirs, want=(True, True, True)):
+    """`nlr_obj_frame_backward_rays`: (d_origins, d_directions, d_viewdirs) [N, 3] of the box-frame points / directions of the K owned
+    samples (int32 lists ri, si, tr sorted by (ray, sample); box [N, n_obj, 8] from `track_box_params`) contracted with their
+    cotangents g_pts, g_dirs [K, 3].  An output that `want` leaves out is None and is neither computed nor written."""
+    L = _lib.lib()
+    n, S, K = td.shape[0], td.shape[1] - 1, ri.shape[0]
+    g_pts, g_dirs = g_pts.contiguous().float(), g_dirs.contiguous().float()
+    out = [torch.empty(n, 3, dtype=torch.float32, device=td.device) if w else None for w in want]
+    with torch.cuda.device(td.device):
+        _lib.check(L.nlr_obj_frame_backward_rays(_lib.ptr(box), _lib.ptr(viewdirs), _lib.ptr(td), n, S, int(box.shape[1]), _lib.ptr(ri),
+                                                 _lib.ptr(si), _lib.ptr(tr), K, _lib.ptr(g_pts), _lib.ptr(g_dirs), _lib.ptr(out[0]),
+                                                 _lib.ptr(out[1]), _lib.ptr(out[2]), _lib.current_stream()), "nlr_obj_frame_backward_rays")
+    return tuple(out)
 
 
 class TrainableModel(torch.nn.Module):
@@ -803,9 +824,10 @@ class TrainableModel(torch.nn.Module):
                       refine=None):
         """Overwrite density / rgb / semantic of the samples inside the tracks' boxes with their ObjMLP's output.  Returns
         (density, rgbs, semantic, obj_mask).  Owner of a sample = the last track whose box holds the interval midpoint
-        (`nlr_box_winner`; the reference's track loop overwrites earlier tracks).  Sample positions carry no gradient, unless
-        refine = (tracks, timestamps) hands over a track tensor that requires one (track refinement, last level only): then the
-        box-frame points and directions lead back to it through `_ObjFrame`."""
+        (`nlr_box_winner`; the reference's track loop overwrites earlier tracks; the owner map is data).  The box-frame points and
+        directions carry no gradient, unless refine = (tracks, timestamps) is given (last level only): then they go through
+        `_ObjFrame`, which leads back to a track tensor that requires a gradient (track refinement) and to the ray tensors of
+        `batch` that require one (pose refinement)."""
         n, S = tdist.shape[0], tdist.shape[1] - 1
         dev = tdist.device
         origins = batch["origins"].reshape(n, 3).contiguous().float()
@@ -825,8 +847,8 @@ class TrainableModel(torch.nn.Module):
         tr = winner[ri, si].long()
         if refine is not None:
             p_all, d_all = _ObjFrame.apply(refine[0], refine[1], origins, dirs, viewdirs, td, box, ri, si, tr)
-        else:
-            p_all, d_all = box_frame(origins, dirs, viewdirs, td, box, ri, si, tr)
+        else:  # (ray tensors that require a gradient are data here: proposal levels, models.py:447-449)
+            p_all, d_all = box_frame(origins.detach(), dirs.detach(), viewdirs.detach(), td, box, ri, si, tr)
         table = torch.stack([self.latent_vector_dict[f"obj_latent_{t}"] for t in range(len(self.class_ids))])
         lat_all = table[tr]
         rank = self._class_rank[tr]
@@ -846,14 +868,18 @@ class TrainableModel(torch.nn.Module):
         return density, rgbs, sem, mask
 
     def forward(self, batch: Dict[str, torch.Tensor], train_frac: float = 1.0, rand: Optional[torch.Generator] = None, randomized: bool = False,
-                sample_n: int = 7, sample_m: int = 3, curr_track=None, color_rays: Optional[int] = None):
+                sample_n: int = 7, sample_m: int = 3, curr_track=None, color_rays: Optional[int] = None, object_ray_grads: bool = False):
         """-> (renderings, ray_history), one entry per level, like `Model.forward`.  randomized (or a generator in `rand`): per-ray
         jitter of the sample positions (stepfun.py:216) and per-multisample rotation (render.py:150), as `model(True, ...)` draws
         them in train.py:272.
         color_rays: None, or the number n of leading rays with colour supervision; the NerfMLP level skips its view MLP for the
         rays [n, N) and renders them black (`TrainableNerfLevel.forward`).  The caller promises `batch['mask_rgb']` = 0 on those
         rays.  With `instance_obj` the object networks still write their own rgb into the samples they own on such rays: harmless,
-        the loss masks those rays."""
+        the loss masks those rays.
+        object_ray_grads: with `instance_obj` and ray tensors that require a gradient (pose refinement), whether the last level's
+        box-frame points and directions lead back to origins / directions / viewdirs (`_ObjFrame`, `nlr_obj_frame_backward_rays`).
+        Off, such a call is refused: a gradient that silently misses the object samples is not the reference's.  `training_step`
+        turns it on.  Values are the same bits either way; a batch of plain data ignores it."""
         mc = self.mc
         color_rays = _check_color_rays(color_rays, batch["origins"].shape[0])
         L = _lib.lib()
@@ -867,9 +893,11 @@ class TrainableModel(torch.nn.Module):
         renderings, history = [], []
         n_levels = len(mc.level_samples())
         box = None
-        if self.instance_obj and rays_require_grad(batch):
+        ray_grads = self.instance_obj and rays_require_grad(batch)
+        if ray_grads and not object_ray_grads:
             raise NotImplementedError("ray tensors that require a gradient (pose refinement) with instance_obj=True: the box-frame path "
-                                      "of the dynamic-object branch is not wired to origins / directions / viewdirs")
+                                      "of the dynamic-object branch leads back to origins / directions / viewdirs only on request, "
+                                      "pass object_ray_grads=True")
         if self.instance_obj:
             if "timestamp" not in batch:
                 raise RuntimeError("batch['timestamp'] is missing (ZI/models.py:315)")
@@ -877,7 +905,8 @@ class TrainableModel(torch.nn.Module):
             ts = batch["timestamp"].reshape(-1).to(dev, torch.float32).contiguous()
             box = track_box_params(tracks, ts)  # (tracks and ts are kept in this form for `refine`: the adjoint reads the same two tensors)
             # track refinement (train.py:244-268): a track that requires a gradient gets one from the last level's object samples
-            refine = (tracks, ts) if tracks.requires_grad and torch.is_grad_enabled() else None
+            # pose refinement (train.py:199-243) on request: ray tensors that require one get theirs through the same samples
+            refine = (tracks, ts) if (tracks.requires_grad and torch.is_grad_enabled()) or ray_grads else None
         for li, ((S, dilation, anneal), level) in enumerate(zip(mc.level_schedule(train_frac), self.levels())):
             last = li == n_levels - 1
             sdist, tdist = torch.empty(n, S + 1, device=dev), torch.empty(n, S + 1, device=dev)
@@ -1122,7 +1151,9 @@ def training_step(model: TrainableModel, optimizer: torch.optim.Optimizer, batch
     train.py:199-243,463-466 runs it.  Before the window the batch is rendered as it is; inside it the PoseNet's learning rate is set,
     its gradients are zeroed, the batch is refined with gradient (`refine_batch`; the caller's batch is not modified), the loss
     reaches the PoseNet through the ray tensors and, after the model's own step, its gradients are clipped and its optimiser steps;
-    after it the batch is refined under no_grad.  The depth and semantic weights follow `loss_lambdas` unless given."""
+    after it the batch is refined under no_grad.  The depth and semantic weights follow `loss_lambdas` unless given.  A model with
+    `instance_obj` is called with `object_ray_grads=True`, so the refined rays also get the share of the samples inside the tracks'
+    boxes; with a tracknet as well both refinements run from the one forward, as train.py:199-268 does."""
     from . import losses as nlosses
     if check_color_rays and color_rays is not None:
         nlosses.check_colourless(batch, color_rays)
@@ -1145,6 +1176,8 @@ def training_step(model: TrainableModel, optimizer: torch.optim.Optimizer, batch
         loss_kw = {**loss_lambdas(step, pose_window), **loss_kw}
     optimizer.zero_grad(set_to_none=True)
     track_kw = {} if tracknet is None else {"curr_track": current_track(tracknet, step, track_start_opt)}
+    if posenet is not None and getattr(model, "instance_obj", False):  # the refined rays reach the object samples too (train.py:199-268)
+        track_kw["object_ray_grads"] = True
     renderings, history = model(batch, train_frac=train_frac, randomized=randomized, color_rays=color_rays, **track_kw)
     terms = nlosses.total_loss(renderings, history, batch, **loss_kw)
     if hash_decay_mult > 0:  # (Config.obj_nodecay, nuscenes_single.gin:24: the object grids stay out)
