@@ -1,4 +1,6 @@
-"""ctypes binding of libnerflidar_hip.so (the C ABI of include/nerflidar_hip.h).
+"""ctypes binding of libnerflidar_hip.so.  include/nerflidar_hip.h is the only statement of the C ABI: the prototypes and the integer
+`#define`s are read from it when this module is imported, `lib()` sets every function's argtypes / restype from them, and `call`
+checks the arguments of a launch against the same table before anything is loaded or launched.
 
 There is no CPU fallback: if the shared object is missing or a call fails, this raises.  Build it
 with `make -C nerf-lidar_amd` (or `python -c "import __graft_entry__ as g; g.build()"`).
@@ -7,17 +9,48 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
+from typing import Dict, NamedTuple, Optional, Tuple
+
+import numpy as np
+import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NLR_LIB_PATH") or os.path.join(_HERE, "libnerflidar_hip.so")  # override: diagnostic builds only
+HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "nerflidar_hip.h")  # as buildinfo.kernel_source_files
 
-NLR_MAX_LEVELS = 4
-NLR_MAX_VIEW_DEPTH = 16
+
+def _code(text: str) -> str:
+    """The header without its comments (they name kernels and Python helpers too); line breaks stay where they were."""
+    return re.sub(r"/\*.*?\*/|//[^\n]*", lambda m: " " + "\n" * m.group(0).count("\n"), text, flags=re.S)
+
+
+def defines(text: str) -> Dict[str, int]:
+    """Every `#define NLR_* <integer>` of a header text."""
+    return {k: int(v, 0) for k, v in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(NLR_\w+)[ \t]+(-?\w+)[ \t]*$", _code(text), flags=re.M)
+            if re.fullmatch(r"-?(0[xX][0-9a-fA-F]+|\d+)", v)}
+
+
+_HEADER = open(HEADER_PATH).read()
+DEFINES = defines(_HEADER)
+NLR_MAX_LEVELS, NLR_MAX_GRID_LEVELS, NLR_MAX_VIEW_DEPTH = (DEFINES[k] for k in ("NLR_MAX_LEVELS", "NLR_MAX_GRID_LEVELS", "NLR_MAX_VIEW_DEPTH"))
+# switches 0..6, then read-backs (nlr_debug_get): LAST_ROUTE = how the last level of the most recent render ran; TRAIN_* = the most
+# recent nlr_mlp_train_forward / _backward (or _split) call: route = TRAIN_FULL | TRAIN_TRUNK | TRAIN_BWD, and the first row / row
+# count the trunk-and-heads instance ran on
+(DBG_FORCE_GENERIC, DBG_MLP_WORKGROUPS, DBG_BINNED_C4, DBG_NO_XPAIR_SCATTER, DBG_SCATTER_LEVELS, DBG_NO_SCATTER_CACHE, DBG_RAY_GROUPS,
+ DBG_LAST_ROUTE, DBG_TRAIN_ROUTE, DBG_TRAIN_TRUNK_ROW0, DBG_TRAIN_TRUNK_ROWS) = (DEFINES["NLR_" + k] for k in (
+     "DBG_FORCE_GENERIC", "DBG_MLP_WORKGROUPS", "DBG_BINNED_C4", "DBG_NO_XPAIR_SCATTER", "DBG_SCATTER_LEVELS", "DBG_NO_SCATTER_CACHE",
+     "DBG_RAY_GROUPS", "DBG_LAST_ROUTE", "DBG_TRAIN_ROUTE", "DBG_TRAIN_TRUNK_ROW0", "DBG_TRAIN_TRUNK_ROWS"))
+# not `#define`s of the header (its NLR_PREC_* and NLR_K_COUNT are enumerators, the route values live in its comments): literals
 PREC_F32, PREC_MIXED, PREC_FAST = 0, 1, 2
+NLR_K_COUNT = 6
+ROUTE_FULL, ROUTE_FULL_FUSED, ROUTE_LIDAR, ROUTE_LIDAR_FUSED = 1, 2, 3, 4
+TRAIN_FULL, TRAIN_TRUNK, TRAIN_BWD = 1, 2, 4
 
 c_fp = C.c_void_p  # device / host pointers travel as integers
 
 
+# ---- the structs of the header, by hand (tests/test_abi.py compares every field's offset and size with the C compiler's) ------------
 class NlrLinear(C.Structure):
     _fields_ = [("weight", c_fp), ("bias", c_fp), ("out_features", C.c_uint32), ("in_features", C.c_uint32)]
 
@@ -59,6 +92,9 @@ class NlrRays(C.Structure):
     _fields_ = [(k, c_fp) for k in ("origins", "directions", "viewdirs", "radii", "near", "far", "base_x", "base_y")]
 
 
+RAY_KEYS = tuple(k for k, _ in NlrRays._fields_)  # the batch keys of a ray bundle
+
+
 class NlrRenderCfg(C.Structure):
     _fields_ = [("train_frac", C.c_float), ("compute_extras", C.c_uint32), ("sample_n", C.c_uint32),
                 ("sample_m", C.c_uint32), ("rand_jitter", c_fp * NLR_MAX_LEVELS), ("rand_deg", c_fp * NLR_MAX_LEVELS),
@@ -76,30 +112,85 @@ class NlrOut(C.Structure):
                [("packed_h", C.c_uint32), ("packed_w", C.c_uint32), ("history", NlrLevelOut * NLR_MAX_LEVELS)]
 
 
-_lib = None
+STRUCTS = {c.__name__: c for c in (NlrLinear, NlrGridDesc, NlrMlpDesc, NlrObjClassDesc, NlrObjectsDesc, NlrModelDesc, NlrRays, NlrRenderCfg,
+                                   NlrLevelOut, NlrOut)}
 
-EXPORTS = ["nlr_last_error", "nlr_version", "nlr_build_sha", "nlr_debug_set", "nlr_debug_get", "nlr_grid_fast_path", "nlr_grid_level_plan", "nlr_grid_encode_forward", "nlr_grid_encode_backward", "nlr_grad_total_variation", "nlr_level_scale",
-           "nlr_sample_u", "nlr_model_create", "nlr_model_destroy", "nlr_model_set_table", "nlr_workspace_bytes",
-           "nlr_render_rays", "nlr_kernel_names", "nlr_resample_level", "nlr_mlp_level", "nlr_composite_level",
-           "nlr_profile_begin", "nlr_profile_begin_kinds", "nlr_profile_end", "nlr_range_workspace_bytes", "nlr_range_project",
-           "nlr_composite_backward", "nlr_hash_decay_forward", "nlr_hash_decay_backward", "nlr_box_winner", "nlr_cast_contract",
-           "nlr_track_box_params", "nlr_objects_create", "nlr_objects_destroy", "nlr_objects_workspace_bytes", "nlr_objects_apply",
-           "nlr_render_rays_dynamic", "nlr_prop_mlp_forward", "nlr_prop_mlp_backward", "nlr_encode_features_forward",
-           "nlr_encode_features_backward", "nlr_encode_features_backward_ws", "nlr_encode_features_backward_rays", "nlr_grid_encode_backward_ws", "nlr_grid_backward_workspace_bytes",
-           "nlr_train_plan_create", "nlr_train_plan_destroy", "nlr_train_act_width", "nlr_train_param_layout", "nlr_train_linear_table",
-           "nlr_train_pack",
-           "nlr_mlp_train_forward", "nlr_mlp_train_backward", "nlr_mlp_train_wgrad_workspace_bytes", "nlr_mlp_train_wgrad",
-           "nlr_mlp_train_forward_split", "nlr_mlp_train_backward_split", "nlr_mlp_train_wgrad_split",
-           "nlr_render_lidar", "nlr_render_lidar_dynamic", "nlr_obj_frame_backward_workspace_bytes", "nlr_obj_frame_backward",
-           "nlr_obj_frame_backward_rays"]
-NLR_K_COUNT = 6
-DBG_FORCE_GENERIC, DBG_MLP_WORKGROUPS, DBG_BINNED_C4, DBG_NO_XPAIR_SCATTER, DBG_SCATTER_LEVELS, DBG_NO_SCATTER_CACHE, DBG_RAY_GROUPS = 0, 1, 2, 3, 4, 5, 6
-DBG_LAST_ROUTE = 7  # read-back (nlr_debug_get): how the last level of the most recent render ran
-ROUTE_FULL, ROUTE_FULL_FUSED, ROUTE_LIDAR, ROUTE_LIDAR_FUSED = 1, 2, 3, 4
-# read-backs of the most recent nlr_mlp_train_forward / _backward (or _split) call: route = TRAIN_FULL | TRAIN_TRUNK | TRAIN_BWD, and
-# the first row / row count the trunk-and-heads instance ran on
-DBG_TRAIN_ROUTE, DBG_TRAIN_TRUNK_ROW0, DBG_TRAIN_TRUNK_ROWS = 8, 9, 10
-TRAIN_FULL, TRAIN_TRUNK, TRAIN_BWD = 1, 2, 4
+
+# ---- the prototypes of the header ---------------------------------------------------------------------------------------------------
+_SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "uint32_t": C.c_uint32, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t}
+_RETURNS = {"void": None, "const char *": C.c_char_p, **_SCALARS}
+# what a tensor behind a `T *` must hold (torch, numpy); void takes any
+_POINTEE_DTYPE = {"float": (torch.float32, np.float32), "double": (torch.float64, np.float64), "int32_t": (torch.int32, np.int32),
+                  "uint32_t": (torch.int32, np.int32), "void": (None, None)}
+
+
+class Param(NamedTuple):
+    name: str                # as the header names it
+    decl: str                # "const int32_t *ray_idx"
+    pointee: Optional[str]   # base type of a pointer, None for a scalar
+    const: bool
+    ctype: object            # what argtypes gets
+    kind: str                # how `call` treats it: int, float, device, host, struct, handle, handles
+
+
+class Signature(NamedTuple):
+    name: str
+    returns: str             # "int", "size_t", "const char *", ...
+    restype: object
+    params: Tuple[Param, ...]
+    prototype: str
+    launcher: bool           # returns a status and ends in `void *stream`: what `call` takes
+
+
+def signatures(text: Optional[str] = None) -> Dict[str, Signature]:
+    """name -> Signature of every `nlr_*` prototype, of the header next to the package or of a header `text`.  Anything outside the
+    ABI's vocabulary - int, int32_t, uint32_t, float, double, size_t, void, const char *, pointers to those, to the bound structs, to
+    the opaque handles, and `T **` - is an error that quotes the prototype: no type is ever guessed."""
+    if text is None:
+        return _SIGNATURES
+    code = re.sub(r"^[ \t]*#.*$", " ", _code(text), flags=re.M)
+    handles = set(re.findall(r"\btypedef\s+struct\s+(\w+)\s+\1\s*;", code))  # declared, never defined: opaque
+    out = {}
+    for m in re.finditer(r"([^;{}()]*?)\b(nlr_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", code):
+        proto = " ".join(m.group(0).split())
+        name = m.group(2)
+
+        def refuse(what):
+            raise RuntimeError(f"include/nerflidar_hip.h: {what} is outside the ABI's type vocabulary in `{proto}`")
+
+        returns = " ".join(m.group(1).split())
+        if returns not in _RETURNS:
+            refuse(f"return type `{returns}`")
+        params = []
+        plist = " ".join(m.group(3).split())
+        for decl in ([] if plist == "void" else plist.split(",")):
+            pm = re.fullmatch(r"\s*(const\s+)?(\w+)\s*((?:\*\s*(?:const\s*)?)*)(\w+)\s*", decl)
+            if not pm:
+                refuse(f"parameter `{decl.strip()}`")
+            const, base, depth, pname = bool(pm.group(1)), pm.group(2), pm.group(3).count("*"), pm.group(4)
+            if depth == 0 and base in _SCALARS:
+                ctype, kind = _SCALARS[base], "float" if base in ("float", "double") else "int"
+            elif depth == 1 and base in _POINTEE_DTYPE:
+                ctype, kind = c_fp, "host" if pname.endswith("_host") else "device"
+            elif depth == 1 and base in STRUCTS:
+                ctype, kind = C.POINTER(STRUCTS[base]), "struct"
+            elif depth == 1 and base in handles:
+                ctype, kind = c_fp, "handle"
+            elif depth == 2 and (base in handles or base in _POINTEE_DTYPE):
+                ctype, kind = C.POINTER(c_fp), "handles"
+            else:
+                refuse(f"parameter `{decl.strip()}`")
+            norm = f"{'const ' if const else ''}{base} {'*' * depth}{pname}" if depth < 2 else " ".join(decl.split())
+            params.append(Param(pname, norm, base if depth else None, const, ctype, kind))
+        launcher = returns == "int" and bool(params) and params[-1].decl == "void *stream"
+        out[name] = Signature(name, returns, _RETURNS[returns], tuple(params), proto, launcher)
+    return out
+
+
+_SIGNATURES = signatures(_HEADER)
+EXPORTS = list(_SIGNATURES)
+
+_lib = None
 
 
 def lib():
@@ -109,98 +200,9 @@ def lib():
             raise RuntimeError(f"{LIB_PATH} is missing: the HIP extension has not been built (make -C nerf-lidar_amd). "
                                "There is no CPU fallback for the render path.")
         L = C.CDLL(LIB_PATH)
-        L.nlr_last_error.restype = C.c_char_p
-        L.nlr_kernel_names.restype = C.c_char_p
-        L.nlr_build_sha.restype = C.c_char_p
-        L.nlr_version.restype = C.c_int
-        L.nlr_workspace_bytes.restype = C.c_size_t
-        L.nlr_workspace_bytes.argtypes = [c_fp, C.c_uint32]
-        L.nlr_model_destroy.restype = None
-        L.nlr_model_destroy.argtypes = [c_fp]
-        L.nlr_model_create.argtypes = [C.POINTER(NlrModelDesc), C.POINTER(c_fp), c_fp]
-        L.nlr_model_set_table.argtypes = [c_fp, C.c_uint32, c_fp, C.c_int]
-        L.nlr_level_scale.restype = None
-        L.nlr_level_scale.argtypes = [C.c_uint32, C.c_float, C.c_uint32, c_fp, c_fp]
-        L.nlr_sample_u.restype = None
-        L.nlr_sample_u.argtypes = [C.c_uint32, C.c_int, c_fp, c_fp]
-        L.nlr_grid_encode_forward.argtypes = [c_fp, c_fp, C.c_int, c_fp, c_fp, C.c_uint32, C.c_uint32, C.c_uint32,
-                                              C.c_uint32, C.c_float, C.c_uint32, c_fp, C.c_uint32, C.c_int, C.c_uint32,
-                                              C.c_int, c_fp]
-        L.nlr_grid_encode_backward.argtypes = [c_fp, c_fp, c_fp, c_fp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
-                                               C.c_float, C.c_uint32, c_fp, c_fp, C.c_uint32, C.c_int, C.c_uint32,
-                                               C.c_int, c_fp]
-        L.nlr_grid_encode_backward_ws.argtypes = L.nlr_grid_encode_backward.argtypes[:-1] + [c_fp, C.c_size_t, c_fp]
-        L.nlr_grid_backward_workspace_bytes.restype = C.c_size_t
-        L.nlr_grid_backward_workspace_bytes.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, c_fp, C.c_uint32, C.c_int]
-        L.nlr_debug_set.argtypes = [C.c_uint32, C.c_int]
-        L.nlr_debug_get.argtypes = [C.c_uint32]
-        L.nlr_grid_fast_path.argtypes = [c_fp, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, C.c_int, C.c_uint32, C.c_int, C.c_uint32]
-        L.nlr_grid_level_plan.argtypes = [c_fp, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, c_fp, c_fp, c_fp]
-        L.nlr_grad_total_variation.argtypes = [c_fp, c_fp, c_fp, c_fp, C.c_float, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float,
-                                               C.c_uint32, C.c_uint32, C.c_int, c_fp]
-        L.nlr_render_rays.argtypes = [c_fp, C.POINTER(NlrRays), C.c_uint32, C.POINTER(NlrRenderCfg), C.POINTER(NlrOut),
-                                      c_fp, C.c_size_t, c_fp]
-        L.nlr_render_lidar.argtypes = L.nlr_render_rays.argtypes
-        L.nlr_resample_level.argtypes = [c_fp, c_fp, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_uint32, c_fp, c_fp,
-                                         c_fp, C.c_float, C.c_uint32, c_fp, c_fp, c_fp]
-        L.nlr_mlp_level.argtypes = [c_fp, C.c_uint32, C.POINTER(NlrRays), c_fp, C.c_uint32, C.c_uint32, C.c_uint32, c_fp,
-                                    c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, C.c_size_t, c_fp]
-        L.nlr_composite_level.argtypes = [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, C.c_uint32, C.c_uint32,
-                                          C.c_uint32, C.c_int, C.c_float, C.c_int, C.c_float, c_fp, C.POINTER(NlrOut),
-                                          c_fp, c_fp]
-        L.nlr_range_workspace_bytes.restype = C.c_size_t
-        L.nlr_range_workspace_bytes.argtypes = [C.c_uint32, C.c_uint32]
-        L.nlr_range_project.argtypes = [c_fp, c_fp, c_fp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_float, c_fp,
-                                        C.c_size_t, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]
-        L.nlr_composite_backward.argtypes = [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int,
-                                             C.c_float, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]
-        L.nlr_hash_decay_forward.argtypes = [c_fp, c_fp, C.c_uint32, C.c_uint32, c_fp, c_fp]
-        L.nlr_hash_decay_backward.argtypes = [c_fp, c_fp, C.c_uint32, C.c_uint32, C.c_float, c_fp, c_fp]
-        L.nlr_cast_contract.argtypes = [C.POINTER(NlrRays), c_fp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, c_fp, c_fp, c_fp,
-                                        c_fp]
-        L.nlr_box_winner.argtypes = [c_fp, c_fp, c_fp, c_fp, C.c_uint32, C.c_uint32, C.c_uint32, c_fp, c_fp]
-        L.nlr_track_box_params.argtypes = [c_fp, c_fp, C.c_uint32, C.c_uint32, C.c_uint32, c_fp, c_fp]
-        L.nlr_obj_frame_backward_workspace_bytes.restype = C.c_size_t
-        L.nlr_obj_frame_backward_workspace_bytes.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
-        L.nlr_obj_frame_backward.argtypes = [c_fp] * 6 + [C.c_uint32] * 4 + [c_fp] * 3 + [C.c_uint32] + [c_fp] * 4 + [C.c_size_t, c_fp]
-        L.nlr_obj_frame_backward_rays.argtypes = [c_fp] * 3 + [C.c_uint32] * 3 + [c_fp] * 3 + [C.c_uint32] + [c_fp] * 6
-        L.nlr_objects_create.argtypes = [C.POINTER(NlrObjectsDesc), C.POINTER(c_fp), c_fp]
-        L.nlr_objects_destroy.restype = None
-        L.nlr_objects_destroy.argtypes = [c_fp]
-        L.nlr_objects_workspace_bytes.restype = C.c_size_t
-        L.nlr_objects_workspace_bytes.argtypes = [c_fp, C.c_uint32, C.c_uint32]
-        L.nlr_objects_apply.argtypes = [c_fp, C.POINTER(NlrRays), c_fp, c_fp, C.c_uint32, C.c_uint32, C.c_uint32, c_fp, c_fp, c_fp,
-                                        C.c_uint32, c_fp, c_fp, C.c_size_t, c_fp]
-        L.nlr_render_rays_dynamic.argtypes = [c_fp, c_fp, C.POINTER(NlrRays), c_fp, C.c_uint32, C.c_uint32, C.POINTER(NlrRenderCfg),
-                                              C.POINTER(NlrOut), C.POINTER(c_fp), c_fp, C.c_size_t, c_fp]
-        L.nlr_render_lidar_dynamic.argtypes = L.nlr_render_rays_dynamic.argtypes
-        L.nlr_prop_mlp_forward.argtypes = [c_fp] * 5 + [C.c_uint32, C.c_uint32, c_fp, c_fp]
-        L.nlr_prop_mlp_backward.argtypes = [c_fp] * 6 + [C.c_uint32, C.c_uint32] + [c_fp] * 6
-        L.nlr_encode_features_forward.argtypes = [C.POINTER(NlrRays), c_fp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, c_fp,
-                                                  C.POINTER(NlrGridDesc), C.c_uint32, c_fp, c_fp]
-        L.nlr_encode_features_backward.argtypes = [C.POINTER(NlrRays), c_fp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, c_fp,
-                                                   C.POINTER(NlrGridDesc), C.c_uint32, c_fp, c_fp, c_fp, c_fp, c_fp]
-        L.nlr_encode_features_backward_ws.argtypes = L.nlr_encode_features_backward.argtypes[:-1] + [c_fp, C.c_size_t, c_fp]
-        L.nlr_encode_features_backward_rays.argtypes = L.nlr_encode_features_forward.argtypes[:10] + [c_fp] * 6
-        L.nlr_train_plan_create.argtypes = [C.c_uint32] * 6 + [C.c_int, C.c_int] + [C.c_float] * 4 + [C.POINTER(c_fp), C.POINTER(C.c_uint32)]
-        L.nlr_train_plan_destroy.restype = None
-        L.nlr_train_plan_destroy.argtypes = [c_fp]
-        L.nlr_train_act_width.restype = C.c_uint32
-        L.nlr_train_act_width.argtypes = [c_fp]
-        L.nlr_train_param_layout.argtypes = [c_fp, c_fp, C.c_uint32]
-        L.nlr_train_linear_table.argtypes = [c_fp, c_fp, C.c_uint32]
-        L.nlr_train_pack.argtypes = [c_fp, c_fp, c_fp]
-        L.nlr_mlp_train_forward.argtypes = [c_fp, c_fp, c_fp, C.c_uint32, C.c_uint32, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]
-        L.nlr_mlp_train_backward.argtypes = [c_fp, C.c_uint32, C.c_uint32] + [c_fp] * 11
-        L.nlr_mlp_train_wgrad_workspace_bytes.restype = C.c_size_t
-        L.nlr_mlp_train_wgrad_workspace_bytes.argtypes = [c_fp, C.c_uint32]
-        L.nlr_mlp_train_wgrad.argtypes = [c_fp, C.c_uint32, C.c_uint32] + [c_fp] * 6 + [C.c_size_t, c_fp]
-        L.nlr_mlp_train_forward_split.argtypes = [c_fp, c_fp, c_fp, C.c_uint32, C.c_uint32, C.c_uint32, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]
-        L.nlr_mlp_train_backward_split.argtypes = [c_fp, C.c_uint32, C.c_uint32, C.c_uint32] + [c_fp] * 11
-        L.nlr_mlp_train_wgrad_split.argtypes = [c_fp, C.c_uint32, C.c_uint32, C.c_uint32] + [c_fp] * 6 + [C.c_size_t, c_fp]
-        L.nlr_profile_begin.argtypes = [c_fp]
-        L.nlr_profile_begin_kinds.argtypes = [c_fp, C.c_uint32]
-        L.nlr_profile_end.argtypes = [c_fp, c_fp, c_fp, c_fp]
+        for sig in _SIGNATURES.values():
+            fn = getattr(L, sig.name)
+            fn.restype, fn.argtypes = sig.restype, [p.ctype for p in sig.params]
         _lib = L
     return _lib
 
@@ -218,5 +220,104 @@ def ptr(t):
 
 
 def current_stream():
-    import torch
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def call(name: str, *args, device=None) -> None:
+    """Launch `name` - a function of the header that returns a status and ends in `void *stream` - with every argument but the
+    stream.  The arguments are checked against the header's prototype before the library is touched; a refusal is a RuntimeError that
+    names the function, the parameter as the header names it, what was expected and what was found.  This refuses, it does not
+    repair: `.contiguous()`, `.float()`, `.int()` stay with the caller.
+      None              NULL for any pointer (the library checks NULLs itself)
+      T *               a contiguous CUDA tensor: float32 for float, float64 for double, int32 for int32_t / uint32_t, any dtype for
+                        void; all of a call's tensors on one device
+      T *name_host      a contiguous CPU tensor or numpy array of that dtype
+      Struct *          an instance of the ctypes class, passed by reference
+      Handle *          the c_void_p a *_create call filled;  T **: such a c_void_p (by reference) or an array of them
+      scalars           through int() / float()
+    The call runs inside `torch.cuda.device` of the tensors' device (`device=` when there is no tensor) on that device's current
+    stream, and its status goes through `check`."""
+    sig = _SIGNATURES.get(name)
+    if sig is None or not sig.launcher:
+        raise RuntimeError(f"{name}: not a launcher of include/nerflidar_hip.h (a status-returning function whose last parameter is the stream)")
+    params = sig.params[:-1]
+    if len(args) != len(params):
+        raise RuntimeError(f"{name}: takes {len(params)} arguments before the stream ({', '.join(p.name for p in params)}), got {len(args)}")
+
+    def refuse(p, expected, a):
+        found = f"{a.dtype} tensor of shape {tuple(a.shape)}, strides {a.stride()} on {a.device}" if isinstance(a, torch.Tensor) else \
+            f"{a.dtype} array of shape {a.shape}" if isinstance(a, np.ndarray) else type(a).__name__
+        raise RuntimeError(f"{name}: {p.name} (`{p.decl}`) must be {expected}, got a {found}")
+
+    dev, conv = None, []
+    for p, a in zip(params, args):
+        kind = p.kind
+        if kind == "int":
+            a = int(a)
+        elif kind == "float":
+            a = float(a)
+        elif a is None:
+            pass
+        elif kind == "device" or kind == "host":
+            dtype, np_dtype = _POINTEE_DTYPE[p.pointee]
+            if kind == "host" and isinstance(a, np.ndarray):
+                if (dtype is not None and a.dtype != np_dtype) or not a.flags.c_contiguous:
+                    refuse(p, f"a contiguous {dtype} CPU tensor or numpy array", a)
+                a = a.ctypes.data
+            else:
+                if not isinstance(a, torch.Tensor):
+                    refuse(p, "a tensor or None", a)
+                if dtype is not None and a.dtype != dtype:
+                    refuse(p, f"a {dtype} tensor", a)
+                if not a.is_contiguous():
+                    refuse(p, "a contiguous tensor", a)
+                if a.is_cuda == (kind == "host"):
+                    refuse(p, "a CPU tensor or numpy array (host memory)" if kind == "host" else "a CUDA tensor (no CPU fallback)", a)
+                if kind == "device":
+                    if dev is None:
+                        dev = a.device
+                    elif a.device != dev:
+                        refuse(p, f"on {dev} like the call's other tensors", a)
+                a = a.data_ptr()
+        elif kind == "struct":
+            if not isinstance(a, p.ctype._type_):
+                refuse(p, f"a {p.ctype._type_.__name__} or None", a)
+            a = C.byref(a)
+        elif kind == "handle":
+            if not isinstance(a, (C.c_void_p, int)):
+                refuse(p, "the c_void_p handle of a *_create call", a)
+        else:  # handles: T **
+            if isinstance(a, C.c_void_p):
+                a = C.byref(a)
+            elif not (isinstance(a, C.Array) and a._type_ is C.c_void_p):
+                refuse(p, "a c_void_p (passed by reference) or an array of c_void_p", a)
+        conv.append(a)
+    if device is not None:
+        device = torch.device(device)
+        if dev is not None and device.index is not None and device != dev:
+            raise RuntimeError(f"{name}: device={device}, but the tensors are on {dev}")
+    dev = dev if dev is not None else device
+    if dev is None:
+        raise RuntimeError(f"{name}: no tensor argument to take the device from: pass device=")
+    fn = getattr(lib(), name)
+    with torch.cuda.device(dev):
+        rc = fn(*conv, torch.cuda.current_stream(dev).cuda_stream)
+    check(rc, name)
+
+
+def rays(batch, n: int, optional=()):
+    """(NlrRays, keep) of a batch of n rays: every key of RAY_KEYS as a contiguous float32 [n, -1] CUDA tensor; `keep` maps the keys
+    to the tensors whose addresses the struct carries (hold it for as long as the struct is in use).  A key listed in `optional` may
+    be absent and stays NULL (`viewdirs` of a LiDAR-only render)."""
+    r, keep = NlrRays(), {}
+    for k in RAY_KEYS:
+        t = batch.get(k)
+        if t is None:
+            if k in optional:
+                continue
+            raise RuntimeError(f"batch['{k}'] is missing")
+        if not t.is_cuda:
+            raise RuntimeError(f"batch['{k}'] must be a CUDA tensor (no CPU fallback)")
+        keep[k] = t = t.reshape(n, -1).contiguous().float()
+        setattr(r, k, t.data_ptr())
+    return r, keep

@@ -29,14 +29,6 @@ GRIDTYPES = ("hash", "tiled")          # ids as in gridencoder.cu:66-84 (0: hash
 INTERPOLATIONS = ("linear", "smoothstep")
 
 
-def _device_operand(t: torch.Tensor, name: str) -> None:
-    """The checks of gridencoder.cu:15-19 (CHECK_CUDA / CHECK_CONTIGUOUS), as RuntimeError like TORCH_CHECK."""
-    if not t.is_cuda:
-        raise RuntimeError(f"{name} must be a CUDA tensor")
-    if not t.is_contiguous():
-        raise RuntimeError(f"{name} must be a contiguous tensor")
-
-
 def _host_offsets(offsets) -> torch.Tensor:
     """int32 level offsets on the host: the launcher derives per-level constants from them (include/nerflidar_hip.h)."""
     if isinstance(offsets, torch.Tensor):
@@ -46,52 +38,31 @@ def _host_offsets(offsets) -> torch.Tensor:
 
 class _Backend:
     """Positional signatures of the pybind module `_gridencoder` (gridencoder.h:12-15) + one trailing layout switch:
-    0 = the reference's [L, B, C] outputs / gradients, 1 = [B, L*C] (what `GridEncoder.forward` returns anyway)."""
+    0 = the reference's [L, B, C] outputs / gradients, 1 = [B, L*C] (what `GridEncoder.forward` returns anyway).  The checks of
+    gridencoder.cu:15-19 (CHECK_CUDA / CHECK_CONTIGUOUS / the dtypes) are `_lib.call`'s, as RuntimeError like TORCH_CHECK."""
 
     @staticmethod
     def grid_encode_forward(inputs, embeddings, offsets, outputs, B, D, C, L, S, H, dy_dx, gridtype, align_corners,
                             interp, out_layout=0):
-        _device_operand(inputs, "inputs")
-        _device_operand(embeddings, "embeddings")
-        _device_operand(outputs, "outputs")
-        if inputs.dtype != torch.float32 or outputs.dtype != torch.float32:
-            raise RuntimeError("inputs/outputs must be float32 tensors")
-        half = {torch.float32: 0, torch.float16: 1}.get(embeddings.dtype)
+        half = {torch.float32: 0, torch.float16: 1}.get(embeddings.dtype)  # (`const void *embeddings`: the one dtype the header leaves open)
         if half is None:
             raise RuntimeError("embeddings must be a floating tensor (float32 or float16)")
-        off = _host_offsets(offsets)
-        with torch.cuda.device(inputs.device):  # launch on the stream of the tensors' device, not of whatever device is current
-            _lib.check(_lib.lib().nlr_grid_encode_forward(
-                _lib.ptr(inputs), _lib.ptr(embeddings), half, _lib.ptr(off), _lib.ptr(outputs), B, D, C, L, float(S), int(H),
-                _lib.ptr(dy_dx), int(gridtype), int(bool(align_corners)), int(interp), int(out_layout),
-                _lib.current_stream()), "grid_encode_forward")
+        _lib.call("nlr_grid_encode_forward", inputs, embeddings, half, _host_offsets(offsets), outputs, B, D, C, L, S, H, dy_dx, gridtype,
+                  bool(align_corners), interp, out_layout)
 
     @staticmethod
     def grid_encode_backward(grad, inputs, embeddings, offsets, grad_embeddings, B, D, C, L, S, H, dy_dx, grad_inputs,
                              gridtype, align_corners, interp, grad_layout=0):
-        _device_operand(grad, "grad")
-        _device_operand(inputs, "inputs")
-        _device_operand(grad_embeddings, "grad_embeddings")
         off = _host_offsets(offsets)
-        with torch.cuda.device(inputs.device):
-            ws = backward_workspace(B, C, L, S, H, off, gridtype, align_corners, inputs.device)
-            _lib.check(_lib.lib().nlr_grid_encode_backward_ws(
-                _lib.ptr(grad), _lib.ptr(inputs), _lib.ptr(off), _lib.ptr(grad_embeddings), B, D, C, L, float(S), int(H),
-                _lib.ptr(dy_dx), _lib.ptr(grad_inputs), int(gridtype), int(bool(align_corners)), int(interp),
-                int(grad_layout), _lib.ptr(ws), 0 if ws is None else ws.numel(), _lib.current_stream()), "grid_encode_backward")
+        ws = backward_workspace(B, C, L, S, H, off, gridtype, align_corners, inputs.device)
+        _lib.call("nlr_grid_encode_backward_ws", grad, inputs, off, grad_embeddings, B, D, C, L, S, H, dy_dx, grad_inputs, gridtype,
+                  bool(align_corners), interp, grad_layout, ws, 0 if ws is None else ws.numel())
 
     @staticmethod
     def grad_total_variation(inputs, embeddings, grad, offsets, weight, B, D, C, L, S, H, gridtype, align_corners):
-        _device_operand(inputs, "inputs")
-        _device_operand(embeddings, "embeddings")
-        _device_operand(grad, "grad")
-        if not (inputs.dtype == embeddings.dtype == grad.dtype == torch.float32):
-            raise RuntimeError("grad_total_variation runs in float32 (grid.py:176 disables autocast for it)")
-        off = _host_offsets(offsets)
-        with torch.cuda.device(inputs.device):
-            _lib.check(_lib.lib().nlr_grad_total_variation(
-                _lib.ptr(inputs), _lib.ptr(embeddings), _lib.ptr(grad), _lib.ptr(off), float(weight), B, D, C, L, float(S), int(H),
-                int(gridtype), int(bool(align_corners)), _lib.current_stream()), "grad_total_variation")
+        # (float32 throughout, the header says: grid.py:176 disables autocast for it)
+        _lib.call("nlr_grad_total_variation", inputs, embeddings, grad, _host_offsets(offsets), weight, B, D, C, L, S, H, gridtype,
+                  bool(align_corners))
 
 
 BINNED_SCATTER = True  # large batches scatter through bins (nlr_grid_encode_backward_ws); False: scattered atomics only (A/B, tests)

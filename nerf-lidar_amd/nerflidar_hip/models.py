@@ -18,7 +18,7 @@ from . import _lib
 from .config import MLPConfig, ModelConfig
 from .weights import grid_layout, mlp_names, mlp_param_shapes
 
-_RAY_KEYS = ("origins", "directions", "viewdirs", "radii", "near", "far", "base_x", "base_y")
+_RAY_KEYS = _lib.RAY_KEYS
 
 
 def _f32c(a) -> np.ndarray:
@@ -75,9 +75,7 @@ class Model:
         desc.bg_intensity = lo if lo == hi else (lo + hi) / 2  # models.py:488-493 (deterministic render)
         desc.opaque_background = int(mc.opaque_background)
         desc.mlp_precision = precision
-        with torch.cuda.device(self.device):
-            rc = _lib.lib().nlr_model_create(C.byref(desc), C.byref(self._handle), _lib.current_stream())
-        _lib.check(rc, "nlr_model_create")
+        _lib.call("nlr_model_create", desc, self._handle, device=self.device)
         self._keep.clear()
 
     # -- descriptor assembly ---------------------------------------------------------------------
@@ -161,10 +159,7 @@ class Model:
     def _render_call(self, rays, n: int, cfg, out, lidar_only: bool = False) -> None:
         """The library call of `render_rays` (DynamicModel substitutes nlr_render_rays_dynamic / nlr_render_lidar_dynamic)."""
         ws = self._workspace(n)
-        name = "nlr_render_lidar" if lidar_only else "nlr_render_rays"
-        rc = getattr(_lib.lib(), name)(self._handle, C.byref(rays), n, C.byref(cfg), C.byref(out), _lib.ptr(ws), ws.numel(),
-                                       _lib.current_stream())
-        _lib.check(rc, name)
+        _lib.call("nlr_render_lidar" if lidar_only else "nlr_render_rays", self._handle, rays, n, cfg, out, ws, ws.numel())
 
     def render_rays(self, batch: Dict[str, torch.Tensor], train_frac: float = 1.0, compute_extras: bool = True,
                     sample_n: int = 7, sample_m: int = 3, want_history: bool = False, scale_factor: float = 0.0,
@@ -179,20 +174,9 @@ class Model:
         packed: optional float32 CUDA buffer for the 7-float-per-ray records (depth, intensity, acc, rgb, label) the
         compositing kernel writes besides the named outputs: shape [n, 7] (ray order) or [wp, H, 7] with wp * H == n
         (azimuth-major tile of a beam-major [H, wp] sector, see sharding.py); returned as r["packed"]."""
-        rays = _lib.NlrRays()
         n = batch["origins"].shape[0]
-        keep = []
-        for k in _RAY_KEYS:
-            t = batch.get(k)
-            if t is None and lidar_only and k == "viewdirs":
-                continue  # (NlrRays.viewdirs stays NULL)
-            if t is None:
-                raise RuntimeError(f"batch['{k}'] is missing")
-            if not t.is_cuda:
-                raise RuntimeError(f"batch['{k}'] must be a CUDA tensor (no CPU fallback)")
-            t = t.reshape(n, -1).contiguous().float()
-            keep.append(t)
-            setattr(rays, k, t.data_ptr())
+        rays, ray_keep = _lib.rays(batch, n, optional=("viewdirs",) if lidar_only else ())
+        keep = [ray_keep]  # tensors whose addresses the descriptors carry
         dev, f32 = self.device, torch.float32
         K = self.mc.nerf_mlp.class_num if self.config.use_semantic else 0
         new = lambda *shape, dtype=f32: torch.empty(*shape, device=dev, dtype=dtype)
@@ -254,8 +238,7 @@ class Model:
                 t = rand_deg[li].reshape(n, samples[li], sample_n).contiguous().float()
                 keep.append(t)
                 cfg.rand_deg[li] = t.data_ptr()
-        with torch.cuda.device(dev):
-            self._render_call(rays, n, cfg, out, lidar_only)
+        self._render_call(rays, n, cfg, out, lidar_only)
         if want_history:  # back to the reference's [N, S, C] layout (ZI/models.py:553-557)
             last = hist[-1]
             if "rgb" in last:

@@ -23,7 +23,7 @@ import torch.nn.functional as F
 from . import _lib, synth
 from .config import MLPConfig, ModelConfig, obj_mlp_config
 from .gridencoder import GridEncoder
-from .models import Model, _RAY_KEYS
+from .models import Model
 from .weights import grid_layout, mlp_param_shapes
 
 
@@ -130,9 +130,7 @@ def track_box_params(tracks: torch.Tensor, timestamps: torch.Tensor) -> torch.Te
     tracks = tracks.contiguous()
     ts = timestamps.reshape(-1).to(dev, torch.float32).contiguous()
     box = torch.empty(ts.shape[0], tracks.shape[0], 8, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().nlr_track_box_params(_lib.ptr(tracks), _lib.ptr(ts), ts.shape[0], tracks.shape[0], tracks.shape[1],
-                                                   _lib.ptr(box), _lib.current_stream()), "nlr_track_box_params")
+    _lib.call("nlr_track_box_params", tracks, ts, ts.shape[0], tracks.shape[0], tracks.shape[1], box)
     return box
 
 
@@ -258,10 +256,10 @@ class DynamicModel(Model):
         od.n_classes, od.classes = n_cls, descs
         od.n_tracks, od.track_class = len(self.class_ids), tc.ctypes.data
         od.latents = lt.ctypes.data
-        with torch.cuda.device(self.device):
-            rc = _lib.lib().nlr_objects_create(C.byref(od), C.byref(self._objects), _lib.current_stream())
-        self._keep.clear()
-        _lib.check(rc, "nlr_objects_create")
+        try:
+            _lib.call("nlr_objects_create", od, self._objects, device=self.device)
+        finally:
+            self._keep.clear()
 
     def __del__(self):
         try:
@@ -283,10 +281,8 @@ class DynamicModel(Model):
         box, winners = self._dyn_call
         ws = self._workspace(n)
         wp = (_lib.c_fp * len(winners))(*[w.data_ptr() for w in winners]) if winners else None
-        name = "nlr_render_lidar_dynamic" if lidar_only else "nlr_render_rays_dynamic"
-        rc = getattr(_lib.lib(), name)(self._handle, self._objects, C.byref(rays), _lib.ptr(box), int(box.shape[1]), n, C.byref(cfg),
-                                       C.byref(out), wp, _lib.ptr(ws), ws.numel(), _lib.current_stream())
-        _lib.check(rc, name)
+        _lib.call("nlr_render_lidar_dynamic" if lidar_only else "nlr_render_rays_dynamic", self._handle, self._objects, rays, box,
+                  box.shape[1], n, cfg, out, wp, ws, ws.numel())
 
     def box_params(self, timestamp: torch.Tensor, curr_track=None) -> torch.Tensor:
         """`track_box_params` of the stored tracks, or of `curr_track` (models.py:307-313), at the rays' timestamps."""
@@ -340,19 +336,10 @@ class DynamicModel(Model):
             raise NotImplementedError("DynamicModel renders deterministically (rand=False), as render_lidar does")
         if "timestamp" not in batch:
             raise RuntimeError("batch['timestamp'] is missing (ZI/models.py:315)")
-        L = _lib.lib()
         mc, dev, f32 = self.mc, self.device, torch.float32
         n = batch["origins"].shape[0]
-        rays, keep = _lib.NlrRays(), []
-        for k in _RAY_KEYS:
-            t = batch[k]
-            if not t.is_cuda:
-                raise RuntimeError(f"batch['{k}'] must be a CUDA tensor (no CPU fallback)")
-            t = t.reshape(n, -1).contiguous().float()
-            keep.append(t)
-            setattr(rays, k, t.data_ptr())
-        origins, dirs, viewdirs = keep[_RAY_KEYS.index("origins")], keep[_RAY_KEYS.index("directions")], keep[_RAY_KEYS.index("viewdirs")]
-        near, far = keep[_RAY_KEYS.index("near")], keep[_RAY_KEYS.index("far")]
+        rays, keep = _lib.rays(batch, n)
+        origins, dirs, viewdirs, near, far = (keep[k] for k in ("origins", "directions", "viewdirs", "near", "far"))
         if curr_track is None:
             curr_track = getattr(self, "_track_override", None)
         tracks = self.tracks if curr_track is None else torch.as_tensor(curr_track, device=dev, dtype=f32)
@@ -365,82 +352,77 @@ class DynamicModel(Model):
         n_obj = obj_pose.shape[1]
         K = mc.nerf_mlp.class_num if self.config.use_semantic else 0
         new = lambda *shape, dtype=f32: torch.empty(*shape, device=dev, dtype=dtype)
-        ws = torch.empty(max(int(L.nlr_workspace_bytes(self._handle, n)), 1 << 20), dtype=torch.uint8, device=dev)
-        st = _lib.current_stream()
+        ws = torch.empty(max(int(_lib.lib().nlr_workspace_bytes(self._handle, n)), 1 << 20), dtype=torch.uint8, device=dev)
         n_levels = len(mc.level_samples())
         prev_s = prev_w = None
         n_prev = 0
         hist: List[Dict[str, torch.Tensor]] = []
         r: Dict[str, torch.Tensor] = {}
-        with torch.cuda.device(dev):
-            for li, (S, dilation, anneal) in enumerate(mc.level_schedule(train_frac)):
-                last = li == n_levels - 1
-                sdist, tdist = new(n, S + 1), new(n, S + 1)
-                _lib.check(L.nlr_resample_level(_lib.ptr(prev_s), _lib.ptr(prev_w), n_prev, float(dilation), float(anneal),
-                                                float(mc.resample_padding), S, None, _lib.ptr(near), _lib.ptr(far), float(mc.power_lambda),
-                                                n, _lib.ptr(sdist), _lib.ptr(tdist), st), "nlr_resample_level")
-                density = new(n, S)
-                rgb = new(3, n, S) if last else None
-                sem = new(K, n, S) if (last and K) else None
-                _lib.check(L.nlr_mlp_level(self._handle, li, C.byref(rays), _lib.ptr(tdist), n, sample_n, sample_m, None, None,
-                                           _lib.ptr(density), _lib.ptr(rgb), _lib.ptr(sem), None, _lib.ptr(ws), ws.numel(), st), "nlr_mlp_level")
-                # ---- dynamic objects: overwrite the samples inside each track's box (models.py:401-477), on the rays that
-                # can reach a box at all (a few % of a sweep); one host sync per level for the per-track counts
-                # owner of every sample (nlr_box_winner: the last track whose box holds the interval midpoint; the reference's
-                # track loop overwrites earlier tracks, models.py:415,475), then only the owned samples - 0.1-2 % of a sweep -
-                # are gathered, all tracks of one class through one ObjMLP call with a latent code per point
-                winner = new(n, S, dtype=torch.int32)
-                _lib.check(L.nlr_box_winner(_lib.ptr(tdist), _lib.ptr(origins), _lib.ptr(dirs), _lib.ptr(box_params), n, S, n_obj,
-                                            _lib.ptr(winner), st), "nlr_box_winner")
-                obj_mask = winner >= 0
-                sel = obj_mask.nonzero()                                                   # host sync 1: [P, 2]
-                if sel.shape[0]:
-                    ri, si = sel[:, 0], sel[:, 1]
-                    tr = winner[ri, si].long()
-                    order = torch.sort(self._class_rank[tr], stable=True)[1]
-                    ri, si, tr = ri[order], si[order], tr[order]
-                    per_class = torch.bincount(self._class_rank[tr], minlength=len(self._class_list)).tolist()   # host sync 2
-                    p_all, d_all = box_frame(origins, dirs, viewdirs, tdist, box_params, ri, si, tr)
-                    lat_all = self._latent_table[tr]
-                    idx = ri * S + si
-                    lo = 0
-                    for rank, cnt in enumerate(per_class):
-                        if cnt == 0:
-                            continue
-                        sl = slice(lo, lo + cnt)
-                        lo += cnt
-                        o = self.obj_mlps[self._class_list[rank]].forward(p_all[sl], d_all[sl], lat_all[sl])
-                        density.view(-1)[idx[sl]] = o["density"]
-                        if last:
-                            rgb.view(3, -1)[:, idx[sl]] = o["rgb"].t()
-                            if sem is not None:
-                                sem.view(K, -1)[:, idx[sl]] = o["semantic"].t()
-                weights, depth_l = new(n, S), new(n)
-                out = _lib.NlrOut()
-                if last:
-                    r = {"rgb": new(n, 3), "depth": new(n)}
-                    if K:
-                        r["semantic"] = new(n, K)
-                    if compute_extras:
-                        for k in ("acc", "distance_mean", "distance_median", "distance_percentile_5", "distance_percentile_95"):
-                            r[k] = new(n)
-                    if scale_factor > 0:
-                        r["points"] = new(n, 3)
-                        if K:
-                            r["labels"] = new(n, dtype=torch.int32)
-                    for k, t in r.items():
-                        setattr(out, k, t.data_ptr())
-                _lib.check(L.nlr_composite_level(_lib.ptr(density), _lib.ptr(tdist), _lib.ptr(dirs), _lib.ptr(rgb), _lib.ptr(sem), None,
-                                                 _lib.ptr(far), _lib.ptr(origins), n, S, K, int(mc.opaque_background), mc.deterministic_bg(),
-                                                 int(compute_extras and last), float(scale_factor if last else 0.0), _lib.ptr(weights),
-                                                 C.byref(out) if last else None, _lib.ptr(depth_l), st), "nlr_composite_level")
-                h = {"depth": depth_l, "obj_mask": obj_mask}
-                if want_history:
-                    h.update(sdist=sdist, tdist=tdist, weights=weights, density=density)
+        for li, (S, dilation, anneal) in enumerate(mc.level_schedule(train_frac)):
+            last = li == n_levels - 1
+            sdist, tdist = new(n, S + 1), new(n, S + 1)
+            _lib.call("nlr_resample_level", prev_s, prev_w, n_prev, dilation, anneal, mc.resample_padding, S, None, near, far,
+                      mc.power_lambda, n, sdist, tdist)
+            density = new(n, S)
+            rgb = new(3, n, S) if last else None
+            sem = new(K, n, S) if (last and K) else None
+            _lib.call("nlr_mlp_level", self._handle, li, rays, tdist, n, sample_n, sample_m, None, None, density, rgb, sem, None, ws,
+                      ws.numel())
+            # ---- dynamic objects: overwrite the samples inside each track's box (models.py:401-477), on the rays that
+            # can reach a box at all (a few % of a sweep); one host sync per level for the per-track counts
+            # owner of every sample (nlr_box_winner: the last track whose box holds the interval midpoint; the reference's
+            # track loop overwrites earlier tracks, models.py:415,475), then only the owned samples - 0.1-2 % of a sweep -
+            # are gathered, all tracks of one class through one ObjMLP call with a latent code per point
+            winner = new(n, S, dtype=torch.int32)
+            _lib.call("nlr_box_winner", tdist, origins, dirs, box_params, n, S, n_obj, winner)
+            obj_mask = winner >= 0
+            sel = obj_mask.nonzero()                                                   # host sync 1: [P, 2]
+            if sel.shape[0]:
+                ri, si = sel[:, 0], sel[:, 1]
+                tr = winner[ri, si].long()
+                order = torch.sort(self._class_rank[tr], stable=True)[1]
+                ri, si, tr = ri[order], si[order], tr[order]
+                per_class = torch.bincount(self._class_rank[tr], minlength=len(self._class_list)).tolist()   # host sync 2
+                p_all, d_all = box_frame(origins, dirs, viewdirs, tdist, box_params, ri, si, tr)
+                lat_all = self._latent_table[tr]
+                idx = ri * S + si
+                lo = 0
+                for rank, cnt in enumerate(per_class):
+                    if cnt == 0:
+                        continue
+                    sl = slice(lo, lo + cnt)
+                    lo += cnt
+                    o = self.obj_mlps[self._class_list[rank]].forward(p_all[sl], d_all[sl], lat_all[sl])
+                    density.view(-1)[idx[sl]] = o["density"]
                     if last:
-                        h["rgb"] = rgb.permute(1, 2, 0)
+                        rgb.view(3, -1)[:, idx[sl]] = o["rgb"].t()
                         if sem is not None:
-                            h["semantic"] = sem.permute(1, 2, 0)
-                hist.append(h)
-                prev_s, prev_w, n_prev = sdist, weights, S
+                            sem.view(K, -1)[:, idx[sl]] = o["semantic"].t()
+            weights, depth_l = new(n, S), new(n)
+            out = _lib.NlrOut()
+            if last:
+                r = {"rgb": new(n, 3), "depth": new(n)}
+                if K:
+                    r["semantic"] = new(n, K)
+                if compute_extras:
+                    for k in ("acc", "distance_mean", "distance_median", "distance_percentile_5", "distance_percentile_95"):
+                        r[k] = new(n)
+                if scale_factor > 0:
+                    r["points"] = new(n, 3)
+                    if K:
+                        r["labels"] = new(n, dtype=torch.int32)
+                for k, t in r.items():
+                    setattr(out, k, t.data_ptr())
+            _lib.call("nlr_composite_level", density, tdist, dirs, rgb, sem, None, far, origins, n, S, K, mc.opaque_background,
+                      mc.deterministic_bg(), compute_extras and last, scale_factor if last else 0.0, weights, out if last else None,
+                      depth_l)
+            h = {"depth": depth_l, "obj_mask": obj_mask}
+            if want_history:
+                h.update(sdist=sdist, tdist=tdist, weights=weights, density=density)
+                if last:
+                    h["rgb"] = rgb.permute(1, 2, 0)
+                    if sem is not None:
+                        h["semantic"] = sem.permute(1, 2, 0)
+            hist.append(h)
+            prev_s, prev_w, n_prev = sdist, weights, S
         return r, hist

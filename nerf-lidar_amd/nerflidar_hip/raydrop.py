@@ -169,10 +169,7 @@ def train_step(model: UNet, optim, vgg_loss: VGGLoss, img, gt_mask, gt_range, vg
 def range_projection(points, semantic=None, rgb=None, H=32, W=1024, fov_up=10.67, fov_down=-30.67):
     """LaserScan.do_range_projection on the GPU (libnerflidar_hip.so `nlr_range_project`; no CPU fallback).
     points [N,3] float64 CUDA tensor in the LiDAR frame; returns dict of [H,W,...] CUDA tensors."""
-    import ctypes as C
     from . import _lib
-    if not points.is_cuda:
-        raise RuntimeError("points must be a CUDA tensor")
     pts = points.double().contiguous()
     n, dev = pts.shape[0], pts.device
     sem = None if semantic is None else semantic.float().contiguous()
@@ -180,13 +177,9 @@ def range_projection(points, semantic=None, rgb=None, H=32, W=1024, fov_up=10.67
     out = dict(proj_range=torch.empty(H, W, device=dev), proj_xyz=torch.empty(H, W, 3, device=dev),
                proj_semantic=torch.empty(H, W, device=dev), proj_rgb=torch.empty(H, W, 3, device=dev),
                proj_idx=torch.empty(H, W, device=dev, dtype=torch.int32), proj_mask=torch.empty(H, W, device=dev))
-    L = _lib.lib()
-    ws = torch.empty(L.nlr_range_workspace_bytes(H, W), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.nlr_range_project(_lib.ptr(pts), _lib.ptr(sem), _lib.ptr(col), n, H, W, float(fov_up), float(fov_down), _lib.ptr(ws),
-                                 ws.numel(), _lib.ptr(out["proj_range"]), _lib.ptr(out["proj_xyz"]), _lib.ptr(out["proj_semantic"]),
-                                 _lib.ptr(out["proj_rgb"]), _lib.ptr(out["proj_idx"]), _lib.ptr(out["proj_mask"]), _lib.current_stream())
-    _lib.check(rc, "nlr_range_project")
+    ws = torch.empty(_lib.lib().nlr_range_workspace_bytes(H, W), dtype=torch.uint8, device=dev)
+    _lib.call("nlr_range_project", pts, sem, col, n, H, W, fov_up, fov_down, ws, ws.numel(), out["proj_range"], out["proj_xyz"],
+              out["proj_semantic"], out["proj_rgb"], out["proj_idx"], out["proj_mask"])
     return out
 
 

@@ -27,8 +27,6 @@ class _Composite(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, density, tdist, dirs, rgbs, semantic, intensity, opaque_background, bg):
-        if not density.is_cuda:
-            raise RuntimeError("composite: density must be a CUDA tensor (no CPU fallback)")
         n, S = density.shape
         dev, f32 = density.device, torch.float32
         d = density.contiguous().float()
@@ -47,11 +45,7 @@ class _Composite(torch.autograd.Function):
         for k, t in res.items():
             setattr(out, k, t.data_ptr())
         weights = torch.empty(n, S, device=dev)
-        with torch.cuda.device(dev):
-            rc = _lib.lib().nlr_composite_level(_lib.ptr(d), _lib.ptr(td), _lib.ptr(dr), _lib.ptr(rgb_cm), _lib.ptr(sem_cm), _lib.ptr(it), None,
-                                                None, n, S, K, int(opaque_background), float(bg), 0, 0.0, _lib.ptr(weights), C.byref(out), None,
-                                                _lib.current_stream())
-        _lib.check(rc, "nlr_composite_level")
+        _lib.call("nlr_composite_level", d, td, dr, rgb_cm, sem_cm, it, None, None, n, S, K, opaque_background, bg, 0, 0.0, weights, out, None)
         ctx.save_for_backward(d, td, dr, rgb_cm, sem_cm, it)
         ctx.meta = (n, S, K, int(opaque_background), float(bg))
         sem_out = res.get("semantic", torch.zeros(n, 0, device=dev))
@@ -71,11 +65,8 @@ class _Composite(torch.autograd.Function):
         d_rgb = torch.empty(3, n, S, device=dev) if rgb_cm is not None else None
         d_sem = torch.empty(K, n, S, device=dev) if K else None
         d_int = torch.empty(n, S, device=dev) if it is not None else None
-        with torch.cuda.device(dev):
-            rc = _lib.lib().nlr_composite_backward(_lib.ptr(d), _lib.ptr(td), _lib.ptr(dr), _lib.ptr(rgb_cm), _lib.ptr(sem_cm), _lib.ptr(it), n, S, K,
-                                                   opaque, bg, _lib.ptr(g_rgb), _lib.ptr(g_depth), _lib.ptr(g_sem), _lib.ptr(g_int), _lib.ptr(g_acc),
-                                                   _lib.ptr(g_w), _lib.ptr(dd), _lib.ptr(d_rgb), _lib.ptr(d_sem), _lib.ptr(d_int), _lib.current_stream())
-        _lib.check(rc, "nlr_composite_backward")
+        _lib.call("nlr_composite_backward", d, td, dr, rgb_cm, sem_cm, it, n, S, K, opaque, bg, g_rgb, g_depth, g_sem, g_int, g_acc, g_w, dd,
+                  d_rgb, d_sem, d_int)
         d_dirs = None
         if ctx.needs_input_grad[2]:
             # dirs enters as |d| in density * dt * |d| only (render.py:176-178): dL/d|d| = sum_s dd_s density_s / |d|, d|d|/dd = d / |d|
@@ -102,15 +93,11 @@ class _HashDecay(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, embeddings, offsets_host):
-        if not embeddings.is_cuda:
-            raise RuntimeError("hash_decay: embeddings must be a CUDA tensor (no CPU fallback)")
         e = embeddings.contiguous().float()
         off = np.ascontiguousarray(np.asarray(offsets_host, np.int32))
         L, Cc = len(off) - 1, e.shape[1]
         ss = torch.empty(L, dtype=torch.float64, device=e.device)
-        with torch.cuda.device(e.device):
-            rc = _lib.lib().nlr_hash_decay_forward(_lib.ptr(e), off.ctypes.data_as(C.c_void_p), L, Cc, _lib.ptr(ss), _lib.current_stream())
-        _lib.check(rc, "nlr_hash_decay_forward")
+        _lib.call("nlr_hash_decay_forward", e, off, L, Cc, ss)
         key = (off.tobytes(), e.device)
         rows = _HashDecay._rows.get(key)                                   # (uploaded once: a host copy per step is a synchronisation)
         if rows is None:
@@ -124,10 +111,7 @@ class _HashDecay(torch.autograd.Function):
         (e,) = ctx.saved_tensors
         off = ctx.off
         grad = torch.zeros_like(e)
-        with torch.cuda.device(e.device):
-            rc = _lib.lib().nlr_hash_decay_backward(_lib.ptr(e), off.ctypes.data_as(C.c_void_p), len(off) - 1, e.shape[1], 1.0,
-                                                    _lib.ptr(grad), _lib.current_stream())
-        _lib.check(rc, "nlr_hash_decay_backward")
+        _lib.call("nlr_hash_decay_backward", e, off, len(off) - 1, e.shape[1], 1.0, grad)
         return grad.mul_(g), None   # (the upstream scalar stays on the device: float(g) would be a host read in every step)
 
 
@@ -147,24 +131,14 @@ def cast_contract(batch: Dict[str, torch.Tensor], tdist: torch.Tensor, sample_n:
     """Rows a-5 + a-6 (`nlr_cast_contract`): multisample means / bound [N,S,n,3] and stds / bound [N,S,n] of the intervals of
     `tdist`, as MLP.predict_density feeds them to the encoder (ZI/models.py:965-973).  Carries no gradient (tdist is detached in
     training, Model.stop_level_grad)."""
-    from .models import _RAY_KEYS
     n, S = tdist.shape[0], tdist.shape[1] - 1
     dev = tdist.device
-    if not tdist.is_cuda:
-        raise RuntimeError("cast_contract: tdist must be a CUDA tensor (no CPU fallback)")
-    rays, keep = _lib.NlrRays(), []
-    for k in _RAY_KEYS:
-        t = batch[k].reshape(n, -1).contiguous().float()
-        keep.append(t)
-        setattr(rays, k, t.data_ptr())
+    rays, keep = _lib.rays(batch, n)
     td = tdist.detach().contiguous().float()
     means = torch.empty(n, S, sample_n, 3, device=dev)
     stds = torch.empty(n, S, sample_n, device=dev)
-    with torch.cuda.device(dev):
-        rd = None if rand_deg is None else rand_deg.reshape(n, S, sample_n).contiguous().float()   # U[0,1) draws, render.py:150
-        rc = _lib.lib().nlr_cast_contract(C.byref(rays), _lib.ptr(td), n, S, sample_n, sample_m, float(std_scale), _lib.ptr(rd), _lib.ptr(means),
-                                          _lib.ptr(stds), _lib.current_stream())
-    _lib.check(rc, "nlr_cast_contract")
+    rd = None if rand_deg is None else rand_deg.reshape(n, S, sample_n).contiguous().float()   # U[0,1) draws, render.py:150
+    _lib.call("nlr_cast_contract", rays, td, n, S, sample_n, sample_m, std_scale, rd, means, stds)
     return means, stds
 
 
@@ -192,32 +166,25 @@ class _EncodeFeatures(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, table, encoder, batch, tdist, sample_n, sample_m, std_scale, rand_deg, re_weights, *rays):
-        from .models import _RAY_KEYS
         n, S = tdist.shape[0], tdist.shape[1] - 1
         dev = tdist.device
-        if not (table.is_cuda and tdist.is_cuda):
-            raise RuntimeError("encode_features: CUDA tensors required (no CPU fallback)")
-        keep = [batch[k].reshape(n, -1).contiguous().float() for k in _RAY_KEYS]
+        if not table.is_cuda:  # (the table travels inside NlrGridDesc, where `call` does not look)
+            raise RuntimeError("encode_features: the table must be a CUDA tensor (no CPU fallback)")
+        rays_desc, keep = _lib.rays(batch, n)
         td = tdist.detach().contiguous().float()
         rd = None if rand_deg is None else rand_deg.reshape(n, S, sample_n).contiguous().float()
         tab = table.detach().contiguous()
-        ctx.args = (encoder, keep, td, rd, int(sample_n), int(sample_m), float(std_scale), int(bool(re_weights)))
+        ctx.args = (encoder, rays_desc, keep, td, rd, int(sample_n), int(sample_m), float(std_scale), int(bool(re_weights)))
         ctx.save_for_backward(tab)
         ctx.ray_shapes = [(t.shape, t.dtype) for t in rays]
         feats = torch.empty(n * S, encoder.output_dim, device=dev)
-        rays, gd = _EncodeFeatures._descs(encoder, keep, tab)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().nlr_encode_features_forward(C.byref(rays), _lib.ptr(td), n, S, sample_n, sample_m, float(std_scale), _lib.ptr(rd),
-                                                              C.byref(gd), int(bool(re_weights)), _lib.ptr(feats), _lib.current_stream()),
-                       "nlr_encode_features_forward")
+        _lib.call("nlr_encode_features_forward", rays_desc, td, n, S, sample_n, sample_m, std_scale, rd, _EncodeFeatures._descs(encoder, tab),
+                  bool(re_weights), feats)
         return feats.reshape(n, S, encoder.output_dim)
 
     @staticmethod
-    def _descs(encoder, keep, tab):
-        from .models import _RAY_KEYS
-        rays = _lib.NlrRays()
-        for k, t in zip(_RAY_KEYS, keep):
-            setattr(rays, k, t.data_ptr())
+    def _descs(encoder, tab):
+        """The NlrGridDesc of `encoder` over the table `tab` (the ray half is `_lib.rays`)."""
         gd = _lib.NlrGridDesc()
         gd.table, gd.table_dtype = tab.data_ptr(), {torch.float32: 0, torch.float16: 1}[tab.dtype]
         gd.num_levels, gd.level_dim = encoder.num_levels, tab.shape[1]
@@ -225,38 +192,32 @@ class _EncodeFeatures(torch.autograd.Function):
         gd.log2_per_level_scale = float(np.log2(encoder.per_level_scale))
         gd.offsets = encoder._offsets_host.data_ptr()
         gd.gridtype, gd.align_corners, gd.interp = encoder.gridtype_id, int(bool(encoder.align_corners)), encoder.interp_id
-        return rays, gd
+        return gd
 
     @staticmethod
     def backward(ctx, g):
         (tab,) = ctx.saved_tensors
-        encoder, keep, td, rd, sample_n, sample_m, std_scale, re_w = ctx.args
+        encoder, rays, _keep, td, rd, sample_n, sample_m, std_scale, re_w = ctx.args
         n, S = td.shape[0], td.shape[1] - 1
         g = g.reshape(n * S, -1).contiguous().float()
-        rays, gd = _EncodeFeatures._descs(encoder, keep, tab)
+        gd = _EncodeFeatures._descs(encoder, tab)
         d_table = None
         if not ctx.ray_shapes or ctx.needs_input_grad[0]:  # (with rays: skipped when the table wants none - pose-only steps on a frozen field)
             grad = torch.zeros(tab.shape, device=tab.device, dtype=torch.float32)
             pts = torch.empty(n * S * sample_n, 3, device=tab.device)                      # scratch: unit-cube positions of the multisamples
             gpt = torch.empty(n * S * sample_n, encoder.output_dim, device=tab.device)     # scratch: their feature gradients
             from .gridencoder import backward_workspace
-            with torch.cuda.device(tab.device):
-                ws = backward_workspace(n * S * sample_n, tab.shape[1], encoder.num_levels, float(np.log2(encoder.per_level_scale)),
-                                        int(encoder.base_resolution), encoder._offsets_host, encoder.gridtype_id, encoder.align_corners, tab.device)
-                _lib.check(_lib.lib().nlr_encode_features_backward_ws(C.byref(rays), _lib.ptr(td), n, S, sample_n, sample_m, std_scale, _lib.ptr(rd),
-                                                                      C.byref(gd), re_w, _lib.ptr(g), _lib.ptr(pts), _lib.ptr(gpt), _lib.ptr(grad),
-                                                                      _lib.ptr(ws), 0 if ws is None else ws.numel(), _lib.current_stream()),
-                           "nlr_encode_features_backward")
+            ws = backward_workspace(n * S * sample_n, tab.shape[1], encoder.num_levels, float(np.log2(encoder.per_level_scale)),
+                                    int(encoder.base_resolution), encoder._offsets_host, encoder.gridtype_id, encoder.align_corners, tab.device)
+            _lib.call("nlr_encode_features_backward_ws", rays, td, n, S, sample_n, sample_m, std_scale, rd, gd, re_w, g, pts, gpt, grad, ws,
+                      0 if ws is None else ws.numel())
             d_table = grad.to(tab.dtype)
         if not ctx.ray_shapes:
             return (d_table,) + (None,) * 8
         if not any(ctx.needs_input_grad[9:13]):  # (the batch's viewdirs alone require a gradient)
             return (d_table,) + (None,) * 12
         d_rays = [torch.empty(n, 3, device=tab.device) if w else None for w in ctx.needs_input_grad[9:13]]
-        with torch.cuda.device(tab.device):
-            _lib.check(_lib.lib().nlr_encode_features_backward_rays(C.byref(rays), _lib.ptr(td), n, S, sample_n, sample_m, std_scale, _lib.ptr(rd),
-                                                                    C.byref(gd), re_w, _lib.ptr(g), *[_lib.ptr(t) for t in d_rays],
-                                                                    _lib.current_stream()), "nlr_encode_features_backward_rays")
+        _lib.call("nlr_encode_features_backward_rays", rays, td, n, S, sample_n, sample_m, std_scale, rd, gd, re_w, g, *d_rays)
         return (d_table,) + (None,) * 8 + tuple(None if t is None else t.reshape(shape).to(dtype) for t, (shape, dtype) in zip(d_rays, ctx.ray_shapes))
 
 
@@ -354,12 +315,8 @@ class _FusedMLP(torch.autograd.Function):
         acts = new(M, plan.act_w, dtype=torch.bfloat16)
         f = feats.detach().contiguous().float()
         e = enc.detach().contiguous().float()
-        L = _lib.lib()
-        with torch.cuda.device(dev):
-            st = _lib.current_stream()
-            _lib.check(L.nlr_train_pack(plan.handle, _lib.ptr(flat), st), "nlr_train_pack")
-            _lib.check(L.nlr_mlp_train_forward_split(plan.handle, _lib.ptr(f), _lib.ptr(e), M, Mc, S, _lib.ptr(density), _lib.ptr(rgb),
-                                                     _lib.ptr(sem), _lib.ptr(inten), _lib.ptr(acts), st), "nlr_mlp_train_forward_split")
+        _lib.call("nlr_train_pack", plan.handle, flat)
+        _lib.call("nlr_mlp_train_forward_split", plan.handle, f, e, M, Mc, S, density, rgb, sem, inten, acts)
         ctx.level, ctx.M, ctx.Mc = level, M, Mc
         ctx.save_for_backward(f, e, density, rgb, sem if sem is not None else density.new_empty(0),
                               inten if inten is not None else density.new_empty(0), acts)
@@ -379,10 +336,8 @@ class _FusedMLP(torch.autograd.Function):
         gd, gr, gs, gi = gp(g_density, density), gp(g_rgb, rgb), gp(g_sem, sem), gp(g_inten, inten)
         gacts = torch.empty(M, plan.act_w + 64, device=dev, dtype=torch.bfloat16)
         d_feat = torch.empty_like(f)
-        with torch.cuda.device(dev):
-            tail = (_lib.ptr(density), _lib.ptr(rgb), _lib.ptr(sem) if sem.numel() else None, _lib.ptr(acts), _lib.ptr(gd), _lib.ptr(gr),
-                    _lib.ptr(gs), _lib.ptr(gi), _lib.ptr(gacts), _lib.ptr(d_feat), _lib.current_stream())
-            _lib.check(_lib.lib().nlr_mlp_train_backward_split(plan.handle, M, Mc, level._S, *tail), "nlr_mlp_train_backward_split")
+        _lib.call("nlr_mlp_train_backward_split", plan.handle, M, Mc, level._S, density, rgb, sem if sem.numel() else None, acts, gd, gr, gs, gi,
+                  gacts, d_feat)
         if getattr(level, "_keep_debug", False):  # tests look at the kernels' raw results
             level._dbg = {k: v.detach() for k, v in dict(acts=acts, gacts=gacts, d_feat=d_feat, feats=f, enc=e, density=density, rgb=rgb,
                                                         sem=sem, inten=inten).items()}
@@ -390,10 +345,7 @@ class _FusedMLP(torch.autograd.Function):
             # ---- weight gradients: one MFMA kernel + a slab reduce (nlr_mlp_train_wgrad); views of one [n_params] f32 buffer
             d_params = torch.empty(plan.n_params, device=dev, dtype=torch.float32)
             ws = level._wgrad_workspace(dev)
-            with torch.cuda.device(dev):
-                tail = (_lib.ptr(f), _lib.ptr(e), _lib.ptr(acts), _lib.ptr(gacts), _lib.ptr(d_params), _lib.ptr(ws), ws.numel(),
-                        _lib.current_stream())
-                _lib.check(_lib.lib().nlr_mlp_train_wgrad_split(plan.handle, M, Mc, level._S, *tail), "nlr_mlp_train_wgrad_split")
+            _lib.call("nlr_mlp_train_wgrad_split", plan.handle, M, Mc, level._S, f, e, acts, gacts, d_params, ws, ws.numel())
             if getattr(level, "_keep_debug", False):
                 level._dbg["d_params"] = d_params.detach()
             grads, off = [], 0
@@ -615,9 +567,7 @@ class _PropDensity(torch.autograd.Function):
         M, F = f.shape
         raw = torch.empty(M, device=f.device)
         ps = [t.detach().contiguous().float() for t in (w1, b1, w2, b2)]
-        with torch.cuda.device(f.device):
-            _lib.check(_lib.lib().nlr_prop_mlp_forward(_lib.ptr(f), *[_lib.ptr(t) for t in ps], M, F, _lib.ptr(raw), _lib.current_stream()),
-                       "nlr_prop_mlp_forward")
+        _lib.call("nlr_prop_mlp_forward", f, *ps, M, F, raw)
         ctx.save_for_backward(f, *ps)
         return raw
 
@@ -628,9 +578,7 @@ class _PropDensity(torch.autograd.Function):
         g = g.contiguous().float()
         d_f = torch.empty_like(f) if ctx.needs_input_grad[0] else None
         d = [torch.empty_like(t) for t in (w1, b1, w2, b2)]
-        with torch.cuda.device(f.device):
-            _lib.check(_lib.lib().nlr_prop_mlp_backward(_lib.ptr(f), _lib.ptr(w1), _lib.ptr(b1), _lib.ptr(w2), _lib.ptr(b2), _lib.ptr(g), M, F,
-                                                        _lib.ptr(d_f), *[_lib.ptr(t) for t in d], _lib.current_stream()), "nlr_prop_mlp_backward")
+        _lib.call("nlr_prop_mlp_backward", f, w1, b1, w2, b2, g, M, F, d_f, *d)
         return (d_f, *d)
 
 
@@ -725,17 +673,13 @@ class _ObjFrame(torch.autograd.Function):
 def obj_frame_backward(tracks, ts, origins, dirs, viewdirs, td, ri, si, tr, g_pts, g_dirs) -> torch.Tensor:
     """`nlr_obj_frame_backward`: d/d tracks [n_obj, T, 9] of the box-frame points / directions of the K owned samples (int32 lists
     ri, si, tr sorted by (ray, sample)) contracted with their cotangents g_pts, g_dirs [K, 3]."""
-    L = _lib.lib()
     n, S, K = td.shape[0], td.shape[1] - 1, ri.shape[0]
     n_obj, T = tracks.shape[0], tracks.shape[1]
     g_pts, g_dirs = g_pts.contiguous().float(), g_dirs.contiguous().float()
     out = torch.empty_like(tracks)
-    need = L.nlr_obj_frame_backward_workspace_bytes(K, n_obj, T)
+    need = _lib.lib().nlr_obj_frame_backward_workspace_bytes(K, n_obj, T)
     ws = torch.empty(need, dtype=torch.uint8, device=tracks.device) if need else None
-    with torch.cuda.device(tracks.device):
-        _lib.check(L.nlr_obj_frame_backward(_lib.ptr(tracks), _lib.ptr(ts), _lib.ptr(origins), _lib.ptr(dirs), _lib.ptr(viewdirs), _lib.ptr(td),
-                                            n, S, n_obj, T, _lib.ptr(ri), _lib.ptr(si), _lib.ptr(tr), K, _lib.ptr(g_pts), _lib.ptr(g_dirs),
-                                            _lib.ptr(out), _lib.ptr(ws), need, _lib.current_stream()), "nlr_obj_frame_backward")
+    _lib.call("nlr_obj_frame_backward", tracks, ts, origins, dirs, viewdirs, td, n, S, n_obj, T, ri, si, tr, K, g_pts, g_dirs, out, ws, need)
     return out
 
 
@@ -743,14 +687,10 @@ def obj_frame_backward_rays(box, viewdirs, td, ri, si, tr, g_pts, g_dirs, want=(
     """`nlr_obj_frame_backward_rays`: (d_origins, d_directions, d_viewdirs) [N, 3] of the box-frame points / directions of the K owned
     samples (int32 lists ri, si, tr sorted by (ray, sample); box [N, n_obj, 8] from `track_box_params`) contracted with their
     cotangents g_pts, g_dirs [K, 3].  An output that `want` leaves out is None and is neither computed nor written."""
-    L = _lib.lib()
     n, S, K = td.shape[0], td.shape[1] - 1, ri.shape[0]
     g_pts, g_dirs = g_pts.contiguous().float(), g_dirs.contiguous().float()
     out = [torch.empty(n, 3, dtype=torch.float32, device=td.device) if w else None for w in want]
-    with torch.cuda.device(td.device):
-        _lib.check(L.nlr_obj_frame_backward_rays(_lib.ptr(box), _lib.ptr(viewdirs), _lib.ptr(td), n, S, int(box.shape[1]), _lib.ptr(ri),
-                                                 _lib.ptr(si), _lib.ptr(tr), K, _lib.ptr(g_pts), _lib.ptr(g_dirs), _lib.ptr(out[0]),
-                                                 _lib.ptr(out[1]), _lib.ptr(out[2]), _lib.current_stream()), "nlr_obj_frame_backward_rays")
+    _lib.call("nlr_obj_frame_backward_rays", box, viewdirs, td, n, S, box.shape[1], ri, si, tr, K, g_pts, g_dirs, *out)
     return tuple(out)
 
 
@@ -835,9 +775,7 @@ class TrainableModel(torch.nn.Module):
         viewdirs = batch["viewdirs"].reshape(n, 3).contiguous().float()
         winner = torch.empty(n, S, dtype=torch.int32, device=dev)
         td = tdist.detach().contiguous()
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().nlr_box_winner(_lib.ptr(td), _lib.ptr(origins), _lib.ptr(dirs), _lib.ptr(box), n, S, int(box.shape[1]),
-                                                 _lib.ptr(winner), _lib.current_stream()), "nlr_box_winner")
+        _lib.call("nlr_box_winner", td, origins, dirs, box, n, S, box.shape[1], winner)
         mask = winner >= 0
         density, sem = o["density"], o.get("semantic") if last else None
         sel = mask.nonzero()
@@ -882,7 +820,6 @@ class TrainableModel(torch.nn.Module):
         turns it on.  Values are the same bits either way; a batch of plain data ignores it."""
         mc = self.mc
         color_rays = _check_color_rays(color_rays, batch["origins"].shape[0])
-        L = _lib.lib()
         n = batch["origins"].shape[0]
         dev = batch["origins"].device
         near, far = batch["near"].reshape(n).contiguous().float(), batch["far"].reshape(n).contiguous().float()
@@ -911,10 +848,8 @@ class TrainableModel(torch.nn.Module):
             last = li == n_levels - 1
             sdist, tdist = torch.empty(n, S + 1, device=dev), torch.empty(n, S + 1, device=dev)
             jit = torch.rand(n, device=dev, generator=rand) if randomized else None
-            with torch.cuda.device(dev):
-                _lib.check(L.nlr_resample_level(_lib.ptr(prev_s), _lib.ptr(prev_w), n_prev, float(dilation), float(anneal), float(mc.resample_padding), S,
-                                                _lib.ptr(jit), _lib.ptr(near), _lib.ptr(far), float(mc.power_lambda), n, _lib.ptr(sdist), _lib.ptr(tdist),
-                                                _lib.current_stream()), "nlr_resample_level")
+            _lib.call("nlr_resample_level", prev_s, prev_w, n_prev, dilation, anneal, mc.resample_padding, S, jit, near, far, mc.power_lambda, n,
+                      sdist, tdist)
             rd = torch.rand(n, S, sample_n, device=dev, generator=rand) if randomized else None
             o = level(batch, tdist, sample_n, sample_m, rand_deg=rd, **({"color_rays": color_rays} if last else {}))
             rgbs = o["rgb"] if last else torch.zeros(n, S, 3, device=dev)   # a PropMLP renders black (models.py:1119-1122)

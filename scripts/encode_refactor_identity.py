@@ -53,7 +53,7 @@ def run(out_path):
     def rays_of(N, S, n, rand):
         sw = nlidar.synthetic_sweep(width=64, seed=3)
         idx = np.linspace(0, sw["origins"].shape[0] - 1, N).astype(np.int64)
-        batch = [torch.from_numpy(np.ascontiguousarray(sw[k][idx])).reshape(N, -1).float().to(dev) for k in _RAY_KEYS]
+        batch = {k: torch.from_numpy(np.ascontiguousarray(sw[k][idx])).to(dev) for k in _RAY_KEYS}
         g = torch.Generator().manual_seed(N * 100 + S)
         # intervals on both sides of the contraction's |x| = 1
         tdist = torch.cumsum(torch.rand(N, S + 1, generator=g) * (6.0 / (S + 1)) + 1e-3, 1).to(dev)
@@ -71,7 +71,7 @@ def run(out_path):
                     grids = [(f"C{c} {'f16' if h else 'f32'}", encoder(c, h), (0, 1)) for c in (1, 2, 4, 8) for h in (0, 1)]
                     grids += [("smoothstep C2 f32", encoder(2, 0, interp="smoothstep"), (0,)), ("align_corners C2 f32", encoder(2, 0, align=True), (0,))]
                     for gname, (enc, tab), routes in grids:
-                        rays, gd = ntrain._EncodeFeatures._descs(enc, batch, tab)
+                        (rays, held), gd = _lib.rays(batch, N), ntrain._EncodeFeatures._descs(enc, tab)
                         case = f"N{N} S{S} rand{rand} n{n} {gname}"
                         for re_w in (0, 1):
                             for generic in routes:

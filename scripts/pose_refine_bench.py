@@ -84,10 +84,9 @@ for ck_name in ("ckpt_trained_c2", "ckpt_trained"):
         f = ntrain.encode_features_fused(enc, b, td, 7, 3, re_weights=True)
         return torch.autograd.grad((f * cot).sum(), [b[k] for k in KEYS] + [enc.embeddings])
 
-    from nerflidar_hip.models import _RAY_KEYS
-    keep = [batch[k].reshape(n, -1).contiguous().float() for k in _RAY_KEYS]
     tab = enc.embeddings.detach().contiguous()
-    rays_d, gd = ntrain._EncodeFeatures._descs(enc, keep, tab)
+    rays_d, keep = _lib.rays(batch, n)
+    gd = ntrain._EncodeFeatures._descs(enc, tab)
     outs = [torch.empty(n, 3, device=dev) for _ in range(4)]
     g2 = cot.reshape(n * S, -1).contiguous()
 

@@ -472,9 +472,9 @@ def test_unsupported_grid_is_an_error_with_a_message():
     dev = torch.device("cuda")
     tab = torch.zeros(k["table"].shape[0] * 2 // 3, 3, device=dev)
     keep = [t.to(dev) for t in k["rays"]]
-    from nerflidar_hip.models import _RAY_KEYS
     order = dict(origins=keep[0], directions=keep[1], base_x=keep[2], base_y=keep[3], radii=keep[4], viewdirs=keep[1], near=keep[4], far=keep[4])
-    rays, gd = ntrain._EncodeFeatures._descs(k["enc"], [order[x] for x in _RAY_KEYS], tab)
+    rays, held = _lib.rays(order, 37)
+    gd = ntrain._EncodeFeatures._descs(k["enc"], tab)
     g = torch.zeros(37 * 3, 9, device=dev)
     out = torch.zeros(37, 3, device=dev)
     rc = _lib.lib().nlr_encode_features_backward_rays(C.byref(rays), _lib.ptr(k["tdist"].to(dev)), 37, 3, 7, 3, 0.35, None, C.byref(gd), 1, _lib.ptr(g),

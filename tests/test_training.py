@@ -644,9 +644,8 @@ def test_encode_kernels_refuse_a_sample_count_beyond_their_lane_index():
     mc, sd, batch = _ref_scene(log2_hashmap=12, width=8)
     enc = GridEncoder(input_dim=3, num_levels=6, level_dim=1, base_resolution=16, desired_resolution=512, log2_hashmap_size=12).cuda()
     n = batch["origins"].shape[0]
-    from nerflidar_hip.models import _RAY_KEYS
-    keep = [batch[k].reshape(n, -1).contiguous().float() for k in _RAY_KEYS]
-    rays, gd = ntrain._EncodeFeatures._descs(enc, keep, enc.embeddings.detach().contiguous())
+    rays, held = _lib.rays(batch, n)
+    gd = ntrain._EncodeFeatures._descs(enc, enc.embeddings.detach().contiguous())
     td = torch.zeros(64, device="cuda")
     out = torch.zeros(64, device="cuda")
     rc = _lib.lib().nlr_encode_features_forward(C.byref(rays), _lib.ptr(td), 1 << 23, 64, 7, 3, 0.35, None, C.byref(gd), 1, _lib.ptr(out), None)
