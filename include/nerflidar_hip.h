@@ -614,6 +614,32 @@ int nlr_encode_features_backward_rays(const NlrRays *rays, const float *tdist, u
                                       const float *d_features /* [N*S, L*C] */, float *d_origins, float *d_directions, float *d_base_x,
                                       float *d_base_y /* [N,3] f32, written, any may be NULL */, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * (10) Patch smoothness: the two edge-aware terms the reference puts on its patch rays (ZI/train.py:365-388 with
+ *     train_utils.py:330-348 edge_aware_loss_v2 and :411-433 edge_aware_loss_for_semantic, both with `mask=`; the patch rays of a
+ *     batch: datasets.py:357-399).  A batch is P patches of s x s pixels, row (p*s + i)*s + j = pixel (i, j) of patch p.
+ *       valid pixel   valid > 0 (NULL: all); a pair of x neighbours (i,j)-(i,j+1) or y neighbours (i,j)-(i+1,j) counts when both are
+ *       edge weight   e = exp(-mean_c |rgb - rgb'|) over the 3 channels of the pair
+ *       T_d           D = depth / (mean of depth over the patch + 1e-7);  sum_x |D - D'| e / #x + sum_y |D - D'| e / #y, sums and
+ *                     counts over all patches together
+ *       T_s           the same with sum_k |S_k - S_k'|, S_k = semantic[.., k] / (mean over the patch + 1e-5)
+ *     #x = 0 or #y = 0 (the reference's mean of nothing, then nan_to_num): both terms 0 and their gradients 0.
+ *     forward:  terms [2] = T_d, T_s (T_s = 0 without semantic); stats [8] = the four sums (depth x, depth y, semantic x, semantic
+ *               y), #x, #y, 0, 0 - what the backward reads.
+ *     backward: d_depth [P*s*s], d_semantic [P*s*s, K] = g_terms[0] dT_d/ddepth, g_terms[1] dT_s/dsemantic, OVERWRITTEN; rgb and
+ *               valid are data.  Means and differences are recomputed from the inputs; the upstream scalars stay on the device.
+ *     All pointers dev f32.  semantic = NULL skips the semantic term (then d_semantic = NULL).  2 <= s <= 64, 1 <= K <= 32, P >= 1,
+ *     workspace_bytes >= nlr_patch_smooth_workspace_bytes(P, K) (per-patch partial sums and counts of the forward; the backward takes
+ *     the same buffer and leaves it alone); anything else, or a NULL required pointer, is NLR_ERR_INVALID with nothing launched.  No
+ *     atomics: a fixed-order reduction, bitwise repeatable values and gradients.
+ * ------------------------------------------------------------------------------------------ */
+size_t nlr_patch_smooth_workspace_bytes(uint32_t P, uint32_t K);
+int nlr_patch_smooth_forward(const float *depth, const float *semantic, const float *rgb, const float *valid, uint32_t P, uint32_t s,
+                             uint32_t K, float *terms, float *stats, void *workspace, size_t workspace_bytes, void *stream);
+int nlr_patch_smooth_backward(const float *depth, const float *semantic, const float *rgb, const float *valid, uint32_t P, uint32_t s,
+                              uint32_t K, const float *stats, const float *g_terms, float *d_depth, float *d_semantic, void *workspace,
+                              size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,7 +2,9 @@
 
 Small elementwise / scan work on [rays, samples] arrays, written with torch ops so that autograd carries the gradients to
 the stages that have HIP backward kernels (compositing, fused MLP, hash grid).  Each function states the reference lines it
-follows; `tests/golden/fn_losses.npz` holds the reference's own values and gradients for the first four.
+follows; `tests/golden/fn_losses.npz` holds the reference's own values and gradients for the first four.  The one exception is
+`patch_smoothness` (the two terms of the patch rays, `fn_smooth.npz`): on CUDA tensors it is a HIP operator with its own backward
+(`training.patch_smooth`), because written with torch ops it is ~80 launches per step.
 
 Formulations differ from the reference where that is cheaper and numerically at least as good:
   * interval look-ups use one `torch.searchsorted` per query instead of an [.., n, m] comparison cube
@@ -160,10 +162,58 @@ def intensity_loss(pred: torch.Tensor, target: torch.Tensor, lidar_mask: torch.T
     return 0.1 * torch.where(m, d.pow(2), torch.zeros_like(d)).sum() / m.sum().clamp_min(1)
 
 
+# ---- patch smoothness (train.py:365-388; train_utils.py:330-348, 411-433) -------------------------------------------------------
+def _patch_smoothness_torch(depth, semantic, rgb, valid, s: int):
+    """The two terms with torch ops in the dtype of `depth`: the CPU path and, in float64, the yardstick of the HIP operator.  The
+    reference selects the valid pairs with boolean indexing and takes their mean; here the pair mask multiplies and the count divides
+    (same value up to the order of the sum, no data-dependent shape), and `torch.where` on the counts stands for its NaN -> 0."""
+    dt = depth.dtype
+    P = depth.numel() // (s * s)
+    rgb = rgb.reshape(P, s, s, 3).to(dt)
+    v = torch.ones(P, s, s, dtype=dt, device=depth.device) if valid is None else (valid.reshape(P, s, s) > 0).to(dt)
+    wx = v[:, :, :-1] * v[:, :, 1:] * torch.exp(-(rgb[:, :, :-1] - rgb[:, :, 1:]).abs().mean(-1))
+    wy = v[:, :-1] * v[:, 1:] * torch.exp(-(rgb[:, :-1] - rgb[:, 1:]).abs().mean(-1))
+    nx, ny = (v[:, :, :-1] * v[:, :, 1:]).sum(), (v[:, :-1] * v[:, 1:]).sum()
+    live = (nx > 0) & (ny > 0)
+
+    def term(x, eps):  # x [P, s, s, channels]
+        D = x / (x.mean(dim=(1, 2), keepdim=True) + eps)
+        gx = (D[:, :, :-1] - D[:, :, 1:]).abs().sum(-1)
+        gy = (D[:, :-1] - D[:, 1:]).abs().sum(-1)
+        t = (gx * wx).sum() / nx.clamp_min(1) + (gy * wy).sum() / ny.clamp_min(1)
+        return torch.where(live, t, torch.zeros_like(t))
+
+    t_d = term(depth.reshape(P, s, s, 1), 1e-7)
+    t_s = term(semantic.reshape(P, s, s, -1).to(dt), 1e-5) if semantic is not None else torch.zeros_like(t_d)
+    return t_d, t_s
+
+
+def patch_smoothness(depth: torch.Tensor, semantic: Optional[torch.Tensor], rgb: torch.Tensor, valid: Optional[torch.Tensor], patch_size: int,
+                     backend: str = "auto"):
+    """(T_d, T_s): `edge_aware_loss_v2(rgb_patch, depth_patch, mask=)` and `edge_aware_loss_for_semantic(rgb_patch, sem_patch, mask=)` as
+    train.py:381,386 calls them, before their weights and nan_to_num.  depth [P s s], semantic [P s s, K] or None (T_s = 0), rgb [P s s, 3]
+    (the target colours: data), valid [P s s] or None (> 0: the pixel takes part; data), rows patch-major as datasets.py:357-399 flattens
+    them.  Edge weights exp(-mean_c |rgb - rgb'|), depth and every class divided by their mean over the patch (+ 1e-7 / 1e-5), one mean
+    over the valid x pairs of ALL patches plus one over the y pairs; no valid x pair or no valid y pair: both terms 0 with zero gradient.
+    backend: "hip" = `training.patch_smooth` (nlr_patch_smooth_forward / _backward: float32 CUDA tensors, no fallback), "torch" = the
+    restatement above in the inputs' dtype, "auto" = "hip" for CUDA tensors and "torch" for CPU tensors."""
+    s = int(patch_size)
+    if s < 2 or depth.numel() == 0 or depth.numel() % (s * s):
+        raise ValueError(f"patch_smoothness: {depth.numel()} rows are not a positive number of {s} x {s} patches (patch_size >= 2)")
+    if backend not in ("auto", "hip", "torch"):
+        raise ValueError(f"patch_smoothness: backend {backend!r} (auto, hip, torch)")
+    if backend == "hip" or (backend == "auto" and depth.is_cuda):
+        from .training import patch_smooth
+        return patch_smooth(depth, semantic, rgb, valid, s)
+    return _patch_smoothness_torch(depth.reshape(-1), semantic, rgb, valid, s)
+
+
 def nusc_masks(batch: Dict[str, torch.Tensor], lidar_supervision: bool = False, only_lidar_supervision: bool = False,
                instance_obj: bool = False, aug_road: bool = False) -> Dict[str, torch.Tensor]:
     """The per-ray masks of a nuScenes batch exactly as train.py:288-324 derives them (dataset_loader == 'nusc'), returned under the keys
-    `total_loss` reads: mask_rgb, depth_mask, sem_mask, lidar_mask (bool).  Reference quirk kept: `batch['mask']` is first replaced by
+    `total_loss` reads: mask_rgb, depth_mask, sem_mask, lidar_mask (bool), and patch_valid (float: the pixels the smoothness terms of
+    the patch rays take part with, train.py:374-375's `where(mask > 0, 0, 1)` of the mask as lines 287-291 leave it, for every ray).
+    Reference quirk kept: `batch['mask']` is first replaced by
     `mask == 0` (a bool) and the colour mask is then `that == 0`, i.e. colour is supervised where the ORIGINAL mask is non-zero."""
     m = batch["mask"] == 0                                           # train.py:288
     if instance_obj:
@@ -171,6 +221,7 @@ def nusc_masks(batch: Dict[str, torch.Tensor], lidar_supervision: bool = False, 
     if aug_road:
         m = m.clone()
         m[batch["aug_mask"] == 1] = 1                                # :292
+    patch_valid = torch.where(m > 0, 0.0, 1.0)                       # :375
     patch = batch["patch_mask"] if "patch_mask" in batch else torch.zeros_like(batch["mask"])
     rgb = torch.logical_and(m == 0, patch == 0)                      # :311
     depth = torch.logical_and(batch["depth"] > 0, rgb)               # :313
@@ -183,7 +234,7 @@ def nusc_masks(batch: Dict[str, torch.Tensor], lidar_supervision: bool = False, 
         sem[lidar] = False
         if only_lidar_supervision:
             depth[~lidar] = False
-    return dict(mask_rgb=rgb, depth_mask=depth, sem_mask=sem, lidar_mask=lidar)
+    return dict(mask_rgb=rgb, depth_mask=depth, sem_mask=sem, lidar_mask=lidar, patch_valid=patch_valid)
 
 
 def colourless_count(n_rays: int, fraction: float) -> int:
@@ -205,12 +256,28 @@ def check_colourless(batch: Dict[str, torch.Tensor], color_rays: int) -> None:
 def total_loss(renderings: List[Dict[str, torch.Tensor]], ray_history: List[Dict[str, torch.Tensor]], batch: Dict[str, torch.Tensor], *,
                data_kind: str = "charb", charb_padding: float = 1e-3, data_coarse_mult: float = 0.0, data_mult: float = 1.0,
                interlevel_mult: float = 0.0, anti_interlevel_mult: float = 0.01, pulse_width: Sequence[float] = (0.03, 0.003),
-               distortion_mult: float = 0.005, depth_lam: float = 0.1, sem_lam: float = 0.01) -> Dict[str, torch.Tensor]:
+               distortion_mult: float = 0.005, depth_lam: float = 0.1, sem_lam: float = 0.01, patch_size: int = 0,
+               patch_rays: Optional[Sequence[int]] = None, smo_lam: float = 0.01, s_lam: float = 0.01) -> Dict[str, torch.Tensor]:
     """The dictionary `losses` of train.py:326-446 for the terms this path covers (defaults = configs.py); the caller adds the
     hash-decay term (`training.hash_decay_loss`) and sums.  Batch keys (all optional except rgb): rgb [N,3], mask_rgb [N],
-    depth [N] + depth_mask [N], semantic [N] + sem_mask [N], intensity [N] + lidar_mask [N]."""
+    depth [N] + depth_mask [N], semantic [N] + sem_mask [N], intensity [N] + lidar_mask [N].
+    patch_size > 1 with patch_rays = (row0, P): the rays [row0, row0 + P * patch_size^2) are P pixel patches, flattened patch-major
+    (`Config.patch_size`, datasets.py:357-399; the masks take them out of every other data term), and get the smoothness terms of
+    train.py:365-388: `d_smo` on the rendered depth and, when the rendering has `semantic`, `s_smo` on the class probabilities
+    (`patch_smoothness`; valid pixels from batch['patch_valid'], see `nusc_masks`; without that key every pixel is valid)."""
     out = {"data": data_loss(renderings, batch["rgb"], batch.get("mask_rgb"), data_kind, charb_padding, data_coarse_mult, data_mult)}
     last = renderings[-1]
+    if patch_size > 1 and patch_rays is not None:
+        row0, n_patch = int(patch_rays[0]), int(patch_rays[1])
+        rows = slice(row0, row0 + n_patch * patch_size ** 2)
+        if n_patch < 1 or row0 < 0 or rows.stop > last["depth"].shape[0]:
+            raise ValueError(f"patch_rays = {tuple(patch_rays)} with patch_size = {patch_size}: rows [{rows.start}, {rows.stop}) of {last['depth'].shape[0]} rays")
+        sem = last["semantic"][rows] if "semantic" in last else None
+        valid = batch["patch_valid"][rows] if "patch_valid" in batch else None
+        t_d, t_s = patch_smoothness(last["depth"][rows], sem, batch["rgb"][rows, :3], valid, patch_size)
+        out["d_smo"] = torch.nan_to_num(smo_lam * t_d)               # train.py:383
+        if sem is not None:
+            out["s_smo"] = torch.nan_to_num(s_lam * t_s)             # :388
     if "depth" in batch:
         out["depth"] = depth_loss(last["depth"], batch["depth"], batch.get("depth_mask", batch["depth"] > 0), depth_lam)
     if "semantic" in batch and "semantic" in last:

@@ -13,7 +13,7 @@ Geometry is stated in metres in the SENSOR-aligned frame (z up, the frame `lidar
 """
 from __future__ import annotations
 
-from typing import Dict, Optional
+from typing import Dict, Optional, Sequence
 
 import numpy as np
 import torch
@@ -150,11 +150,48 @@ def random_lidar_rays(n: int, seed: int, step: int, device, rot_seed: int = 0, s
                 semantic=torch.full((n,), 255.0, device=dev), mask=torch.ones(n, device=dev))
 
 
-def supervise(batch: Dict[str, torch.Tensor], rot_seed: int = 0, scale_factor: float = 1.0 / 250.0, colourless: int = 0) -> Dict[str, torch.Tensor]:
+def random_patch_rays(n_patches: int, patch_size: int, seed: int, step: int, device, rot_seed: int = 0, scale_factor: float = 1.0 / 250.0,
+                      origin_range: float = 0.01, width: int = 1600, height: int = 900, focal: float = 1266.0) -> Dict[str, torch.Tensor]:
+    """`n_patches` pixel patches of patch_size x patch_size pinhole rays (`camera.pixels_to_rays`, ZI/camera_utils.py:454-564) into the
+    scene, flattened patch-major as the reference's loader does (datasets.py:357-399): row (p * s + i) * s + j is the pixel in row i,
+    column j of patch p.  Per patch a camera at one of the sensor positions of `random_lidar_rays`, level, with a random heading, and a
+    random patch of its width x height image (the nuScenes camera's 1600 x 900 at f = 1266).  Same keys as `random_lidar_rays`, so the
+    two concatenate; `supervise(.., patch_rows=)` gives the rows their colours from `cast`.  Deterministic in (seed, step)."""
+    from . import camera as ncamera
+    s = int(patch_size)
+    if n_patches < 1 or s < 2 or s > min(width, height):
+        raise ValueError(f"random_patch_rays: {n_patches} patches of size {s} in a {width} x {height} image")
+    dev = torch.device(device)
+    rng = np.random.default_rng([seed, step, 0x9A7C])
+    pos = np.stack([synth.uniform(rot_seed, 9100 + i, (3,), -origin_range, origin_range) for i in range(64)]).astype(np.float64)
+    R = nlidar.seeded_rotation(rot_seed)
+    pixtocam = np.linalg.inv(np.array([[focal, 0, width / 2], [0, focal, height / 2], [0, 0, 1.0]]))
+    jj, ii = np.meshgrid(np.arange(s), np.arange(s), indexing="xy")       # jj: column (x), ii: row (y); row-major = i * s + j
+    parts = []
+    for _ in range(n_patches):
+        yaw = rng.uniform(0, 2 * np.pi)
+        fwd, up = np.array([np.sin(yaw), np.cos(yaw), 0.0]), np.array([0.0, 0.0, 1.0])
+        c2w = np.concatenate([R @ np.stack([np.cross(fwd, up), up, -fwd], axis=1), pos[rng.integers(64)][:, None]], axis=1)  # OpenGL camera: looks along -z
+        x0, y0 = rng.integers(0, width - s + 1), rng.integers(0, height - s + 1)
+        parts.append(ncamera.pixels_to_rays((x0 + jj).reshape(-1).astype(np.float64), (y0 + ii).reshape(-1).astype(np.float64), pixtocam, c2w))
+    o, d, v, r, ip, bx, by = (np.concatenate([p[k] for p in parts], axis=0) for k in range(7))
+    n = o.shape[0]
+    t = lambda x: torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(dev)
+    col = lambda val: torch.full((n, 1), float(val), device=dev)
+    return dict(origins=t(o), directions=t(d), viewdirs=t(v), radii=t(r), imageplane=t(ip), lossmult=col(1.0), near=col(2.0 * scale_factor),
+                far=col(500.0 * scale_factor), cam_idx=col(0.0), base_x=t(bx), base_y=t(by), rgb=torch.zeros(n, 3, device=dev),
+                semantic=torch.full((n,), 255.0, device=dev), mask=torch.ones(n, device=dev))
+
+
+def supervise(batch: Dict[str, torch.Tensor], rot_seed: int = 0, scale_factor: float = 1.0 / 250.0, colourless: int = 0,
+              patch_rows: Optional[Sequence[int]] = None) -> Dict[str, torch.Tensor]:
     """Adds the supervision keys train.py:283-424 reads for LiDAR rays (`rgb`, `depth`, `semantic`, `intensity`, and the masks
     `losses.total_loss` takes) to a ray batch, from the analytic scene.  colourless: the last that many rays get `mask_rgb` =
     `sem_mask` = False, as train.py:316-320 sets them for the LiDAR rays at the end of a mixed batch (depth and intensity stay
-    supervised); pass `color_rays = N - colourless` to `training.training_step` with such a batch."""
+    supervised); pass `color_rays = N - colourless` to `training.training_step` with such a batch.
+    patch_rows = (row0, n): these rows are patch rays (`random_patch_rays`): every mask is False on them, as train.py:310-314 takes
+    `patch_mask == 1` out of the colour, depth and semantic masks and they are no LiDAR rays; their `rgb` is what the smoothness terms
+    weigh edges with (`losses.total_loss(patch_size=, patch_rays=)`)."""
     n = batch["origins"].shape[0]
     gt = cast(batch["origins"].reshape(n, 3), batch["directions"].reshape(n, 3), nlidar.seeded_rotation(rot_seed), scale_factor)
     out = dict(batch)
@@ -166,6 +203,13 @@ def supervise(batch: Dict[str, torch.Tensor], rot_seed: int = 0, scale_factor: f
             raise ValueError(f"colourless must lie in [0, {n}], got {colourless}")
         keep = torch.arange(n, device=ones.device) < n - colourless
         out.update(mask_rgb=keep, sem_mask=keep)
+    if patch_rows is not None:
+        row0, rows = int(patch_rows[0]), int(patch_rows[1])
+        if not 0 <= row0 <= row0 + rows <= n:
+            raise ValueError(f"patch_rows = ({row0}, {rows}) outside the {n} rays")
+        idx = torch.arange(n, device=ones.device)
+        keep = (idx < row0) | (idx >= row0 + rows)
+        out.update({k: out[k] & keep for k in ("mask_rgb", "depth_mask", "sem_mask", "lidar_mask")})
     return out
 
 

@@ -10,6 +10,8 @@ contract of ZI/lidar_utils.py:8-33) and supervised by ray casting (`scene.superv
 through the HIP backward kernels, Adam), and `checkpoints.save_checkpoint` writes `checkpoint_<step>.ckpt` at the end.  Afterwards the
 checkpoint is read back through `checkpoints.model_from_checkpoint` and a held-out sweep is rendered on the fused inference path and
 compared with the analytic ground truth (metres, label accuracy), so that a run reports whether the field it leaves is a scene.
+With `--patch-size S` a `--patch-fraction` of every batch is pinhole pixel patches (`scene.random_patch_rays`) supervised only by the
+smoothness terms of train.py:365-388; the batch is ordered pixel | patch | lidar (`batch_layout`) and the summary reports d_smo, s_smo.
 """
 from __future__ import annotations
 
@@ -66,6 +68,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--colourless-fraction", type=float, default=0.0,
                     help="the last round(F * rays) rays of every batch carry no colour or semantic supervision (mask_rgb = sem_mask = 0, as "
                          "train.py:316-320 sets them for LiDAR rays) and skip the view MLP (training_step(color_rays=..)); 0: off")
+    ap.add_argument("--patch-size", type=int, default=0,
+                    help="Config.patch_size (nuscenes_single.gin:10: 32): a --patch-fraction of every batch is pinhole pixel patches of this size "
+                         "(scene.random_patch_rays) whose only supervision is the edge-aware smoothness of the rendered depth and class "
+                         "probabilities (train.py:365-388: d_smo, s_smo); 0 or 1: no patches")
+    ap.add_argument("--patch-fraction", type=float, default=0.25, help="share of the batch that is patch rays (datasets.py:357-399: a quarter)")
     ap.add_argument("--pose-refine", action="store_true",
                     help="pose refinement (Config.pose_refine, train.py:199-221): the rays of every batch belong to --pose-frames frames whose "
                          "poses carry a seeded error (scene.perturb_frames); a PoseNet learns the correction over the whole run and the "
@@ -84,16 +91,45 @@ def pose_error(posenet, seed: int, frames: int, dev, scale_factor: float, rays: 
         return nscene.hit_point_error_m(ntrain.refine_batch(bad, posenet(bad["glo_idx"])), true, scale_factor)
 
 
-def main(argv=None) -> int:
+def batch_layout(rays: int, colourless_fraction: float = 0.0, patch_size: int = 0, patch_fraction: float = 0.25):
+    """(color_rays, n_patches, colourless) of a batch ordered  pixel | patch | lidar:  the rays with colour supervision, then
+    n_patches = floor(patch_fraction * rays / patch_size^2) patches (patch_size > 1), then the colourless LiDAR rays.  The patches open
+    the colourless tail, so `color_rays` (None when the whole batch has colour) is the row they start at."""
     from .losses import colourless_count
+    colourless = colourless_count(rays, colourless_fraction)
+    if not 0.0 <= patch_fraction <= 1.0:
+        raise ValueError(f"patch fraction must lie in [0, 1], got {patch_fraction}")
+    n_patches = int(patch_fraction * rays) // patch_size ** 2 if patch_size > 1 else 0
+    if colourless + n_patches * patch_size ** 2 > rays:
+        raise ValueError(f"{n_patches} patches of {patch_size}^2 rays and {colourless} colourless rays do not fit into {rays} rays")
+    tail = colourless + n_patches * patch_size ** 2
+    return (rays - tail if tail else None), n_patches, colourless
+
+
+def make_batch(rays: int, seed: int, step: int, dev, scale_factor: float, colourless: int = 0, n_patches: int = 0, patch_size: int = 0):
+    """The supervised batch of a step in the order of `batch_layout`; also returns patch_rays = (row0, n_patches) for
+    `losses.total_loss`, or None without patches."""
+    n_patch_rows = n_patches * patch_size ** 2
+    lid = nscene.random_lidar_rays(rays - n_patch_rows, seed, step, dev, seed, scale_factor)
+    if not n_patches:
+        return nscene.supervise(lid, seed, scale_factor, colourless=colourless), None
+    row0 = rays - colourless - n_patch_rows
+    pat = nscene.random_patch_rays(n_patches, patch_size, seed, step, dev, seed, scale_factor)
+    both = {k: torch.cat([lid[k][:row0], pat[k], lid[k][row0:]], 0) for k in lid}
+    return nscene.supervise(both, seed, scale_factor, colourless=colourless + n_patch_rows, patch_rows=(row0, n_patch_rows)), (row0, n_patches)
+
+
+def main(argv=None) -> int:
     ap = build_parser()
     a = ap.parse_args(argv)
     if a.fused_wgrad and not a.fused:
         ap.error("--fused-wgrad requires --fused 1")
     if not 0.0 <= a.colourless_fraction <= 1.0:
         ap.error("--colourless-fraction must lie in [0, 1]")
-    colourless = colourless_count(a.rays, a.colourless_fraction)
-    color_rays = a.rays - colourless if colourless else None
+    try:
+        color_rays, n_patches, colourless = batch_layout(a.rays, a.colourless_fraction, a.patch_size, a.patch_fraction)
+    except ValueError as e:
+        ap.error(str(e))
     if not torch.cuda.is_available():
         raise RuntimeError("train_scene needs a GPU: the training operators have no CPU fallback")
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -115,13 +151,13 @@ def main(argv=None) -> int:
     for step in range(1, a.steps + 1):                                     # train.py:180: steps count from 1
         for g in opt.param_groups:
             g["lr"] = lr_fn(step)                                          # train.py:187-190
-        batch = nscene.supervise(nscene.random_lidar_rays(a.rays, a.seed, step, dev, a.seed, a.scale_factor), a.seed, a.scale_factor,
-                                 colourless=colourless)
+        batch, patch_rays = make_batch(a.rays, a.seed, step, dev, a.scale_factor, colourless, n_patches, a.patch_size)
+        patch_kw = dict(patch_size=a.patch_size, patch_rays=patch_rays) if patch_rays else {}
         if posenet is not None:
             batch, _, _ = nscene.perturb_frames(batch, a.pose_frames, a.seed)
         train_frac = float(np.clip((step - 1) / max(a.steps - 1, 1), 0, 1))  # train.py:184
         terms = ntrain.training_step(tm, opt, batch, train_frac=train_frac, randomized=True, hash_decay_mult=a.hash_decay,
-                                     depth_lam=a.depth_lam, sem_lam=a.sem_lam, as_tensors=True, color_rays=color_rays, step=step, **pose_kw)
+                                     depth_lam=a.depth_lam, sem_lam=a.sem_lam, as_tensors=True, color_rays=color_rays, step=step, **pose_kw, **patch_kw)
         if step % a.log_every == 0 or step == 1 or step == a.steps:          # the only host read of the loop
             torch.cuda.synchronize()
             rec = dict(step=step, lr=lr_fn(step), elapsed_s=round(time.time() - t0, 1), **{k: round(float(v), 6) for k, v in terms.items()})
@@ -140,6 +176,8 @@ def main(argv=None) -> int:
     summary = dict(workload=a.workload, log2_hashmap=a.log2_hashmap, steps=a.steps, rays_per_step=a.rays, fused=bool(a.fused), fused_wgrad=a.fused_wgrad,
                    colourless_fraction=a.colourless_fraction, train_seconds=round(train_s, 1), train_rays_per_s=round(a.steps * a.rays / train_s), checkpoint=path,
                    checkpoint_bytes=os.path.getsize(path), restored_step=step, held_out_sweep=ev, final_terms=log[-1])
+    if n_patches:  # the final step's smoothness terms (also in final_terms): zero would mean the patches saw no valid pair
+        summary.update(patch_size=a.patch_size, patches_per_step=n_patches, d_smo=log[-1].get("d_smo"), s_smo=log[-1].get("s_smo"))
     if posenet is not None:
         nckpt.save_posenet(a.out, posenet, a.steps, pn_opt)
         summary["pose_refine"] = dict(frames=a.pose_frames, hit_point_error_m_before=round(pose_err_before, 4),

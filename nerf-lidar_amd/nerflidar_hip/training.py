@@ -1,6 +1,7 @@
 """Training on the fused path (scope row f-3): the operators with HIP backward kernels and the modules that chain them.
 
   * differentiable compositing (`nlr_composite_level` / `nlr_composite_backward`) and the hash-decay regulariser;
+  * the edge-aware smoothness terms of the patch rays (`nlr_patch_smooth_forward` / `_backward`, `patch_smooth`);
   * `gridencoder.GridEncoder` (HIP forward + backward + total-variation gradient, Z/gridencoder/grid.py:24-198);
   * the NerfMLP either as torch Linear modules or through the fused MFMA forward / backward (`_FusedMLP`);
   * `TrainableNerfLevel`, `TrainablePropLevel`, `TrainableModel`: the reference's `Model.forward` with autograd (proposal
@@ -123,6 +124,53 @@ def hash_decay_loss(encoders, mult: float = 1.0) -> torch.Tensor:
         l = _HashDecay.apply(enc.embeddings, enc._offsets_host)
         total = l if total is None else total + l
     return mult * total
+
+
+class _PatchSmooth(torch.autograd.Function):
+    """nlr_patch_smooth_forward / _backward: the edge-aware smoothness terms of the patch rays (ZI/train.py:365-388) as one operator.
+    Returns terms [2] = (T_d, T_s); gradients to depth and semantic, rgb and valid are data.  Nothing of size [P, s, s, K] is kept
+    between the passes besides the inputs themselves, and the upstream gradient stays on the device."""
+    _workspaces: Dict = {}  # device -> uint8 tensor, grown on demand (only the forward writes it, and reads it back in the same call)
+
+    @staticmethod
+    def _workspace(dev, P, K):
+        need = int(_lib.lib().nlr_patch_smooth_workspace_bytes(P, K))
+        ws = _PatchSmooth._workspaces.get(dev)
+        if ws is None or ws.numel() < need:
+            ws = _PatchSmooth._workspaces[dev] = torch.empty(need, dtype=torch.uint8, device=dev)
+        return ws
+
+    @staticmethod
+    def forward(ctx, depth, semantic, rgb, valid, s):
+        d = depth.reshape(-1).contiguous().float()
+        P = d.numel() // (s * s)
+        sem = None if semantic is None else semantic.reshape(d.numel(), -1).contiguous().float()
+        K = 1 if sem is None else sem.shape[1]
+        c = rgb.reshape(d.numel(), 3).contiguous().float()
+        v = None if valid is None else valid.reshape(-1).contiguous().float()
+        terms, stats = torch.empty(2, device=d.device), torch.empty(8, device=d.device)
+        ws = _PatchSmooth._workspace(d.device, P, K)
+        _lib.call("nlr_patch_smooth_forward", d, sem, c, v, P, s, K, terms, stats, ws, ws.numel())
+        ctx.save_for_backward(d, sem, c, v, stats)
+        ctx.meta = (P, s, K, depth.shape, None if semantic is None else semantic.shape)
+        return terms
+
+    @staticmethod
+    def backward(ctx, g_terms):
+        d, sem, c, v, stats = ctx.saved_tensors
+        P, s, K, d_shape, sem_shape = ctx.meta
+        d_depth = torch.empty_like(d)
+        d_sem = None if sem is None else torch.empty_like(sem)
+        ws = _PatchSmooth._workspace(d.device, P, K)
+        _lib.call("nlr_patch_smooth_backward", d, sem, c, v, P, s, K, stats, g_terms.contiguous().float(), d_depth, d_sem, ws, ws.numel())
+        return d_depth.reshape(d_shape), None if d_sem is None else d_sem.reshape(sem_shape), None, None, None
+
+
+def patch_smooth(depth, semantic, rgb, valid, patch_size: int):
+    """(T_d, T_s) of `losses.patch_smoothness` on the HIP operator: float32 CUDA tensors, rows patch-major; semantic / valid may be
+    None (T_s is then a constant 0).  The refusals are the library's (2 <= patch_size <= 64, at most 32 classes)."""
+    terms = _PatchSmooth.apply(depth, semantic, rgb, valid, int(patch_size))
+    return terms[0], terms[1]
 
 
 # ---- a trainable NerfMLP level: fused cast/contract + HIP grid op (fwd/bwd) + torch Linear stack + HIP compositing (fwd/bwd) ----------
