@@ -569,6 +569,62 @@ int nlr_render_lidar_dynamic(const NlrModel *m, const NlrObjects *o, const NlrRa
                              uint32_t N, const NlrRenderCfg *cfg, const NlrOut *out, int32_t *const *winner, void *workspace,
                              size_t workspace_bytes, void *stream);
 
+/* (7e) The object branch of a level for TRAINING (ZI/models.py:401-477 as `loss.backward()` walks it, train.py:272-281,459): the
+ *      forward of nlr_objects_apply from trainable tensors, and its backward.  Nothing is read back to the host in either pass.
+ *
+ * NlrObjTrainPlan: made of shapes only.  nlr_obj_train_plan_create takes the NlrObjectsDesc of nlr_objects_create and the same
+ *      envelope (trunk hidden 64, bottleneck <= 64, view width <= 32, depth <= 4, deg_view <= 4, skip_layer_dir concat, split_latent,
+ *      level_dim 1 / 2 / 4) with f32 tables only and at most 128 tracks (the per-track sums of the weight-gradient kernel live in LDS);
+ *      anything else is NLR_ERR_UNSUPPORTED with a message.  The Linear weight / bias pointers, grid.table and latents of the
+ *      descriptor are NOT read: n_params_host [n_classes] receives the length of every class's flat f32 DEVICE parameter buffer, which
+ *      holds, in the order density_layer.0, density_layer.2, lin_second_stage_0..D-1, rgb_layer, each weight (row-major [out, in])
+ *      then its bias.  nlr_obj_train_param_layout returns the offsets (weight, bias per Linear; the count, or a negative status);
+ *      nlr_obj_train_desc_layout the same offsets followed by the buffer's length, from a descriptor alone (host arithmetic, no device).
+ *      nlr_obj_train_pack (params[c] = class c's buffer, a host array of device pointers) re-packs the kernel's weight images on the
+ *      device: call it after every optimiser step.  Tables and latent codes are passed to every call (tables[c] = class c's f32 table,
+ *      latents [n_tracks, latent_size], both device tensors read in place).
+ *
+ * nlr_obj_train_forward: owner map -> per-class lists (sample order) -> the class's network -> density [N,S], rgb [3,N,S], semantic
+ *      [K,N,S] overwritten in place at the owned samples; winner [N,S] int32 receives the owner map.  Owner map and lists come from
+ *      the kernels of nlr_objects_apply; the networks run in its layout but sum every Linear as the reference's torch Linear does (one
+ *      f32 FMA chain from zero, the bias added last), so the values are within nlr_objects_apply's summation-order noise of it and
+ *      follow the reference's step more closely.  rgb / semantic may be NULL (proposal levels: density only, no backward).  The workspace keeps the
+ *      owner map, the lists and their counts for the backward.
+ *
+ * nlr_obj_train_backward: same plan, tensors and WORKSPACE as the forward it follows (rgb form).  g_density [N,S], g_rgb [3,N,S] =
+ *      gradients of the merged tensors (the one-hot semantic is a constant; entries of unowned samples are not read).  Per class c:
+ *      d_params[c] [n_params] f32 OVERWRITTEN, in the order of the flat buffer; grad_tables[c] ACCUMULATED into (float atomics, zero
+ *      it first, like nlr_encode_features_backward); d_latents [n_tracks, latent_size] OVERWRITTEN, an exact zero row for a track that
+ *      owns no sample.  The activations are recomputed (the forward's code, the same bits), one lane per owned sample, and every Linear's input and pre-activation
+ *      gradient go to the workspace (f32, N * S rows whatever the classes own: capacity, so no count reaches the host).  Weight and
+ *      bias gradients are GEMMs over those rows, accumulated in registers per 64-row chunk, written as 96 slabs per (class, Linear)
+ *      and summed in slab order: no atomics, and the same inputs give the same bits in d_params and d_latents.  The latent code
+ *      enters through Linear layers only, so its gradient and that of the weights it multiplies are products of weight slices / codes
+ *      with the PER-TRACK sums of the pre-activation gradients, formed in the same reduction; no [samples, latent_size] tensor exists.
+ *      Not here: gradients of the box frame (tracks, rays) - see 7c / 7d.
+ *
+ * nlr_obj_train_workspace_bytes(plan, N, S, backward): backward = 0 for a forward whose backward never runs (the size of
+ *      nlr_objects_workspace_bytes), 1 adds (act_width + gact_width) * N * S * 4 bytes and the slabs (REF shape 65 536 x 32, shipped
+ *      ObjMLP: 221 + 196 columns = 3.3 GiB; 96 * classes * ~20 k floats of slabs).
+ * Refused with nothing launched and a message naming the argument: a NULL required pointer (plan, tables / tables[c], latents, rays'
+ *      origins / directions / viewdirs, tdist, box_params, density, winner; g_density, g_rgb, d_params[c], grad_tables[c], d_latents),
+ *      n_obj != the plan's track count, N * S >= 2^32, box_params not 16-byte aligned (NLR_ERR_INVALID), a workspace below
+ *      nlr_obj_train_workspace_bytes (NLR_ERR_WORKSPACE).  N = 0, S = 0 or n_obj = 0 returns NLR_OK and touches nothing. */
+typedef struct NlrObjTrainPlan NlrObjTrainPlan;
+int nlr_obj_train_plan_create(const NlrObjectsDesc *desc, NlrObjTrainPlan **out, uint32_t *n_params_host, void *stream);
+void nlr_obj_train_plan_destroy(NlrObjTrainPlan *p);
+int nlr_obj_train_param_layout(const NlrObjTrainPlan *p, uint32_t cls, uint32_t *offsets_host, uint32_t capacity);
+int nlr_obj_train_desc_layout(const NlrObjectsDesc *desc, uint32_t cls, uint32_t *offsets_host, uint32_t capacity);
+int nlr_obj_train_pack(NlrObjTrainPlan *p, const float *const *params, void *stream);
+size_t nlr_obj_train_workspace_bytes(const NlrObjTrainPlan *p, uint32_t N, uint32_t S, int backward);
+int nlr_obj_train_forward(NlrObjTrainPlan *p, const float *const *tables, const float *latents, const NlrRays *rays, const float *tdist,
+                          const float *box_params, uint32_t N, uint32_t S, uint32_t n_obj, float *density, float *rgb, float *semantic,
+                          uint32_t K, int32_t *winner, void *workspace, size_t workspace_bytes, void *stream);
+int nlr_obj_train_backward(NlrObjTrainPlan *p, const float *const *tables, const float *latents, const NlrRays *rays, const float *tdist,
+                           const float *box_params, uint32_t N, uint32_t S, uint32_t n_obj, const float *g_density, const float *g_rgb,
+                           float *const *d_params, float *d_latents, float *const *grad_tables, void *workspace, size_t workspace_bytes,
+                           void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * (8) PropMLP density network for training (ZI/models.py:887-889,996-997 with disable_rgb = True):
  *     raw [M] = W2 relu(W1 f + b1) + b2, f = [M, F] grid features (F = L*C <= 16), nn.Linear layouts W1 [64, F], W2 [1, 64];

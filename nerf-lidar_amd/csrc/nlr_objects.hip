@@ -1044,3 +1044,6 @@ extern "C" int nlr_objects_apply(const NlrObjects *o, const NlrRays *rays, const
     return nlr_objects_apply_impl(o, rays, tdist, box_params, N, S, n_obj, density, rgb, semantic, K, winner_out, workspace, workspace_bytes,
                                   (hipStream_t)stream);
 }
+
+// ---- the training form of the branch: plan, forward, backward (header section 7e) ---------------------------------------------
+#include "nlr_objects_train.h"

@@ -1,0 +1,953 @@
+// Training form of the dynamic-object branch (header section 7e).  This file is the tail of nlr_objects.hip - one translation unit:
+// the kernels below go through the box-frame map, the owner / scan / scatter kernels, the ObjNet image and the obj_* layer helpers of
+// that file, on the plan's own NlrObjects.
+//
+//   forward   owner map -> per-class lists (the kernels of nlr_objects_apply) -> nlr_objtrain_kernel<.., FWD = true>: nlr_objmlp_kernel's
+//             layout from the weight image nlr_obj_train_pack made of the flat buffers, every Linear summed in the reference's order
+//             (one FMA chain from zero, bias last: obj_zero / obj_add_bias)
+//   backward  (1) nlr_objtrain_kernel<.., FWD = false>: one lane per owned sample.  It repeats that forward (same code, same bits), writes
+//                 every layer's input to `acts` and every Linear's pre-activation gradient to `gacts` (column-major [column][row]:
+//                 a wave stores 256 contiguous bytes per column), and scatters the grid-feature gradient into the class's table
+//                 gradient (float atomics, like every grid scatter here).  Rows are numbered class after class: the rows of class c
+//                 start at the sum of the counts of the classes before it, so both tensors have N * S rows whatever the classes own.
+//             (2) nlr_objtrain_wgrad_kernel: dW = gacts_l^T . input_l per Linear as a register-tiled f32 FMA GEMM over the rows.  A
+//                 workgroup (class, Linear, slice) walks the 64-row chunks slice, slice + 96, ... of the class, stages the chunk in
+//                 LDS, and keeps a [64 outputs x 128 inputs] accumulator tile in its 256 threads' registers; the bias gradient and
+//                 the per-track sums of the pre-activation gradient (one owner thread per output, in row order) ride along.  Its
+//                 results go to the slice's slab; no atomics.
+//             (3) nlr_objtrain_sum_kernel adds the slabs in slice order; nlr_objtrain_params_kernel writes d_params - the weight
+//                 columns that multiply the latent code are  sum_t  G_t (x) latent_t  of the per-track sums - and
+//                 nlr_objtrain_latents_kernel writes d_latents[t] = sum over those Linears of W_latent^T G_t.  No [K, latent_size]
+//                 tensor exists anywhere.
+//   The same inputs give the same bits in d_params and d_latents: the lists are in sample order, a chunk belongs to one slice, and
+//   every sum has a fixed order.
+
+#include <algorithm>
+
+#define NLR_OBJT_LINEARS (2 + NLR_OBJ_MAX_DEPTH + 1)
+#define NLR_OBJT_SLICES 96      // slabs per (class, Linear)
+#define NLR_OBJT_GS 65          // row stride of the staged gradient chunk (floats): lanes read along a row, stores walk a column
+#define NLR_OBJT_XS 132         // row stride of the staged input chunk: 16-byte aligned rows, broadcast ds_read_b128
+#define NLR_OBJT_XMAX 128       // input columns a Linear may take from `acts` (4 thread groups x 32 accumulators)
+#define NLR_OBJT_MAX_TRACKS 128 // per-track sums of a workgroup: [tracks][64] floats of LDS
+
+struct ObjTrainLin {
+    uint32_t w_off, b_off, n_out, n_in;  // in the class's flat parameter buffer: weight [n_out, n_in] row-major, bias [n_out]
+    uint32_t outp, img_w, img_b;         // in the LDS image: [n_in][outp] at img_w, bias at img_b
+    uint32_t g_col;                      // first column of its pre-activation gradient in gacts
+    uint32_t n_blk, blk[3][3];           // input blocks that are columns of acts: (acts column, count, first input column)
+    uint32_t lat_n, lat_wcol, lat_off;   // input block that is the track's latent code: count, first input column, offset in the code
+    uint32_t gt_off;                     // its per-track sums [n_tracks][n_out] in a slab (behind the n_params floats)
+};
+struct ObjTrainCls {
+    uint32_t n_lin, n_params, slab_floats, aw, gw;
+    ObjTrainLin lin[NLR_OBJT_LINEARS];
+};
+struct ObjTrainPtrs {
+    float *p[NLR_OBJ_MAX_CLASSES];
+};
+
+// the tables and the latent codes live in the caller's tensors: point the ObjNets at them, in stream order
+__global__ void nlr_objtrain_repoint_kernel(ObjNet *nets, uint32_t nc, ObjTrainPtrs tables) {
+    if (threadIdx.x < nc) nets[threadIdx.x].gp.table = tables.p[threadIdx.x];
+}
+
+// flat parameter buffers -> LDS images (the padding of an image is zero from its creation and is never written)
+__global__ void __launch_bounds__(256) nlr_objtrain_pack_kernel(const ObjTrainCls *__restrict__ tcls, const ObjNet *__restrict__ nets,
+                                                               ObjTrainPtrs params) {
+    const ObjTrainCls &tc = tcls[blockIdx.z];
+    if (blockIdx.y >= tc.n_lin) return;
+    const ObjTrainLin &L = tc.lin[blockIdx.y];
+    const float *src = params.p[blockIdx.z];
+    float *img = const_cast<float *>(nets[blockIdx.z].wpack);
+    const uint32_t tot = L.n_out * L.n_in;
+    for (uint32_t e = blockIdx.x * 256 + threadIdx.x; e < tot + L.n_out; e += gridDim.x * 256) {
+        if (e < tot) {
+            const uint32_t o = e / L.n_in, i = e - o * L.n_in;
+            img[L.img_w + i * L.outp + o] = src[L.w_off + e];
+        } else {
+            img[L.img_b + (e - tot)] = src[L.b_off + (e - tot)];
+        }
+    }
+}
+
+// ---- (1) backward by the data ----------------------------------------------------------------------------------------------
+struct ObjTrainB {
+    const float *g_density, *g_rgb;  // [N,S], [3,N,S]
+    float *acts, *gacts;             // [aw][cap], [gw][cap]
+    ObjTrainPtrs grad_tables;
+};
+
+template <int OUT>
+__device__ __forceinline__ float obj_dot_row(const float *wrow, const float (&g)[OUT]) {
+    float s[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int o = 0; o < OUT; o += 4) {
+        const f32x4 w = *reinterpret_cast<const f32x4 *>(wrow + o);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) s[e] = fmaf(w[e], g[o + e], s[e]);
+    }
+    return (s[0] + s[1]) + (s[2] + s[3]);
+}
+
+// A Linear in the reference's own order of operations.  At these widths (K = 64 .. 175) torch's Linear on the CPU (the f32 GEMM the reference
+// runs) was observed to give every output as ONE fused-multiply-add chain over the inputs in their order, started at zero, with the bias
+// added after the last input (DESIGN, round-4 f-1 x f-3): restated that way an output had the reference's bits, where nlr_objmlp_kernel (chain started at the bias) is a few ulp of the hidden units away.
+// Under the x1500 density gain of a trained-like field those ulp are 2e-5 of a density, which the resampler of the next level turns
+// into moved sample positions: training is held to the reference's step, so its forward sums as the reference does.
+template <int OUT>
+__device__ __forceinline__ void obj_zero(float (&acc)[OUT]) {
+#pragma unroll
+    for (int o = 0; o < OUT; ++o) acc[o] = 0.0f;
+}
+template <int OUT>
+__device__ __forceinline__ void obj_add_bias(float (&acc)[OUT], const float *b) {
+#pragma unroll
+    for (int o = 0; o < OUT; ++o) acc[o] = acc[o] + b[o];
+}
+
+// adjoint of nlr_level_accum_m with w_erf = 1: the 8 corner weights times the level's feature gradient, added into the table gradient
+template <int C, int MODE>
+__device__ __forceinline__ void obj_level_scatter_m(const GridParams &gp, uint32_t level, const Gauss &g, const float *gf, float *gt) {
+    float pos[3];
+    uint32_t pg[3];
+    nlr_level_cell(gp, level, g, pg, pos);
+    if (gp.interp == 1) {
+#pragma unroll
+        for (int d = 0; d < 3; ++d) pos[d] = pos[d] * pos[d] * (3.0f - 2.0f * pos[d]);
+    }
+    uint32_t idx[8];
+    nlr_corner_idx<MODE>(gp, level, pg, idx);
+    float *grid = gt + (size_t)gp.offset[level] * C;
+    const float wx[2] = {1 - pos[0], pos[0]}, wy[2] = {1 - pos[1], pos[1]}, wz[2] = {1 - pos[2], pos[2]};
+#pragma unroll
+    for (int c8 = 0; c8 < 8; ++c8) {
+        const float w = (wx[c8 & 1] * wy[(c8 >> 1) & 1]) * wz[(c8 >> 2) & 1];
+#pragma unroll
+        for (int c = 0; c < C; ++c) atomicAdd(grid + (size_t)idx[c8] * C + c, w * gf[c]);
+    }
+}
+template <int C>
+__device__ __forceinline__ void obj_level_scatter(const GridParams &gp, uint32_t level, const Gauss &g, const float *gf, float *gt) {
+    const uint32_t mode = gp.mode[level];
+    if (mode == 0) obj_level_scatter_m<C, 0>(gp, level, g, gf, gt);
+    else if (mode == 1) obj_level_scatter_m<C, 1>(gp, level, g, gf, gt);
+    else obj_level_scatter_m<C, 2>(gp, level, g, gf, gt);
+}
+
+__device__ __forceinline__ uint32_t obj_pick_mask(const uint32_t (&mv)[NLR_OBJ_MAX_DEPTH], uint32_t i) {
+    uint32_t m = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < NLR_OBJ_MAX_DEPTH; ++j) m = j == i ? mv[j] : m;
+    return m;
+}
+
+// the rows of class c: [row0, row0 + count) of acts / gacts, clipped to the capacity whatever the count buffer holds
+__device__ __forceinline__ void obj_class_rows(const uint32_t *counts, uint32_t c, uint32_t cap, uint32_t &row0, uint32_t &count) {
+    uint64_t r = 0;
+    for (uint32_t j = 0; j < c; ++j) r += counts[j];
+    count = counts[c];
+    if (r >= cap) {
+        row0 = 0;
+        count = 0;
+        return;
+    }
+    row0 = (uint32_t)r;
+    if (count > cap - row0) count = cap - row0;
+}
+
+// FWD: the forward alone - results written over a.density / a.rgb / a.sem (rgb NULL: density and semantic only), nothing saved.
+// Otherwise the backward: the same forward again (same code, same bits), then the layers walked back.
+template <int C, int LMAX, bool FWD>
+__global__ void __launch_bounds__(64 * NLR_OBJ_WAVES) nlr_objtrain_kernel(const ObjNet *__restrict__ nets, ObjApply a, ObjTrainB t) {
+    const ObjNet &net = nets[blockIdx.y];
+    const uint32_t *list = a.lists + (size_t)blockIdx.y * a.cap;
+    __shared__ __attribute__((aligned(16))) float wl[NLR_OBJ_WMAX];
+    __shared__ float slab_a[NLR_OBJ_WAVES][64 * 64];  // hidden units, bottleneck; then the bottleneck gradient, the hidden gradient
+    __shared__ float slab_v[NLR_OBJ_WAVES][32 * 64];  // view layers; then a view layer's input gradient
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    uint32_t row0, count;
+    obj_class_rows(a.counts, blockIdx.y, a.cap, row0, count);
+    if (blockIdx.x * (64 * NLR_OBJ_WAVES) >= count) return;  // (the whole workgroup)
+    for (uint32_t i = threadIdx.x * 4; i < net.wfloats; i += 64 * NLR_OBJ_WAVES * 4)
+        *reinterpret_cast<f32x4 *>(wl + i) = *reinterpret_cast<const f32x4 *>(net.wpack + i);
+    __syncthreads();
+    float *sa = slab_a[wave], *sv = slab_v[wave];
+    const size_t cap = a.cap;
+    // columns of acts: [grid | hidden 64 | bottleneck | dir enc | view 0 .. D-1]; of gacts: [hidden 64 | bottleneck | view 0 .. D-1 | rgb 4]
+    const uint32_t cH0 = net.n_grid, cBOT = cH0 + 64, cDE = cBOT + net.BW, cV = cDE + net.DE;
+    const uint32_t gBOT = 64, gV = gBOT + net.BW, gRGB = gV + net.D * net.W;
+    float *gt = FWD ? nullptr : t.grad_tables.p[blockIdx.y];
+    const bool want_rgb = !FWD || a.rgb != nullptr, save = !FWD;
+    for (uint32_t base = (blockIdx.x * NLR_OBJ_WAVES + wave) * 64; base < count; base += gridDim.x * (64 * NLR_OBJ_WAVES)) {
+        bool valid = base + lane < count;
+        uint32_t m = list[valid ? base + lane : count - 1];
+        if (m >= a.cap) {  // (a list this plan's forward did not write)
+            m = 0;
+            valid = false;
+        }
+        const uint32_t ray = m / a.S, k = m - ray * a.S;
+        float pw[3], po[3];
+        nlr_interval_midpoint(a.tdist, a.origins, a.dirs, a.S, ray, k, pw);
+        uint32_t tr = (uint32_t)a.winner[m];
+        if (tr >= a.n_obj) {
+            tr = 0;
+            valid = false;
+        }
+        const f32x4 *b = reinterpret_cast<const f32x4 *>(a.box + ((size_t)ray * a.n_obj + tr) * 8);  // (32-byte records of a float array)
+        const f32x4 b0 = b[0], b1 = b[1];
+        nlr_box_coords(b0, b1, pw, po);
+        Gauss g;
+        g.x0 = (po[0] + 1.0f) / 2.0f;
+        g.x1 = (po[1] + 1.0f) / 2.0f;
+        g.x2 = (po[2] + 1.0f) / 2.0f;
+        g.zs = 0.0f;
+        float de[3], ds0[3 * NLR_OBJ_MAX_DEG], ds1[3 * NLR_OBJ_MAX_DEG];
+        if (want_rgb) {
+            float vd[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) vd[c] = a.viewdirs[(size_t)ray * 3 + c];
+            nlr_box_dir(b0, b1, vd, de);
+#pragma unroll
+            for (int j = 0; j < NLR_OBJ_MAX_DEG; ++j)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const float xb = de[c] * (float)(1 << j);
+                    ds0[3 * j + c] = sinf(xb);
+                    ds1[3 * j + c] = sinf(xb + 0.5f * 3.14159265358979323846f);
+                }
+        }
+        float gf[LMAX * C];
+#pragma unroll
+        for (int l = 0; l < LMAX; ++l) {
+            float acc[C];
+#pragma unroll
+            for (int c = 0; c < C; ++c) acc[c] = 0.0f;
+            if ((uint32_t)l < net.gp.L) nlr_level_accum<float, C>(net.gp, l, g, 1.0f, acc);
+#pragma unroll
+            for (int c = 0; c < C; ++c) gf[l * C + c] = acc[c];
+        }
+        float *ar = t.acts + (size_t)row0 + base + lane, *gr = t.gacts + (size_t)row0 + base + lane;  // this lane's row; column stride cap
+        if (save && valid) {
+#pragma unroll
+            for (int j = 0; j < LMAX * C; ++j)
+                if ((uint32_t)j < net.n_grid) ar[j * cap] = gf[j];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) ar[(cDE + c) * cap] = de[c];
+#pragma unroll
+            for (int j = 0; j < 3 * NLR_OBJ_MAX_DEG; ++j)
+                if ((uint32_t)j < 3 * net.deg) {
+                    ar[(cDE + 3 + j) * cap] = ds0[j];
+                    ar[(cDE + 3 + 3 * net.deg + j) * cap] = ds1[j];
+                }
+        }
+        const float *lat = net.latents + (size_t)tr * net.lat_size;
+        // ---- the forward, layer by layer as nlr_objmlp_kernel walks it, every Linear summed as the reference sums it (obj_zero /
+        // obj_add_bias); the backward also writes every layer's output to acts
+        uint64_t mh = 0;  // hidden unit o passed its ReLU
+        {
+            float h[64];
+            obj_zero<64>(h);
+            obj_seg_reg<64, LMAX * C>(h, wl + net.o_d0, 0, net.n_grid, gf);
+            obj_seg_mem<64>(h, wl + net.o_d0, net.n_grid, net.lat_shape, lat);
+            obj_add_bias<64>(h, wl + net.o_bd0);
+#pragma unroll
+            for (int o = 0; o < 64; ++o) {
+                const float r = fmaxf(h[o], 0.0f);
+                sa[o * 64 + lane] = r;
+                mh |= (uint64_t)(h[o] > 0.0f) << o;
+                if (save && valid) ar[(cH0 + o) * cap] = r;
+            }
+        }
+        float xd;
+        {
+            float x0 = 0.0f;  // output 0 of density_layer.2, the raw density
+            for (uint32_t kk = 0; kk < 64; ++kk) x0 = fmaf(wl[net.o_d2 + kk * 64], sa[kk * 64 + lane], x0);
+            x0 = x0 + wl[net.o_bd2];
+            xd = x0 + net.density_bias;
+            if (FWD) {
+                if (valid) a.density[m] = xd > 20.0f ? xd : log1pf(expf(xd));  // F.softplus, models.py:1116
+                if (valid && a.sem) {  // fixed_semantic: one-hot of the class (models.py:1124-1130)
+                    for (uint32_t c = 0; c < a.K; ++c) a.sem[(size_t)c * a.N * a.S + m] = ((int32_t)c == net.class_type) ? 1.0f : 0.0f;
+                }
+                if (!want_rgb) continue;
+            }
+            float x[64];
+            obj_zero<64>(x);
+            obj_seg_lds<64>(x, wl + net.o_d2, 0, 64, sa, lane);
+            obj_add_bias<64>(x, wl + net.o_bd2);
+#pragma unroll
+            for (int o = 0; o < 64; ++o) {
+                sa[o * 64 + lane] = x[o];
+                if (save && valid && (uint32_t)o < net.BW) ar[(cBOT + o) * cap] = x[o];
+            }
+        }
+        const float *lat_tex = lat + net.lat_tex_off;
+        uint32_t mv[NLR_OBJ_MAX_DEPTH] = {0, 0, 0, 0};  // unit o of view layer i passed its ReLU
+        for (uint32_t i = 0; i < net.D; ++i) {
+            float h[32];
+            const float *wv = wl + net.o_v[i];
+            obj_zero<32>(h);
+            uint32_t row = 0;
+            if (i > 0) {
+                obj_seg_lds<32>(h, wv, 0, net.W, sv, lane);
+                row = net.W;
+            }
+            if (i == 0 || i - 1 == net.skip) {
+                obj_seg_lds<32>(h, wv, row, net.BW, sa, lane);
+                obj_seg_reg<32, 3>(h, wv, row + net.BW, 3, de);
+                obj_seg_reg<32, 3 * NLR_OBJ_MAX_DEG>(h, wv, row + net.BW + 3, 3 * net.deg, ds0);
+                obj_seg_reg<32, 3 * NLR_OBJ_MAX_DEG>(h, wv, row + net.BW + 3 + 3 * net.deg, 3 * net.deg, ds1);
+                obj_seg_mem<32>(h, wv, row + net.BW + net.DE, net.lat_tex, lat_tex);
+            }
+            obj_add_bias<32>(h, wl + net.o_bv[i]);
+            uint32_t mk = 0;
+#pragma unroll
+            for (int o = 0; o < 32; ++o) {
+                const float r = fmaxf(h[o], 0.0f);
+                sv[o * 64 + lane] = r;
+                mk |= (uint32_t)(h[o] > 0.0f) << o;
+                if (save && valid && (uint32_t)o < net.W) ar[(cV + i * net.W + o) * cap] = r;
+            }
+#pragma unroll
+            for (uint32_t j = 0; j < NLR_OBJ_MAX_DEPTH; ++j) mv[j] = j == i ? mk : mv[j];
+        }
+        float c4[4];
+        const float *wr = wl + net.o_rgb;
+        obj_zero<4>(c4);
+        obj_seg_lds<4>(c4, wr, 0, net.W, sv, lane);
+        if (net.D - 1 == net.skip) {
+            obj_seg_lds<4>(c4, wr, net.W, net.BW, sa, lane);
+            obj_seg_reg<4, 3>(c4, wr, net.W + net.BW, 3, de);
+            obj_seg_reg<4, 3 * NLR_OBJ_MAX_DEG>(c4, wr, net.W + net.BW + 3, 3 * net.deg, ds0);
+            obj_seg_reg<4, 3 * NLR_OBJ_MAX_DEG>(c4, wr, net.W + net.BW + 3 + 3 * net.deg, 3 * net.deg, ds1);
+            obj_seg_mem<4>(c4, wr, net.W + net.BW + net.DE, net.lat_tex, lat_tex);
+        }
+        obj_add_bias<4>(c4, wl + net.o_brgb);
+        if (FWD) {
+            if (valid) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {  // models.py:1251-1255
+                    const float sg = 1.0f / (1.0f + expf(-(net.premul * c4[c] + net.rgb_bias)));
+                    a.rgb[(size_t)c * a.N * a.S + m] = sg * (1.0f + 2.0f * net.rgb_pad) - net.rgb_pad;
+                }
+            }
+            continue;
+        }
+        // ---- backward.  rgb = sigmoid(premul * c4 + rgb_bias) * (1 + 2 pad) - pad (models.py:1251-1255)
+        float gc[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float sg = 1.0f / (1.0f + expf(-(net.premul * c4[c] + net.rgb_bias)));
+            const float up = valid ? t.g_rgb[(size_t)c * a.N * a.S + m] : 0.0f;
+            gc[c] = ((up * (1.0f + 2.0f * net.rgb_pad)) * (sg * (1.0f - sg))) * net.premul;
+            if (valid) gr[(gRGB + c) * cap] = gc[c];
+        }
+#pragma unroll
+        for (int o = 0; o < 64; ++o) sa[o * 64 + lane] = 0.0f;  // the bottleneck gradient collects here (every read of the bottleneck is done)
+        float gv[32];  // pre-activation gradient of the view layer in hand
+        {
+            const uint32_t mk = obj_pick_mask(mv, net.D - 1);
+#pragma unroll
+            for (int o = 0; o < 32; ++o) {
+                const f32x4 w = *reinterpret_cast<const f32x4 *>(wr + ((uint32_t)o < net.W ? o : 0) * 4);
+                const float s = (w[0] * gc[0] + w[1] * gc[1]) + w[2] * gc[2];
+                gv[o] = ((uint32_t)o < net.W && ((mk >> o) & 1u)) ? s : 0.0f;
+            }
+            if (net.D - 1 == net.skip)
+                for (uint32_t kk = 0; kk < net.BW; ++kk) {
+                    const f32x4 w = *reinterpret_cast<const f32x4 *>(wr + (net.W + kk) * 4);
+                    sa[kk * 64 + lane] += (w[0] * gc[0] + w[1] * gc[1]) + w[2] * gc[2];
+                }
+        }
+        for (uint32_t ii = net.D; ii > 0; --ii) {
+            const uint32_t i = ii - 1;
+            if (valid) {
+#pragma unroll
+                for (int o = 0; o < 32; ++o)
+                    if ((uint32_t)o < net.W) gr[(gV + i * net.W + o) * cap] = gv[o];
+            }
+            const float *wv = wl + net.o_v[i];
+            uint32_t row = 0;
+            if (i > 0) {
+                for (uint32_t kk = 0; kk < net.W; ++kk) sv[kk * 64 + lane] = obj_dot_row<32>(wv + kk * 32, gv);
+                row = net.W;
+            }
+            if (i == 0 || i - 1 == net.skip)
+                for (uint32_t kk = 0; kk < net.BW; ++kk) sa[kk * 64 + lane] += obj_dot_row<32>(wv + (row + kk) * 32, gv);
+            if (i > 0) {
+                const uint32_t mk = obj_pick_mask(mv, i - 1);
+#pragma unroll
+                for (int o = 0; o < 32; ++o) {
+                    const float s = sv[o * 64 + lane];
+                    gv[o] = ((uint32_t)o < net.W && ((mk >> o) & 1u)) ? s : 0.0f;
+                }
+            }
+        }
+        {
+            float gb[64];  // gradient of density_layer.2's output: the view layers' share, and softplus'(raw + bias) on output 0
+#pragma unroll
+            for (int o = 0; o < 64; ++o) {
+                const float s = sa[o * 64 + lane];
+                gb[o] = (uint32_t)o < net.BW ? s : 0.0f;
+            }
+            const float sp = xd > 20.0f ? 1.0f : 1.0f / (1.0f + expf(-xd));
+            gb[0] += valid ? t.g_density[m] * sp : 0.0f;
+            if (valid) {
+#pragma unroll
+                for (int o = 0; o < 64; ++o)
+                    if ((uint32_t)o < net.BW) gr[(gBOT + o) * cap] = gb[o];
+            }
+            for (uint32_t kk = 0; kk < 64; ++kk) {
+                float s = obj_dot_row<64>(wl + net.o_d2 + kk * 64, gb);
+                s = ((mh >> kk) & 1ull) ? s : 0.0f;
+                sa[kk * 64 + lane] = s;
+                if (valid) gr[kk * cap] = s;
+            }
+        }
+        float gh[64];
+#pragma unroll
+        for (int o = 0; o < 64; ++o) gh[o] = sa[o * 64 + lane];
+        float gfe[LMAX * C];
+#pragma unroll
+        for (int j = 0; j < LMAX * C; ++j) gfe[j] = (uint32_t)j < net.n_grid ? obj_dot_row<64>(wl + net.o_d0 + j * 64, gh) : 0.0f;
+        if (valid && gt && !nlr_outside_unit_cube(g)) {
+#pragma unroll
+            for (int l = 0; l < LMAX; ++l)
+                if ((uint32_t)l < net.gp.L) obj_level_scatter<C>(net.gp, l, g, gfe + l * C, gt);
+        }
+    }
+}
+
+// ---- (2) weight, bias and per-track gradients ---------------------------------------------------------------------------------
+struct ObjTrainW {
+    const uint32_t *lists, *counts;
+    const int32_t *winner;
+    uint32_t cap, n_tracks;
+    const float *acts, *gacts;
+    float *slabs;  // [NLR_OBJT_SLICES][n_classes][slab_stride]
+    uint32_t slab_stride;
+};
+
+__global__ void __launch_bounds__(256) nlr_objtrain_wgrad_kernel(const ObjTrainCls *__restrict__ tcls, ObjTrainW a) {
+    const uint32_t c = blockIdx.z;
+    const ObjTrainCls &tc = tcls[c];
+    if (blockIdx.y >= tc.n_lin) return;
+    const ObjTrainLin &L = tc.lin[blockIdx.y];
+    __shared__ float Gs[64 * NLR_OBJT_GS];
+    __shared__ __attribute__((aligned(16))) float Xs[64 * NLR_OBJT_XS];
+    __shared__ uint32_t trk[64];
+    __shared__ float Gt[NLR_OBJT_MAX_TRACKS * 64];
+    const uint32_t o = threadIdx.x & 63, q = threadIdx.x >> 6;
+    uint32_t row0, count;
+    obj_class_rows(a.counts, c, a.cap, row0, count);
+    const uint32_t *list = a.lists + (size_t)c * a.cap;
+    const size_t cap = a.cap;
+    if (L.lat_n)
+        for (uint32_t i = threadIdx.x; i < a.n_tracks * 64; i += 256) Gt[i] = 0.0f;
+    // this thread's staging columns: input column xi = q, q + 4, .. -> its column of acts (or none)
+    float acc[32], accb = 0.0f;
+#pragma unroll
+    for (int j = 0; j < 32; ++j) acc[j] = 0.0f;
+    for (uint32_t chunk = blockIdx.x; (size_t)chunk * 64 < count; chunk += NLR_OBJT_SLICES) {
+        const uint32_t r0 = chunk * 64, nrows = count - r0 < 64 ? count - r0 : 64;
+        const bool in = o < nrows;  // (staging: o is the row)
+        __syncthreads();            // the previous chunk has been read
+        const float *gsrc = a.gacts + (size_t)row0 + r0 + o, *xsrc = a.acts + (size_t)row0 + r0 + o;
+        for (uint32_t col = q; col < 64; col += 4) Gs[o * NLR_OBJT_GS + col] = (in && col < L.n_out) ? gsrc[(L.g_col + col) * cap] : 0.0f;
+        for (uint32_t xi = q; xi < NLR_OBJT_XMAX; xi += 4) {
+            uint32_t rest = xi, col = 0xffffffffu;
+            for (uint32_t bk = 0; bk < L.n_blk; ++bk) {
+                if (rest < L.blk[bk][1]) {
+                    col = L.blk[bk][0] + rest;
+                    break;
+                }
+                rest -= L.blk[bk][1];
+            }
+            Xs[o * NLR_OBJT_XS + xi] = (in && col != 0xffffffffu) ? xsrc[col * cap] : 0.0f;
+        }
+        if (L.lat_n && threadIdx.x < 64) {
+            uint32_t tr = 0;
+            if (in) {
+                const uint32_t m = list[r0 + o];
+                tr = m < a.cap ? (uint32_t)a.winner[m] : 0;
+                tr = tr < a.n_tracks ? tr : 0;
+            }
+            trk[o] = tr;
+        }
+        __syncthreads();
+        for (uint32_t r = 0; r < nrows; ++r) {
+            const float gg = Gs[r * NLR_OBJT_GS + o];
+            const float *xr = Xs + r * NLR_OBJT_XS + q * 32;
+#pragma unroll
+            for (int j = 0; j < 32; j += 4) {
+                const f32x4 x = *reinterpret_cast<const f32x4 *>(xr + j);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc[j + e] = fmaf(gg, x[e], acc[j + e]);
+            }
+            if (q == 0) {
+                accb += gg;
+                if (L.lat_n) Gt[trk[r] * 64 + o] += gg;  // (one thread owns output o: row order)
+            }
+        }
+    }
+    // the slice's slab: weights at their place in the flat buffer (the latent columns are not written here), bias, per-track sums
+    float *slab = a.slabs + ((size_t)blockIdx.x * gridDim.z + c) * a.slab_stride;
+    if (o < L.n_out) {
+#pragma unroll
+        for (int j = 0; j < 32; ++j) {
+            uint32_t rest = q * 32 + j;
+            for (uint32_t bk = 0; bk < L.n_blk; ++bk) {
+                if (rest < L.blk[bk][1]) {
+                    slab[L.w_off + o * L.n_in + L.blk[bk][2] + rest] = acc[j];
+                    break;
+                }
+                rest -= L.blk[bk][1];
+            }
+        }
+        if (q == 0) slab[L.b_off + o] = accb;
+    }
+    if (L.lat_n) {
+        // the weight columns that multiply the latent code come from the per-track sums (nlr_objtrain_params_kernel): zeros here, so that
+        // every float of a slab is written
+        for (uint32_t i = threadIdx.x; i < L.n_out * L.lat_n; i += 256) {
+            const uint32_t oo = i / L.lat_n, kk = i - oo * L.lat_n;
+            slab[L.w_off + oo * L.n_in + L.lat_wcol + kk] = 0.0f;
+        }
+        __syncthreads();
+        for (uint32_t i = threadIdx.x; i < a.n_tracks * 64; i += 256) {
+            const uint32_t tk = i >> 6, oo = i & 63;
+            if (oo < L.n_out) slab[L.gt_off + tk * L.n_out + oo] = Gt[i];
+        }
+    }
+}
+
+// ---- (3) slabs -> totals -> d_params, d_latents ----------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) nlr_objtrain_sum_kernel(const ObjTrainCls *__restrict__ tcls, const float *__restrict__ slabs,
+                                                              uint32_t slab_stride, float *__restrict__ totals) {
+    const uint32_t c = blockIdx.y, j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= tcls[c].slab_floats) return;
+    float s = 0.0f;
+    for (uint32_t sl = 0; sl < NLR_OBJT_SLICES; ++sl) s += slabs[((size_t)sl * gridDim.y + c) * slab_stride + j];
+    totals[(size_t)c * slab_stride + j] = s;
+}
+
+__global__ void __launch_bounds__(256) nlr_objtrain_params_kernel(const ObjTrainCls *__restrict__ tcls, const float *__restrict__ totals,
+                                                                 uint32_t slab_stride, const float *__restrict__ latents, uint32_t lat_size,
+                                                                 uint32_t n_tracks, ObjTrainPtrs d_params) {
+    const uint32_t c = blockIdx.y, j = blockIdx.x * 256 + threadIdx.x;
+    const ObjTrainCls &tc = tcls[c];
+    if (j >= tc.n_params) return;
+    const float *tot = totals + (size_t)c * slab_stride;
+    float v = tot[j];
+    for (uint32_t li = 0; li < tc.n_lin; ++li) {
+        const ObjTrainLin &L = tc.lin[li];
+        if (!L.lat_n || j < L.w_off || j >= L.w_off + L.n_out * L.n_in) continue;
+        const uint32_t o = (j - L.w_off) / L.n_in, i = (j - L.w_off) - o * L.n_in;
+        if (i < L.lat_wcol || i >= L.lat_wcol + L.lat_n) continue;
+        v = 0.0f;  // a weight on the latent code: sum over the tracks of (sum of its output's gradient over the track) * code
+        for (uint32_t tk = 0; tk < n_tracks; ++tk)
+            v = fmaf(tot[L.gt_off + tk * L.n_out + o], latents[(size_t)tk * lat_size + L.lat_off + (i - L.lat_wcol)], v);
+    }
+    d_params.p[c][j] = v;
+}
+
+__global__ void __launch_bounds__(256) nlr_objtrain_latents_kernel(const ObjTrainCls *__restrict__ tcls, const ObjNet *__restrict__ nets,
+                                                                  const int32_t *__restrict__ track_class, const float *__restrict__ totals,
+                                                                  uint32_t slab_stride, uint32_t lat_size, uint32_t n_tracks,
+                                                                  float *__restrict__ d_latents) {
+    const uint32_t e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= n_tracks * lat_size) return;
+    const uint32_t tk = e / lat_size, kk = e - tk * lat_size;
+    const uint32_t c = (uint32_t)track_class[tk];
+    const ObjTrainCls &tc = tcls[c];
+    const float *tot = totals + (size_t)c * slab_stride, *img = nets[c].wpack;
+    float s = 0.0f;
+    for (uint32_t li = 0; li < tc.n_lin; ++li) {
+        const ObjTrainLin &L = tc.lin[li];
+        if (kk < L.lat_off || kk >= L.lat_off + L.lat_n) continue;
+        const float *wrow = img + L.img_w + (size_t)(L.lat_wcol + (kk - L.lat_off)) * L.outp;  // the image holds W transposed
+        for (uint32_t o = 0; o < L.n_out; ++o) s = fmaf(wrow[o], tot[L.gt_off + tk * L.n_out + o], s);
+    }
+    d_latents[e] = s;
+}
+
+// ---- host side -------------------------------------------------------------------------------------------------------------------
+struct NlrObjTrainPlan {
+    NlrObjects *objs = nullptr;  // the ObjNets, their images, the latent table and track_class: what nlr_objects_apply_impl runs on
+    std::vector<ObjTrainCls> cls;
+    ObjTrainCls *cls_dev = nullptr;
+    float *lat_dev = nullptr;    // objs' latent table [n_tracks, lat_size]: the caller's codes are copied here on the stream
+    uint32_t lat_size = 0, slab_stride = 0, aw = 0, gw = 0;
+    ~NlrObjTrainPlan() {
+        if (cls_dev) (void)hipFree(cls_dev);
+        delete objs;
+    }
+};
+
+// The Linears of one class in the order of its flat buffer, from the descriptor's scalars alone: (out, in) per Linear; returns their number
+// (0: a depth outside the envelope).  The one statement of the shapes: the plan's zero-weight descriptor and nlr_obj_train_desc_layout.
+static uint32_t obj_train_shapes(const NlrObjClassDesc &cd, uint32_t (&shape)[NLR_OBJT_LINEARS][2]) {
+    const NlrMlpDesc &md = cd.mlp;
+    if (md.net_depth_viewdirs < 1 || md.net_depth_viewdirs > NLR_OBJ_MAX_DEPTH) return 0;
+    const uint32_t lat = cd.latent_size, lat_shape = lat ? (cd.split_latent ? lat / 2 : lat) : 0;
+    const uint32_t lat_tex = (lat && cd.split_latent) ? lat - lat / 2 : 0;
+    const uint32_t in_rgb = md.bottleneck_width + 3 + 6 * md.deg_view + lat_tex;
+    uint32_t n = 0, last = in_rgb;
+    shape[n][0] = 64, shape[n++][1] = md.grid.num_levels * md.grid.level_dim + lat_shape;
+    shape[n][0] = md.bottleneck_width, shape[n++][1] = 64;
+    for (uint32_t i = 0; i < md.net_depth_viewdirs; ++i) {
+        shape[n][0] = md.net_width_viewdirs, shape[n++][1] = last;
+        last = md.net_width_viewdirs + (i == md.skip_layer_dir ? in_rgb : 0);
+    }
+    shape[n][0] = 3, shape[n++][1] = last;
+    return n;
+}
+
+// host arithmetic only: the offsets (weight, bias per Linear) of class `cls` of a descriptor, then the buffer's length; returns the
+// number of entries written (2 per Linear + 1)
+extern "C" int nlr_obj_train_desc_layout(const NlrObjectsDesc *d, uint32_t cls, uint32_t *offsets_host, uint32_t capacity) {
+    NLR_CHECK_ARG(d && d->classes && offsets_host && cls < d->n_classes, "obj_train_desc_layout: NULL argument or class %u outside the descriptor", cls);
+    uint32_t shape[NLR_OBJT_LINEARS][2];
+    const uint32_t n = obj_train_shapes(d->classes[cls], shape);
+    if (!n) NLR_FAIL(NLR_ERR_UNSUPPORTED, "obj_train_desc_layout: net_depth_viewdirs %u outside [1,%d]", d->classes[cls].mlp.net_depth_viewdirs, NLR_OBJ_MAX_DEPTH);
+    NLR_CHECK_ARG(capacity >= 2 * n + 1, "obj_train_desc_layout: buffer too small (%u entries)", 2 * n + 1);
+    uint32_t off = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        offsets_host[2 * i] = off;
+        offsets_host[2 * i + 1] = off + shape[i][0] * shape[i][1];
+        off += shape[i][0] * shape[i][1] + shape[i][0];
+    }
+    offsets_host[2 * n] = off;
+    return (int)(2 * n + 1);
+}
+
+extern "C" int nlr_obj_train_plan_create(const NlrObjectsDesc *d, NlrObjTrainPlan **out, uint32_t *n_params_host, void *stream) {
+    NLR_CHECK_ARG(d && out && n_params_host, "obj_train_plan_create: NULL argument");
+    NLR_CHECK_ARG(d->n_classes >= 1 && d->n_classes <= NLR_OBJ_MAX_CLASSES && d->classes, "obj_train_plan_create: n_classes = %u outside [1,%d]",
+                  d->n_classes, NLR_OBJ_MAX_CLASSES);
+    NLR_CHECK_ARG(d->n_tracks >= 1 && d->track_class, "obj_train_plan_create: no tracks");
+    if (d->n_tracks > NLR_OBJT_MAX_TRACKS)
+        NLR_FAIL(NLR_ERR_UNSUPPORTED, "obj_train_plan_create: n_tracks = %u, the weight-gradient kernel keeps per-track sums for at most %d",
+                 d->n_tracks, NLR_OBJT_MAX_TRACKS);
+    // The plan is made of shapes: the object set is created on zero weights and zero codes of those shapes (nlr_objects_create checks
+    // the envelope and lays out the images), nlr_obj_train_pack fills the images from the flat buffers.
+    std::vector<NlrObjClassDesc> cds(d->classes, d->classes + d->n_classes);
+    size_t zmax = (size_t)d->n_tracks * d->classes[0].latent_size + 64;
+    for (NlrObjClassDesc &cd : cds) {
+        NlrMlpDesc &md = cd.mlp;
+        if (md.grid.table_dtype != 0) NLR_FAIL(NLR_ERR_UNSUPPORTED, "obj_train_plan_create: the table gradient is f32, table_dtype must be 0");
+        uint32_t shape[NLR_OBJT_LINEARS][2];
+        const uint32_t n = obj_train_shapes(cd, shape);
+        if (!n) NLR_FAIL(NLR_ERR_UNSUPPORTED, "obj_train_plan_create: net_depth_viewdirs %u outside [1,%d]", md.net_depth_viewdirs, NLR_OBJ_MAX_DEPTH);
+        NlrLinear *lin[NLR_OBJT_LINEARS] = {&md.density0, &md.density2};
+        for (uint32_t i = 0; i < md.net_depth_viewdirs; ++i) lin[2 + i] = &md.view[i];
+        lin[n - 1] = &md.rgb_layer;
+        for (uint32_t i = 0; i < n; ++i) {
+            lin[i]->out_features = shape[i][0];
+            lin[i]->in_features = shape[i][1];
+            zmax = std::max(zmax, (size_t)shape[i][0] * shape[i][1]);
+        }
+    }
+    std::vector<float> zeros(zmax, 0.0f);
+    for (NlrObjClassDesc &cd : cds) {
+        NlrMlpDesc &md = cd.mlp;
+        md.density0.weight = md.density0.bias = md.density2.weight = md.density2.bias = zeros.data();
+        for (uint32_t i = 0; i < md.net_depth_viewdirs; ++i) md.view[i].weight = md.view[i].bias = zeros.data();
+        md.rgb_layer.weight = md.rgb_layer.bias = zeros.data();
+    }
+    NlrObjectsDesc od = *d;
+    od.classes = cds.data();
+    od.latents = zeros.data();
+    std::unique_ptr<NlrObjTrainPlan> p(new NlrObjTrainPlan());
+    int rc = nlr_objects_create(&od, &p->objs, stream);
+    if (rc) return rc;
+    p->lat_size = d->classes[0].latent_size;
+    p->lat_dev = const_cast<float *>(p->objs->cls[0].latents);
+    p->cls.resize(d->n_classes);
+    for (uint32_t c = 0; c < d->n_classes; ++c) {
+        const ObjNet &n = p->objs->cls[c];
+        ObjTrainCls &tc = p->cls[c];
+        memset(&tc, 0, sizeof(tc));
+        const uint32_t in_rgb = n.BW + n.DE + n.lat_tex;
+        const uint32_t aH0 = n.n_grid, aBOT = aH0 + 64, aDE = aBOT + n.BW, aV = aDE + n.DE;
+        const uint32_t gBOT = 64, gV = gBOT + n.BW, gRGB = gV + n.D * n.W;
+        tc.aw = aV + n.D * n.W;
+        tc.gw = gRGB + 4;
+        uint32_t off = 0, gt = 0;
+        auto add = [&](uint32_t n_out, uint32_t n_in, uint32_t outp, uint32_t img_w, uint32_t img_b, uint32_t g_col) -> ObjTrainLin & {
+            ObjTrainLin &L = tc.lin[tc.n_lin++];
+            L.w_off = off;
+            L.b_off = off + n_out * n_in;
+            off = L.b_off + n_out;
+            L.n_out = n_out, L.n_in = n_in, L.outp = outp, L.img_w = img_w, L.img_b = img_b, L.g_col = g_col;
+            return L;
+        };
+        auto block = [](ObjTrainLin &L, uint32_t col, uint32_t cnt, uint32_t wcol) {
+            if (!cnt) return;
+            L.blk[L.n_blk][0] = col, L.blk[L.n_blk][1] = cnt, L.blk[L.n_blk][2] = wcol;
+            ++L.n_blk;
+        };
+        auto latent = [&](ObjTrainLin &L, uint32_t cnt, uint32_t wcol, uint32_t lat_off) {
+            if (!cnt) return;
+            L.lat_n = cnt, L.lat_wcol = wcol, L.lat_off = lat_off;
+            L.gt_off = gt;
+            gt += d->n_tracks * L.n_out;
+        };
+        // the view layers' concatenated input [bottleneck | dir enc | texture half] behind `row` columns of the previous layer
+        auto concat = [&](ObjTrainLin &L, uint32_t row) {
+            block(L, aBOT, n.BW, row);
+            block(L, aDE, n.DE, row + n.BW);
+            latent(L, n.lat_tex, row + n.BW + n.DE, n.lat_tex_off);
+        };
+        {
+            ObjTrainLin &L = add(64, n.n_grid + n.lat_shape, 64, n.o_d0, n.o_bd0, 0);
+            block(L, 0, n.n_grid, 0);
+            latent(L, n.lat_shape, n.n_grid, 0);
+        }
+        block(add(n.BW, 64, 64, n.o_d2, n.o_bd2, gBOT), aH0, 64, 0);
+        uint32_t last = in_rgb;
+        for (uint32_t i = 0; i < n.D; ++i) {
+            ObjTrainLin &L = add(n.W, last, 32, n.o_v[i], n.o_bv[i], gV + i * n.W);
+            if (i > 0) block(L, aV + (i - 1) * n.W, n.W, 0);
+            if (i == 0 || i - 1 == n.skip) concat(L, i > 0 ? n.W : 0);
+            last = n.W + (i == n.skip ? in_rgb : 0);
+        }
+        {
+            ObjTrainLin &L = add(3, last, 4, n.o_rgb, n.o_brgb, gRGB);
+            block(L, aV + (n.D - 1) * n.W, n.W, 0);
+            if (n.D - 1 == n.skip) concat(L, n.W);
+        }
+        tc.n_params = off;
+        for (uint32_t li = 0; li < tc.n_lin; ++li) tc.lin[li].gt_off += off;  // (unused where lat_n = 0)
+        tc.slab_floats = off + gt;
+        n_params_host[c] = off;
+        p->slab_stride = std::max(p->slab_stride, (tc.slab_floats + 63u) & ~63u);
+        p->aw = std::max(p->aw, tc.aw);
+        p->gw = std::max(p->gw, tc.gw);
+    }
+    NLR_HIP(hipMalloc((void **)&p->cls_dev, p->cls.size() * sizeof(ObjTrainCls)));
+    NLR_HIP(hipMemcpyAsync(p->cls_dev, p->cls.data(), p->cls.size() * sizeof(ObjTrainCls), hipMemcpyHostToDevice, (hipStream_t)stream));
+    NLR_HIP(hipStreamSynchronize((hipStream_t)stream));
+    *out = p.release();
+    return NLR_OK;
+}
+
+extern "C" void nlr_obj_train_plan_destroy(NlrObjTrainPlan *p) { delete p; }
+
+// offsets (weight, bias) of every Linear of class `cls` in its flat buffer, in the order density_layer.0, density_layer.2,
+// lin_second_stage_0..D-1, rgb_layer; returns the number of entries
+extern "C" int nlr_obj_train_param_layout(const NlrObjTrainPlan *p, uint32_t cls, uint32_t *offsets_host, uint32_t capacity) {
+    NLR_CHECK_ARG(p && offsets_host && cls < p->cls.size(), "obj_train_param_layout: NULL argument or class %u outside the plan", cls);
+    const ObjTrainCls &tc = p->cls[cls];
+    NLR_CHECK_ARG(capacity >= 2 * tc.n_lin, "obj_train_param_layout: buffer too small (%u entries)", 2 * tc.n_lin);
+    for (uint32_t i = 0; i < tc.n_lin; ++i) offsets_host[2 * i] = tc.lin[i].w_off, offsets_host[2 * i + 1] = tc.lin[i].b_off;
+    return (int)(2 * tc.n_lin);
+}
+
+extern "C" int nlr_obj_train_pack(NlrObjTrainPlan *p, const float *const *params, void *stream) {
+    NLR_CHECK_ARG(p && params, "obj_train_pack: NULL argument");
+    ObjTrainPtrs pp;
+    memset(&pp, 0, sizeof(pp));
+    for (size_t c = 0; c < p->cls.size(); ++c) {
+        NLR_CHECK_ARG(params[c], "obj_train_pack: params[%zu] is NULL", c);
+        pp.p[c] = const_cast<float *>(params[c]);
+    }
+    hipLaunchKernelGGL(nlr_objtrain_pack_kernel, dim3(8, NLR_OBJT_LINEARS, (unsigned)p->cls.size()), dim3(256), 0, (hipStream_t)stream, p->cls_dev,
+                       p->objs->nets_dev, pp);
+    NLR_LAUNCH_CHECK("nlr_objtrain_pack_kernel");
+    return NLR_OK;
+}
+
+// workspace: [what nlr_objects_apply carves: counts | owner map | lists | per-wave counts] and, for the backward,
+// [acts aw x M | gacts gw x M | slabs SLICES x classes x stride | totals classes x stride] f32
+static size_t obj_train_fwd_bytes(const NlrObjTrainPlan *p, uint32_t N, uint32_t S) { return nlr_objects_workspace_bytes(p->objs, N, S); }
+extern "C" size_t nlr_obj_train_workspace_bytes(const NlrObjTrainPlan *p, uint32_t N, uint32_t S, int backward) {
+    if (!p) return 0;
+    size_t b = obj_train_fwd_bytes(p, N, S);
+    if (backward) {
+        const size_t M = (size_t)N * S, nc = p->cls.size();
+        b += al(M * p->aw * 4) + al(M * p->gw * 4) + al((size_t)NLR_OBJT_SLICES * nc * p->slab_stride * 4) + al(nc * p->slab_stride * 4);
+    }
+    return b;
+}
+
+// the checks both passes share; *run = 0: nothing to do
+static int obj_train_check(const char *fn, const NlrObjTrainPlan *p, const float *const *tables, const float *latents, const NlrRays *rays,
+                           const float *tdist, const float *box_params, uint32_t N, uint32_t S, uint32_t n_obj, const void *workspace,
+                           size_t workspace_bytes, int backward, int *run) {
+    *run = 0;
+    NLR_CHECK_ARG(p, "%s: plan is NULL", fn);
+    if (N == 0 || S == 0 || n_obj == 0) return NLR_OK;
+    NLR_CHECK_ARG(tables, "%s: tables is NULL", fn);
+    for (size_t c = 0; c < p->cls.size(); ++c) NLR_CHECK_ARG(tables[c], "%s: tables[%zu] is NULL", fn, c);
+    NLR_CHECK_ARG(latents || p->lat_size == 0, "%s: latents is NULL", fn);
+    NLR_CHECK_ARG(rays && rays->origins && rays->directions && rays->viewdirs, "%s: rays (origins / directions / viewdirs) is NULL", fn);
+    NLR_CHECK_ARG(tdist, "%s: tdist is NULL", fn);
+    NLR_CHECK_ARG(box_params, "%s: box_params is NULL", fn);
+    NLR_CHECK_ARG(((uintptr_t)box_params & 15) == 0, "%s: box_params must be 16-byte aligned", fn);
+    NLR_CHECK_ARG(n_obj == p->objs->n_tracks, "%s: n_obj = %u boxes per ray, the plan has %u tracks", fn, n_obj, p->objs->n_tracks);
+    NLR_CHECK_ARG((size_t)N * S < (1ull << 32), "%s: N * S = %zu does not fit the 32-bit sample index", fn, (size_t)N * S);
+    const size_t need = nlr_obj_train_workspace_bytes(p, N, S, backward);
+    if (!workspace || workspace_bytes < need)
+        NLR_FAIL(NLR_ERR_WORKSPACE, "%s: workspace %zu B < nlr_obj_train_workspace_bytes() = %zu B", fn, workspace_bytes, need);
+    *run = 1;
+    return NLR_OK;
+}
+
+static int obj_train_bind(NlrObjTrainPlan *p, const float *const *tables, const float *latents, hipStream_t st) {
+    ObjTrainPtrs tp;
+    memset(&tp, 0, sizeof(tp));
+    for (size_t c = 0; c < p->cls.size(); ++c) tp.p[c] = const_cast<float *>(tables[c]);
+    hipLaunchKernelGGL(nlr_objtrain_repoint_kernel, dim3(1), dim3(64), 0, st, p->objs->nets_dev, (uint32_t)p->cls.size(), tp);
+    NLR_LAUNCH_CHECK("nlr_objtrain_repoint_kernel");
+    if (p->lat_size)
+        NLR_HIP(hipMemcpyAsync(p->lat_dev, latents, (size_t)p->objs->n_tracks * p->lat_size * 4, hipMemcpyDeviceToDevice, st));
+    return NLR_OK;
+}
+
+extern "C" int nlr_obj_train_forward(NlrObjTrainPlan *p, const float *const *tables, const float *latents, const NlrRays *rays,
+                                     const float *tdist, const float *box_params, uint32_t N, uint32_t S, uint32_t n_obj, float *density,
+                                     float *rgb, float *semantic, uint32_t K, int32_t *winner, void *workspace, size_t workspace_bytes,
+                                     void *stream) {
+    int run = 0, rc = obj_train_check("obj_train_forward", p, tables, latents, rays, tdist, box_params, N, S, n_obj, workspace, workspace_bytes, 0, &run);
+    if (rc || !run) return rc;
+    NLR_CHECK_ARG(density, "obj_train_forward: density is NULL");
+    NLR_CHECK_ARG(winner, "obj_train_forward: winner is NULL");
+    hipStream_t st = (hipStream_t)stream;
+    if ((rc = obj_train_bind(p, tables, latents, st))) return rc;
+    // owner map and lists as nlr_objects_apply_impl makes them (same kernels, same carving), then this file's forward
+    const size_t M = (size_t)N * S;
+    const uint32_t nc = (uint32_t)p->cls.size();
+    char *w = (char *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    uint32_t *counts = (uint32_t *)w;
+    int32_t *own = (int32_t *)(w + 256);
+    uint32_t *lists = (uint32_t *)(w + 256 + al(M * 4));
+    uint32_t *wave_counts = (uint32_t *)(w + 256 + al(M * 4) + al((size_t)nc * M * 4));
+    const uint32_t nblk = (uint32_t)((M + 255) / 256), nw = nblk * 4;
+    hipLaunchKernelGGL(nlr_box_owner_kernel, dim3(nblk), dim3(256), 0, st, tdist, rays->origins, rays->directions, box_params, N, S, n_obj,
+                       p->objs->track_class, nc, own, wave_counts);
+    NLR_LAUNCH_CHECK("nlr_box_owner_kernel");
+    hipLaunchKernelGGL(nlr_obj_scan_kernel, dim3(nc), dim3(1024), 0, st, wave_counts, nw, counts);
+    NLR_LAUNCH_CHECK("nlr_obj_scan_kernel");
+    hipLaunchKernelGGL(nlr_obj_scatter_kernel, dim3(nblk), dim3(256), 0, st, own, p->objs->track_class, (uint32_t)M, nc, wave_counts, lists, (uint32_t)M);
+    NLR_LAUNCH_CHECK("nlr_obj_scatter_kernel");
+    NLR_HIP(hipMemcpyAsync(winner, own, M * 4, hipMemcpyDeviceToDevice, st));
+    ObjApply a;
+    a.lists = lists;
+    a.counts = counts;
+    a.cap = (uint32_t)M;
+    a.winner = own;
+    a.tdist = tdist;
+    a.origins = rays->origins;
+    a.dirs = rays->directions;
+    a.viewdirs = rays->viewdirs;
+    a.box = box_params;
+    a.N = N;
+    a.S = S;
+    a.n_obj = n_obj;
+    a.K = semantic ? K : 0;
+    a.density = density;
+    a.rgb = rgb;
+    a.sem = semantic;
+    ObjTrainB tb;
+    memset(&tb, 0, sizeof(tb));
+    const uint32_t per = 64 * NLR_OBJ_WAVES, nb = (uint32_t)((M + per - 1) / per);
+    const uint32_t grid = p->objs->cus < nb ? p->objs->cus : nb;
+    const uint32_t C = p->objs->cls[0].gp.C;
+#define OBJT_LAUNCH(C_, LM) hipLaunchKernelGGL((nlr_objtrain_kernel<C_, LM, true>), dim3(grid, nc), dim3(64 * NLR_OBJ_WAVES), 0, st, p->objs->nets_dev, a, tb)
+    if (C == 2) OBJT_LAUNCH(2, 8);
+    else if (C == 4) OBJT_LAUNCH(4, 4);
+    else OBJT_LAUNCH(1, 16);
+#undef OBJT_LAUNCH
+    NLR_LAUNCH_CHECK("nlr_objtrain_kernel (forward)");
+    return NLR_OK;
+}
+
+extern "C" int nlr_obj_train_backward(NlrObjTrainPlan *p, const float *const *tables, const float *latents, const NlrRays *rays,
+                                      const float *tdist, const float *box_params, uint32_t N, uint32_t S, uint32_t n_obj,
+                                      const float *g_density, const float *g_rgb, float *const *d_params, float *d_latents,
+                                      float *const *grad_tables, void *workspace, size_t workspace_bytes, void *stream) {
+    int run = 0, rc = obj_train_check("obj_train_backward", p, tables, latents, rays, tdist, box_params, N, S, n_obj, workspace, workspace_bytes, 1, &run);
+    if (rc || !run) return rc;
+    NLR_CHECK_ARG(g_density && g_rgb, "obj_train_backward: g_density / g_rgb is NULL");
+    NLR_CHECK_ARG(d_params && grad_tables, "obj_train_backward: d_params / grad_tables is NULL");
+    NLR_CHECK_ARG(d_latents || p->lat_size == 0, "obj_train_backward: d_latents is NULL");
+    const uint32_t nc = (uint32_t)p->cls.size();
+    ObjTrainB tb;
+    ObjTrainPtrs dp;
+    memset(&dp, 0, sizeof(dp));
+    memset(&tb, 0, sizeof(tb));
+    for (uint32_t c = 0; c < nc; ++c) {
+        NLR_CHECK_ARG(d_params[c] && grad_tables[c], "obj_train_backward: d_params[%u] / grad_tables[%u] is NULL", c, c);
+        dp.p[c] = d_params[c];
+        tb.grad_tables.p[c] = grad_tables[c];
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if ((rc = obj_train_bind(p, tables, latents, st))) return rc;
+    const size_t M = (size_t)N * S;
+    // the forward's part of the workspace, as nlr_objects_apply_impl carved it
+    char *w = (char *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    const uint32_t *counts = (const uint32_t *)w;
+    const int32_t *winner = (const int32_t *)(w + 256);
+    const uint32_t *lists = (const uint32_t *)(w + 256 + al(M * 4));
+    w += obj_train_fwd_bytes(p, N, S) - 256;
+    float *acts = (float *)w;
+    w += al(M * p->aw * 4);
+    float *gacts = (float *)w;
+    w += al(M * p->gw * 4);
+    float *slabs = (float *)w;
+    w += al((size_t)NLR_OBJT_SLICES * nc * p->slab_stride * 4);
+    float *totals = (float *)w;
+    ObjApply a;
+    a.lists = lists;
+    a.counts = counts;
+    a.cap = (uint32_t)M;
+    a.winner = winner;
+    a.tdist = tdist;
+    a.origins = rays->origins;
+    a.dirs = rays->directions;
+    a.viewdirs = rays->viewdirs;
+    a.box = box_params;
+    a.N = N;
+    a.S = S;
+    a.n_obj = n_obj;
+    a.K = 0;
+    a.density = a.rgb = a.sem = nullptr;
+    tb.g_density = g_density;
+    tb.g_rgb = g_rgb;
+    tb.acts = acts;
+    tb.gacts = gacts;
+    const uint32_t per = 64 * NLR_OBJ_WAVES, nb = (uint32_t)((M + per - 1) / per);
+    const uint32_t grid = p->objs->cus < nb ? p->objs->cus : nb;
+    const uint32_t C = p->objs->cls[0].gp.C;
+#define OBJT_LAUNCH(C_, LM) hipLaunchKernelGGL((nlr_objtrain_kernel<C_, LM, false>), dim3(grid, nc), dim3(64 * NLR_OBJ_WAVES), 0, st, p->objs->nets_dev, a, tb)
+    if (C == 2) OBJT_LAUNCH(2, 8);
+    else if (C == 4) OBJT_LAUNCH(4, 4);
+    else OBJT_LAUNCH(1, 16);
+#undef OBJT_LAUNCH
+    NLR_LAUNCH_CHECK("nlr_objtrain_kernel (backward)");
+    ObjTrainW tw;
+    tw.lists = lists;
+    tw.counts = counts;
+    tw.winner = winner;
+    tw.cap = (uint32_t)M;
+    tw.n_tracks = n_obj;
+    tw.acts = acts;
+    tw.gacts = gacts;
+    tw.slabs = slabs;
+    tw.slab_stride = p->slab_stride;
+    hipLaunchKernelGGL(nlr_objtrain_wgrad_kernel, dim3(NLR_OBJT_SLICES, NLR_OBJT_LINEARS, nc), dim3(256), 0, st, p->cls_dev, tw);
+    NLR_LAUNCH_CHECK("nlr_objtrain_wgrad_kernel");
+    hipLaunchKernelGGL(nlr_objtrain_sum_kernel, dim3((p->slab_stride + 255) / 256, nc), dim3(256), 0, st, p->cls_dev, slabs, p->slab_stride, totals);
+    NLR_LAUNCH_CHECK("nlr_objtrain_sum_kernel");
+    hipLaunchKernelGGL(nlr_objtrain_params_kernel, dim3((p->slab_stride + 255) / 256, nc), dim3(256), 0, st, p->cls_dev, totals, p->slab_stride,
+                       p->lat_dev, p->lat_size, n_obj, dp);
+    NLR_LAUNCH_CHECK("nlr_objtrain_params_kernel");
+    if (p->lat_size) {
+        hipLaunchKernelGGL(nlr_objtrain_latents_kernel, dim3((n_obj * p->lat_size + 255) / 256), dim3(256), 0, st, p->cls_dev, p->objs->nets_dev,
+                           p->objs->track_class, totals, p->slab_stride, p->lat_size, n_obj, d_latents);
+        NLR_LAUNCH_CHECK("nlr_objtrain_latents_kernel");
+    }
+    return NLR_OK;
+}

@@ -85,8 +85,12 @@ def anti_interlevel_loss(ray_history: Sequence[Dict[str, torch.Tensor]], mult: f
         wp = h["weights"]
         term = (w_target - wp).clamp_min(0) ** 2 / (wp + 1e-5)
         if "obj_mask" in h:  # samples inside dynamic-object boxes are not held to the static envelope (train_utils.py:153-154)
-            term = term[~h["obj_mask"]]
-        total = total + term.mean()
+            # selected with `torch.where` and divided by the count, like the masked terms below `depth_loss`: no host read.  A level
+            # whose samples are all inside boxes gives 0 / 0, the reference's mean of nothing
+            keep = ~h["obj_mask"]
+            total = total + torch.where(keep, term, torch.zeros_like(term)).sum() / keep.sum().to(term.dtype)
+        else:
+            total = total + term.mean()
     return mult * total
 
 

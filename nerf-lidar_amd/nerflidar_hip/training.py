@@ -742,6 +742,168 @@ def obj_frame_backward_rays(box, viewdirs, td, ri, si, tr, g_pts, g_dirs, want=(
     return tuple(out)
 
 
+def _ptr_array(tensors):
+    """Host array of device pointers (`T *const *` of the header)."""
+    return (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def objects_desc(mlps, track_class, latent_size: int, weights: bool = False, latents=None):
+    """(`NlrObjectsDesc`, keep) of the `TrainableObjMLP`s `mlps` (one per class) and the tracks' classes.  weights = False: shapes and
+    scalars only, what `nlr_obj_train_plan_create` and `nlr_obj_train_desc_layout` read.  True: also the Linears, the tables (the
+    modules' own device tensors) and `latents` [n_tracks, latent_size] as host copies, what `nlr_objects_create` takes.  Hold `keep`
+    while the descriptor is in use."""
+    keep = []
+
+    def linear(lin):
+        w, b = (np.ascontiguousarray(t.detach().cpu().numpy(), np.float32) for t in (lin.weight, lin.bias))
+        keep.extend([w, b])
+        l = _lib.NlrLinear()
+        l.weight, l.bias, (l.out_features, l.in_features) = w.ctypes.data, b.ctypes.data, w.shape
+        return l
+    descs = (_lib.NlrObjClassDesc * len(mlps))()
+    for d, m in zip(descs, mlps):
+        cfg, md = m.cfg, d.mlp
+        md.grid = _EncodeFeatures._descs(m.encoder, m.encoder.embeddings)
+        md.disable_rgb, md.bottleneck_width = int(cfg.disable_rgb), cfg.bottleneck_width
+        md.net_depth_viewdirs, md.net_width_viewdirs = cfg.net_depth_viewdirs, cfg.net_width_viewdirs
+        md.skip_layer_dir, md.deg_view, md.class_num = cfg.skip_layer_dir, cfg.deg_view, cfg.class_num
+        md.density_bias, md.rgb_premultiplier = cfg.density_bias, cfg.rgb_premultiplier
+        md.rgb_bias, md.rgb_padding, md.re_weights = cfg.rgb_bias, cfg.rgb_padding, int(cfg.re_weights)
+        d.latent_size, d.split_latent, d.class_type = int(latent_size), int(cfg.split_latent), int(cfg.class_type)
+        if weights:
+            md.density0, md.density2 = linear(m.get_submodule("density_layer.0")), linear(m.get_submodule("density_layer.2"))
+            for i in range(cfg.net_depth_viewdirs):
+                md.view[i] = linear(m.get_submodule(f"lin_second_stage_{i}"))
+            md.rgb_layer = linear(m.rgb_layer)
+    tc = np.ascontiguousarray(track_class, np.int32)
+    od = _lib.NlrObjectsDesc()
+    od.n_classes, od.classes, od.n_tracks, od.track_class = len(mlps), descs, len(tc), tc.ctypes.data
+    keep.extend([descs, tc])
+    if weights and latents is not None:
+        lt = np.ascontiguousarray(latents.detach().cpu().numpy(), np.float32)
+        keep.append(lt)
+        od.latents = lt.ctypes.data
+    return od, keep
+
+
+def _no_plan():
+    return None
+
+
+class _ObjTrainPlan:
+    """`NlrObjTrainPlan` (header section 7e) of a model's object networks: made of the classes' shapes and the tracks' classes; knows the
+    order of every class's flat parameter buffer (`flat`) and checks it against `nlr_obj_train_param_layout` once."""
+
+    def __init__(self, mlps, track_class, latent_size: int, device):
+        from .weights import mlp_param_shapes
+        self.n_classes, self.device = len(mlps), torch.device(device)
+        od, _keep = objects_desc(mlps, track_class, latent_size)  # (shapes only: the plan reads neither weights nor tables)
+        n_params = np.zeros(len(mlps), np.int32)
+        self.handle = C.c_void_p(None)
+        _lib.call("nlr_obj_train_plan_create", od, self.handle, n_params, device=self.device)
+        self.n_params = [int(v) for v in n_params]
+        self.names = [[name for name, _, _ in mlp_param_shapes(m.cfg)] for m in mlps]
+        self._ws = None
+        for c, m in enumerate(mlps):  # the order `flat` concatenates in is the order the kernels read
+            offs = (C.c_uint32 * 32)()
+            cnt = _lib.lib().nlr_obj_train_param_layout(self.handle, c, offs, len(offs))
+            if cnt <= 0:
+                _lib.check(cnt or -1, "nlr_obj_train_param_layout")
+            want, at = [], 0
+            for name in self.names[c]:
+                lin = m.get_submodule(name)
+                want += [at, at + lin.weight.numel()]
+                at += lin.weight.numel() + lin.bias.numel()
+            if list(offs[:cnt]) != want or at != self.n_params[c]:
+                raise RuntimeError(f"nlr_obj_train_param_layout: class {c} has offsets {list(offs[:cnt])} ({self.n_params[c]} parameters), "
+                                   f"the module's Linears give {want} ({at})")
+
+    def flat(self, c: int, m) -> torch.Tensor:
+        """Class c's parameters as the flat buffer of the header, a differentiable `cat` of the module's own tensors."""
+        return torch.cat([p.reshape(-1) for name in self.names[c] for p in (m.get_submodule(name).weight, m.get_submodule(name).bias)]).float()
+
+    def pack(self, flats) -> None:
+        _lib.call("nlr_obj_train_pack", self.handle, _ptr_array(flats), device=self.device)
+
+    def workspace(self, n: int, S: int) -> torch.Tensor:
+        """The forward-only workspace, kept between calls (a forward with a backward gets one of its own, `_ObjectsFused`)."""
+        need = _lib.lib().nlr_obj_train_workspace_bytes(self.handle, n, S, 0)
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self._ws
+
+    # a plan is a handle the library owns: a copied or unpickled model gets none and makes its own on first use
+    def __deepcopy__(self, memo):
+        return None
+
+    def __reduce__(self):
+        return (_no_plan, ())
+
+    def __del__(self):
+        try:
+            _lib.lib().nlr_obj_train_plan_destroy(self.handle)
+        except Exception:
+            pass
+
+
+def objects_forward(plan: _ObjTrainPlan, tables, latents, rays_desc, td, box, density, rgb=None, semantic=None, workspace=None):
+    """`nlr_obj_train_forward` in place on density [N,S], rgb [3,N,S] / semantic [K,N,S] (None: the density-only form); returns the
+    owner map [N,S] int32.  `workspace`: a tensor of `nlr_obj_train_workspace_bytes(.., 1)` bytes when a backward follows."""
+    n, S = td.shape[0], td.shape[1] - 1
+    winner = torch.full((n, S), -1, dtype=torch.int32, device=td.device)  # (no tracks, no samples: the call writes nothing)
+    ws = plan.workspace(n, S) if workspace is None else workspace
+    _lib.call("nlr_obj_train_forward", plan.handle, _ptr_array(tables), latents, rays_desc, td, box, n, S, box.shape[1], density, rgb, semantic,
+              0 if semantic is None else semantic.shape[0], winner, ws, ws.numel())
+    return winner
+
+
+class _ObjectsFused(torch.autograd.Function):
+    """The object branch of the last level as one operator (header section 7e): (density [N,S], rgb [N,S,3], semantic [N,S,K] of the
+    static field, latent table [n_tracks, latent_size], the classes' hash tables, the classes' flat parameter buffers) -> (merged
+    density, rgb, semantic, owner mask).  forward = `nlr_obj_train_forward`; backward = `nlr_obj_train_backward` for tables, flat
+    buffers and latent codes, and the upstream gradient with the owned samples zeroed for the static tensors (the merge overwrote
+    them).  The box frame carries no gradient here.
+    The backward runs on the plan's weight images as the LAST `pack` left them (`TrainableModel.forward` packs once per forward): run a
+    forward's backward before the same model's parameters change and its next forward packs again, as `training_step` does."""
+
+    @staticmethod
+    def forward(ctx, plan, rays_desc, keep, td, box, density, rgbs, sem, latents, *tables_flats):
+        nc = plan.n_classes
+        tabs = [t.detach() for t in tables_flats[:nc]]
+        n, S = td.shape[0], td.shape[1] - 1
+        cf = torch.contiguous_format
+        dens = density.detach().float().clone(memory_format=cf)
+        rgb_t = rgbs.detach().float().permute(2, 0, 1).clone(memory_format=cf)
+        sem_t = None if sem is None else sem.detach().float().permute(2, 0, 1).clone(memory_format=cf)
+        lat = latents.detach().float().contiguous()
+        need = _lib.lib().nlr_obj_train_workspace_bytes(plan.handle, n, S, 1)
+        ws = torch.empty(need, dtype=torch.uint8, device=td.device)  # holds the lists until the backward: not shared between calls
+        winner = objects_forward(plan, tabs, lat, rays_desc, td, box, dens, rgb_t, sem_t, workspace=ws)
+        mask = winner >= 0
+        ctx.save_for_backward(td, box, lat, ws, mask, *tabs)
+        ctx.misc = (plan, rays_desc, keep)
+        ctx.mark_non_differentiable(mask)
+        return dens, rgb_t.permute(1, 2, 0), None if sem_t is None else sem_t.permute(1, 2, 0), mask
+
+    @staticmethod
+    def backward(ctx, g_dens, g_rgb, g_sem, _g_mask):
+        td, box, lat, ws, mask, *tabs = ctx.saved_tensors
+        plan, rays_desc, _keep = ctx.misc
+        n, S = td.shape[0], td.shape[1] - 1
+        dev = td.device
+        gd = torch.zeros(n, S, device=dev) if g_dens is None else g_dens.float().contiguous()
+        gr = torch.zeros(3, n, S, device=dev) if g_rgb is None else g_rgb.float().permute(2, 0, 1).contiguous()
+        d_flats = [torch.empty(k, device=dev) for k in plan.n_params]
+        d_lat = torch.empty_like(lat)
+        g_tabs = [torch.zeros_like(t) for t in tabs]
+        _lib.call("nlr_obj_train_backward", plan.handle, _ptr_array(tabs), lat, rays_desc, td, box, n, S, box.shape[1], gd, gr,
+                  _ptr_array(d_flats), d_lat, _ptr_array(g_tabs), ws, ws.numel())
+
+        def static(g, m):
+            return None if g is None else torch.where(m, torch.zeros_like(g), g)
+        return (None,) * 5 + (static(g_dens, mask), static(g_rgb, mask[..., None]), static(g_sem, mask[..., None]), d_lat, *g_tabs, *d_flats)
+
+
 class TrainableModel(torch.nn.Module):
     """`Model` (ZI/models.py:31-576, no GLO) as a trainable module: submodules `prop_mlp_<i>` and `nerf_mlp` with the reference's
     parameter names, so a reference checkpoint loads with `load_reference` and the trained `state_dict()` goes straight into
@@ -756,9 +918,20 @@ class TrainableModel(torch.nn.Module):
     hash-grid features and their gradient from the HIP grid operator, the NerfMLP from torch Linear modules or the fused MFMA
     forward / backward (`fused_mlp=True`), compositing and its gradient from `nlr_composite_level` / `nlr_composite_backward`."""
 
-    def __init__(self, mc, fused_mlp: bool = False, fused_wgrad: bool = False, tracks=None, class_names=None, obj_log2_hashmap: int = 21):
+    def __init__(self, mc, fused_mlp: bool = False, fused_wgrad: bool = False, tracks=None, class_names=None, obj_log2_hashmap: int = 21,
+                 fused_objects: bool = False):
+        """fused_objects (with `instance_obj`): every level's object merge runs through the operator of header section 7e
+        (`nlr_obj_train_forward` / `_backward`: owner map, per-class lists and the object networks on the device, weight / latent / table
+        gradients from fixed-order reductions) instead of the torch chain of `_object_merge`; a step then reads nothing back to the host.
+        Parameters, their names and `state_dict()` are the same either way.  Proposal levels replace the density only.  That is NOT what the
+        reference's merge and `_object_merge` do: a PropMLP returns a black rgb (models.py:1119-1122) which they overwrite with the
+        detached object rgb inside the boxes, so with `fused_objects=True` a proposal level's rendered rgb stays black there and a
+        nonzero `data_coarse_mult` gives another coarse data loss than the reference's (the shipped value is 0: no difference).
+        Not wired on this path, refused with NotImplementedError: tracks that require a gradient (track refinement) and ray tensors that require one (pose refinement)."""
         super().__init__()
         self.mc = mc
+        self.fused_objects = bool(fused_objects)
+        self._obj_plan = None
         for i in range(mc.num_levels - 1):
             self.add_module(f"prop_mlp_{i}", TrainablePropLevel(mc.prop_cfg(i), fused=fused_mlp))
         import dataclasses
@@ -853,6 +1026,38 @@ class TrainableModel(torch.nn.Module):
                 sem[ri[pick], si[pick]] = res["semantic"]
         return density, rgbs, sem, mask
 
+    def _fused_objects_begin(self, batch, n: int, dev):
+        """What the fused object operator needs for every level of one forward: the plan (made on first use), the classes' tables and
+        flat parameter buffers (packed into the kernels' weight images once per forward), the latent table, the ray descriptor."""
+        mlps = [getattr(self, f"obj_mlp_{cid}") for cid in self._class_list]
+        if self._obj_plan is None or self._obj_plan.device != torch.device(dev):
+            self._obj_plan = _ObjTrainPlan(mlps, [self._class_list.index(c) for c in self.class_ids], self.mc.config.latent_size, dev)
+        plan = self._obj_plan
+        flats = [plan.flat(c, m) for c, m in enumerate(mlps)]
+        plan.pack([f.detach() for f in flats])
+        tables = [m.encoder.embeddings for m in mlps]
+        latents = torch.stack([self.latent_vector_dict[f"obj_latent_{t}"] for t in range(len(self.class_ids))])
+        rays_desc, keep = _lib.rays({k: batch[k].detach() for k in ("origins", "directions", "viewdirs")}, n, optional=_lib.RAY_KEYS)
+        return plan, flats, tables, latents, rays_desc, keep
+
+    def _object_merge_fused(self, o: Dict[str, torch.Tensor], rgbs: torch.Tensor, tdist: torch.Tensor, box: torch.Tensor, last: bool, state):
+        """`_object_merge` through `nlr_obj_train_forward`: nothing is read back.  Proposal levels: the density-only form under no
+        gradient (models.py:447-449), the static density keeps its gradient outside the boxes.  Last level: `_ObjectsFused`."""
+        plan, flats, tables, latents, rays_desc, keep = state
+        td = tdist.detach().contiguous()
+        density = o["density"]
+        if not last:
+            with torch.no_grad():
+                dens = density.detach().float().clone(memory_format=torch.contiguous_format)
+                winner = objects_forward(plan, [t.detach() for t in tables], latents.detach().float().contiguous(), rays_desc, td, box, dens)
+            mask = winner >= 0
+            return torch.where(mask, dens, density), rgbs, None, mask
+        sem = o.get("semantic")
+        use_sem = sem is not None and all(getattr(self, f"obj_mlp_{cid}").cfg.use_semantic for cid in self._class_list)
+        dens, rgbs, sem_m, mask = _ObjectsFused.apply(plan, rays_desc, keep, td, box, density, rgbs, sem if use_sem else None, latents, *tables,
+                                                      *flats)
+        return dens, rgbs, sem_m if use_sem else sem, mask
+
     def forward(self, batch: Dict[str, torch.Tensor], train_frac: float = 1.0, rand: Optional[torch.Generator] = None, randomized: bool = False,
                 sample_n: int = 7, sample_m: int = 3, curr_track=None, color_rays: Optional[int] = None, object_ray_grads: bool = False):
         """-> (renderings, ray_history), one entry per level, like `Model.forward`.  randomized (or a generator in `rand`): per-ray
@@ -883,6 +1088,10 @@ class TrainableModel(torch.nn.Module):
             raise NotImplementedError("ray tensors that require a gradient (pose refinement) with instance_obj=True: the box-frame path "
                                       "of the dynamic-object branch leads back to origins / directions / viewdirs only on request, "
                                       "pass object_ray_grads=True")
+        fused_obj = self.instance_obj and self.fused_objects
+        if fused_obj and ray_grads:
+            raise NotImplementedError("fused_objects=True with ray tensors that require a gradient (pose refinement, object_ray_grads=True): "
+                                      "the fused object operator has no box-frame gradient, use fused_objects=False")
         if self.instance_obj:
             if "timestamp" not in batch:
                 raise RuntimeError("batch['timestamp'] is missing (ZI/models.py:315)")
@@ -892,6 +1101,11 @@ class TrainableModel(torch.nn.Module):
             # track refinement (train.py:244-268): a track that requires a gradient gets one from the last level's object samples
             # pose refinement (train.py:199-243) on request: ray tensors that require one get theirs through the same samples
             refine = (tracks, ts) if (tracks.requires_grad and torch.is_grad_enabled()) or ray_grads else None
+            if fused_obj and refine is not None:
+                raise NotImplementedError("fused_objects=True with tracks that require a gradient (track refinement): the fused object "
+                                          "operator has no box-frame gradient, use fused_objects=False")
+            if fused_obj:
+                fused_state = self._fused_objects_begin(batch, n, dev)
         for li, ((S, dilation, anneal), level) in enumerate(zip(mc.level_schedule(train_frac), self.levels())):
             last = li == n_levels - 1
             sdist, tdist = torch.empty(n, S + 1, device=dev), torch.empty(n, S + 1, device=dev)
@@ -903,7 +1117,10 @@ class TrainableModel(torch.nn.Module):
             rgbs = o["rgb"] if last else torch.zeros(n, S, 3, device=dev)   # a PropMLP renders black (models.py:1119-1122)
             obj_mask = None
             if box is not None:
-                dens_m, rgbs, sem_m, obj_mask = self._object_merge(o, rgbs, batch, tdist, box, last, refine if last else None)
+                if fused_obj:
+                    dens_m, rgbs, sem_m, obj_mask = self._object_merge_fused(o, rgbs, tdist, box, last, fused_state)
+                else:
+                    dens_m, rgbs, sem_m, obj_mask = self._object_merge(o, rgbs, batch, tdist, box, last, refine if last else None)
                 o = dict(o, density=dens_m)
                 if sem_m is not None:
                     o["semantic"] = sem_m
@@ -1119,7 +1336,8 @@ def training_step(model: TrainableModel, optimizer: torch.optim.Optimizer, batch
     """One optimiser step as train.py:272-459 takes it: forward with random jitter, the loss dictionary (`losses.total_loss` +
     hash decay), backward through the HIP backward kernels, optional total-variation gradient on the tables (grid.py:176-198),
     gradient clipping incl. the unconditional nan_to_num_ (train_utils.clip_gradients), step.  Returns the loss terms as floats, or
-    with `as_tensors` as detached device scalars: reading them is the only host synchronisation of a step (without object tracks), so a
+    with `as_tensors` as detached device scalars: reading them is the only host synchronisation of a step (without object tracks, or
+    with them on a `TrainableModel(fused_objects=True)`; the torch object merge reads its owner lists back on every level), so a
     loop that logs every n-th step keeps the next step's launches ahead of the GPU in between.
     color_rays: None, or the number n of leading rays with colour supervision (`TrainableModel.forward`): the caller promises
     `batch['mask_rgb']` = 0 on the rays [n, N), as train.py:316-320 sets it for the LiDAR rays at the end of a batch
