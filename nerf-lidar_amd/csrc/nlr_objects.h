@@ -1,10 +1,7 @@
 // Internal interface of the dynamic-object branch (nlr_objects.hip) used by the render loop (nlr_api.hip).
 #pragma once
 #include "nlr_common.h"
-
-#define NLR_OBJ_MAX_CLASSES 8
-#define NLR_OBJ_MAX_DEPTH 4
-#define NLR_OBJ_MAX_DEG 4
+#include "nlr_obj_layers.h"
 
 // workspace carving of both files: every slab starts on a 256-byte boundary
 static inline size_t al(size_t b) { return (b + 255) & ~(size_t)255; }

@@ -12,6 +12,14 @@
 // track loop in registers: the reference materialises [N, S, N_obj, 3] tensors for this), the networks' inputs
 // (nlr_objmlp_kernel) and the forward half of the adjoint (nlr_obj_frame_bwd_kernel).  Built with -ffp-contract=off: the
 // multiply / add chains below are the reference's torch expressions, operation by operation.
+//   The network of a class is stated as data ONCE, in nlr_obj_layers.h (nlr_obj_layers: the Linears, their input blocks, their places
+// in the LDS image, in the flat training buffer and in acts / gacts, the envelope and its messages): the ObjNet offsets here, the
+// training plan's layouts and the weight-gradient records of nlr_objects_train.h are made of that table.  An object set is made in two
+// steps, obj_layout ("lay out and allocate": the training plan stops there) and obj_fill_images (from NlrLinears).  The launch
+// preparation - the carved workspace (obj_carve), owner -> scan -> scatter (obj_make_lists), ObjApply (obj_apply_args), the grid
+// (obj_net_grid) - is written once for nlr_objects_apply and the two training entry points.  The walk through the layers is written
+// twice, in nlr_objmlp_kernel below and in nlr_objtrain_kernel: they share the segment helpers and the accumulator policy
+// (obj_begin / obj_end<BIAS_LAST>, the one numerical difference between them).
 #include "nlr_kernels.h"
 #include "nlr_grid_level.h"
 #include "nlr_objects.h"
@@ -640,6 +648,7 @@ struct ObjNet {
     uint32_t n_grid, lat_size, lat_shape, lat_tex, lat_tex_off, BW, W, D, skip, deg, DE;
     float density_bias, premul, rgb_bias, rgb_pad;
     int32_t class_type;
+    __host__ __device__ ObjCols cols() const { return nlr_obj_cols(n_grid, BW, DE, D, W); }  // columns of acts / gacts (training form)
 };
 
 struct ObjApply {
@@ -651,14 +660,8 @@ struct ObjApply {
     float *density, *rgb, *sem;
 };
 
-#define NLR_OBJ_WAVES 3
-#define NLR_OBJ_WMAX 20480  // floats of LDS for the weight image (80 KiB)
+#define NLR_OBJ_WAVES 3  // (NLR_OBJ_WMAX, the floats of LDS for the weight image: nlr_obj_layers.h)
 
-template <int OUT>
-__device__ __forceinline__ void obj_bias(float (&acc)[OUT], const float *b) {
-#pragma unroll
-    for (int o = 0; o < OUT; ++o) acc[o] = b[o];
-}
 template <int OUT>
 __device__ __forceinline__ void obj_fma_row(float (&acc)[OUT], const float *wrow, float x) {
 #pragma unroll
@@ -689,6 +692,25 @@ __device__ __forceinline__ void obj_seg_reg(float (&acc)[OUT], const float *w, u
 #pragma unroll
     for (int k = 0; k < NR; ++k)
         if ((uint32_t)k < n) obj_fma_row<OUT>(acc, wr + (size_t)k * OUT, x[k]);
+}
+
+// The accumulator chain of a Linear - the ONE numerical difference between the two kernels.  Every output is one fused-multiply-add
+// chain over the inputs in their order.  BIAS_LAST = false (rendering): the chain starts at the bias.  BIAS_LAST = true (training):
+// it starts at zero and the bias is added after the last input - the reference's own order of operations.  At these widths
+// (K = 64 .. 175) torch's Linear on the CPU (the f32 GEMM the reference runs) was observed to sum that way (DESIGN, round-4
+// f-1 x f-3): restated so an output has the reference's bits, where the chain started at the bias is a few ulp of the hidden units
+// away.  Under the x1500 density gain of a trained-like field those ulp are 2e-5 of a density, which the resampler of the next level
+// turns into moved sample positions: training is held to the reference's step, so its forward sums as the reference does.
+template <bool BIAS_LAST, int OUT>
+__device__ __forceinline__ void obj_begin(float (&acc)[OUT], const float *b) {
+#pragma unroll
+    for (int o = 0; o < OUT; ++o) acc[o] = BIAS_LAST ? 0.0f : b[o];
+}
+template <bool BIAS_LAST, int OUT>
+__device__ __forceinline__ void obj_end(float (&acc)[OUT], const float *b) {
+    if (!BIAS_LAST) return;
+#pragma unroll
+    for (int o = 0; o < OUT; ++o) acc[o] = acc[o] + b[o];
 }
 
 template <typename T, int C, int LMAX>
@@ -753,7 +775,7 @@ __global__ void __launch_bounds__(64 * NLR_OBJ_WAVES) nlr_objmlp_kernel(const Ob
         // ---- density_layer: [grid | shape latent] -> 64 -> ReLU -> bottleneck (models.py:887-889,996-1003)
         {
             float h[64];
-            obj_bias<64>(h, wl + net.o_bd0);
+            obj_begin<false, 64>(h, wl + net.o_bd0);
             obj_seg_reg<64, LMAX * C>(h, wl + net.o_d0, 0, net.n_grid, gf);
             obj_seg_mem<64>(h, wl + net.o_d0, net.n_grid, net.lat_shape, lat);
 #pragma unroll
@@ -761,7 +783,7 @@ __global__ void __launch_bounds__(64 * NLR_OBJ_WAVES) nlr_objmlp_kernel(const Ob
         }
         float x[64];
         if (want_rgb) {
-            obj_bias<64>(x, wl + net.o_bd2);
+            obj_begin<false, 64>(x, wl + net.o_bd2);
             obj_seg_lds<64>(x, wl + net.o_d2, 0, 64, sa, lane);
         } else {  // proposal levels replace the density only: output 0 of density_layer.2
             float r = wl[net.o_bd2];
@@ -783,7 +805,7 @@ __global__ void __launch_bounds__(64 * NLR_OBJ_WAVES) nlr_objmlp_kernel(const Ob
         for (uint32_t i = 0; i < net.D; ++i) {
             float h[32];
             const float *wv = wl + net.o_v[i];
-            obj_bias<32>(h, wl + net.o_bv[i]);
+            obj_begin<false, 32>(h, wl + net.o_bv[i]);
             uint32_t row = 0;
             if (i > 0) {
                 obj_seg_lds<32>(h, wv, 0, net.W, sv, lane);
@@ -801,7 +823,7 @@ __global__ void __launch_bounds__(64 * NLR_OBJ_WAVES) nlr_objmlp_kernel(const Ob
         }
         float c4[4];
         const float *wr = wl + net.o_rgb;
-        obj_bias<4>(c4, wl + net.o_brgb);
+        obj_begin<false, 4>(c4, wl + net.o_brgb);
         obj_seg_lds<4>(c4, wr, 0, net.W, sv, lane);
         if (net.D - 1 == net.skip) {
             obj_seg_lds<4>(c4, wr, net.W, net.BW, sa, lane);
@@ -822,6 +844,7 @@ __global__ void __launch_bounds__(64 * NLR_OBJ_WAVES) nlr_objmlp_kernel(const Ob
 
 // ---- host side -----------------------------------------------------------------------------------------------------------
 struct NlrObjects {
+    std::vector<ObjLayers> layers;  // the layer table of every class: what cls' offsets are made of
     std::vector<ObjNet> cls;
     ObjNet *nets_dev = nullptr;  // the same, as the kernel reads them
     std::vector<void *> allocs;
@@ -834,145 +857,185 @@ struct NlrObjects {
     }
 };
 
+// a device buffer of the object set: a copy of `host`, or zeros where host is NULL
 static int obj_upload(NlrObjects *o, const void *host, size_t bytes, void **out, hipStream_t st) {
     void *p = nullptr;
     NLR_HIP(hipMalloc(&p, bytes ? bytes : 16));
     o->allocs.push_back(p);
-    if (bytes) {
-        NLR_HIP(hipMemcpyAsync(p, host, bytes, hipMemcpyHostToDevice, st));
-        NLR_HIP(hipStreamSynchronize(st));  // the sources are temporaries
-    }
+    if (!host) NLR_HIP(hipMemsetAsync(p, 0, bytes ? bytes : 16, st));
+    else if (bytes) NLR_HIP(hipMemcpyAsync(p, host, bytes, hipMemcpyHostToDevice, st));
+    NLR_HIP(hipStreamSynchronize(st));  // the sources are temporaries
     *out = p;
     return NLR_OK;
 }
-// nn.Linear weight [out, in] -> [in][OUTP] (zero padded) appended to the class's LDS image; returns its offset
-static int obj_pack_linear(std::vector<float> &img, const NlrLinear &l, uint32_t out_f, uint32_t in_f, uint32_t outp, const char *name,
-                           uint32_t *w_off) {
-    NLR_CHECK_ARG(l.weight && l.bias, "objects: %s weight/bias is NULL", name);
-    NLR_CHECK_ARG(l.out_features == out_f && l.in_features == in_f, "objects: %s expected [%u,%u], got [%u,%u]", name, out_f, in_f,
-                  l.out_features, l.in_features);
-    *w_off = (uint32_t)img.size();
-    img.resize(img.size() + (size_t)in_f * outp, 0.0f);
-    float *w = img.data() + *w_off;
-    for (uint32_t r = 0; r < out_f; ++r)
-        for (uint32_t c = 0; c < in_f; ++c) w[(size_t)c * outp + r] = l.weight[(size_t)r * in_f + c];
-    return NLR_OK;
-}
-static void obj_pack_bias(std::vector<float> &img, const NlrLinear &l, uint32_t outp, uint32_t *b_off) {
-    *b_off = (uint32_t)img.size();
-    img.resize(img.size() + outp, 0.0f);
-    for (uint32_t r = 0; r < l.out_features; ++r) img[*b_off + r] = l.bias[r];
-}
 
-extern "C" int nlr_objects_create(const NlrObjectsDesc *d, NlrObjects **out, void *stream) {
-    NLR_CHECK_ARG(d && out, "objects_create: NULL argument");
-    NLR_CHECK_ARG(d->n_classes >= 1 && d->n_classes <= NLR_OBJ_MAX_CLASSES && d->classes, "objects_create: n_classes = %u outside [1,%d]",
-                  d->n_classes, NLR_OBJ_MAX_CLASSES);
-    NLR_CHECK_ARG(d->n_tracks >= 1 && d->track_class, "objects_create: no tracks");
-    hipStream_t st = (hipStream_t)stream;
-    std::unique_ptr<NlrObjects> own(new NlrObjects());
+// Step 1 of making an object set, "lay out and allocate": the layer table of every class (nlr_obj_layers: envelope and offsets),
+// its grid parameters and ObjNet, the track classes, a zeroed latent table and zeroed weight images on the device.  The training plan
+// stops here (its images are filled from the flat buffers by nlr_obj_train_pack, its latent table from the caller's tensor).
+static int obj_layout(const NlrObjectsDesc *d, const char *who, std::unique_ptr<NlrObjects> &own, hipStream_t st) {
+    NLR_CHECK_ARG(d->n_classes >= 1 && d->n_classes <= NLR_OBJ_MAX_CLASSES && d->classes, "%s: n_classes = %u outside [1,%d]", who, d->n_classes,
+                  NLR_OBJ_MAX_CLASSES);
+    NLR_CHECK_ARG(d->n_tracks >= 1 && d->track_class, "%s: no tracks", who);
+    own.reset(new NlrObjects());
     NlrObjects *o = own.get();
     int rc = NLR_OK;
-    auto fail = [&](int code) { return code; };
     NLR_HIP(hipGetDevice(&o->device));
     int cus = 0;
     NLR_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, o->device));
     o->cus = (uint32_t)cus;
     o->n_tracks = d->n_tracks;
-    uint32_t lat_size = d->classes[0].latent_size;
+    const uint32_t lat_size = d->classes[0].latent_size;
     for (uint32_t t = 0; t < d->n_tracks; ++t)
-        if (d->track_class[t] < 0 || (uint32_t)d->track_class[t] >= d->n_classes) {
-            nlr_set_error("objects_create: track_class[%u] = %d outside [0,%u)", t, d->track_class[t], d->n_classes);
-            return fail(NLR_ERR_INVALID);
-        }
-    if ((rc = obj_upload(o, d->track_class, (size_t)d->n_tracks * 4, (void **)&o->track_class, st))) return fail(rc);
-    const float *lat_dev = nullptr;
-    if (lat_size) {
-        if (!d->latents) {
-            nlr_set_error("objects_create: latent_size = %u but latents is NULL", lat_size);
-            return fail(NLR_ERR_INVALID);
-        }
-        if ((rc = obj_upload(o, d->latents, (size_t)d->n_tracks * lat_size * 4, (void **)&lat_dev, st))) return fail(rc);
-    }
+        NLR_CHECK_ARG(d->track_class[t] >= 0 && (uint32_t)d->track_class[t] < d->n_classes, "objects_create: track_class[%u] = %d outside [0,%u)", t,
+                      d->track_class[t], d->n_classes);
+    if ((rc = obj_upload(o, d->track_class, (size_t)d->n_tracks * 4, (void **)&o->track_class, st))) return rc;
+    float *lat_dev = nullptr;
+    if (lat_size && (rc = obj_upload(o, nullptr, (size_t)d->n_tracks * lat_size * 4, (void **)&lat_dev, st))) return rc;
     o->cls.resize(d->n_classes);
+    o->layers.resize(d->n_classes);
     for (uint32_t c = 0; c < d->n_classes; ++c) {
         const NlrObjClassDesc &cd = d->classes[c];
         const NlrMlpDesc &md = cd.mlp;
         ObjNet &n = o->cls[c];
+        ObjLayers &t = o->layers[c];
         memset(&n, 0, sizeof(n));
-#define OBJ_REQ(cond, ...)                   \
-    if (!(cond)) {                           \
-        nlr_set_error(__VA_ARGS__);          \
-        return fail(NLR_ERR_UNSUPPORTED);    \
-    }
-        OBJ_REQ(cd.latent_size == lat_size, "objects_create: classes disagree on latent_size (%u vs %u)", cd.latent_size, lat_size);
-        OBJ_REQ(!md.disable_rgb, "objects_create: class %u: an ObjMLP has an rgb branch", c);
-        OBJ_REQ(md.bottleneck_width >= 1 && md.bottleneck_width <= 64, "objects_create: bottleneck_width %u outside [1,64]", md.bottleneck_width);
-        OBJ_REQ(md.net_width_viewdirs >= 1 && md.net_width_viewdirs <= 32, "objects_create: net_width_viewdirs %u outside [1,32]", md.net_width_viewdirs);
-        OBJ_REQ(md.net_depth_viewdirs >= 1 && md.net_depth_viewdirs <= NLR_OBJ_MAX_DEPTH, "objects_create: net_depth_viewdirs %u outside [1,%d]",
-                md.net_depth_viewdirs, NLR_OBJ_MAX_DEPTH);
-        OBJ_REQ(md.deg_view <= NLR_OBJ_MAX_DEG, "objects_create: deg_view %u > %d", md.deg_view, NLR_OBJ_MAX_DEG);
-        OBJ_REQ(md.grid.table_dtype == 0 || md.grid.table_dtype == 1, "objects_create: table dtype");
-        OBJ_REQ((md.grid.level_dim == 2 && md.grid.num_levels <= 8) || (md.grid.level_dim == 4 && md.grid.num_levels <= 4) ||
-                    (md.grid.level_dim == 1 && md.grid.num_levels <= 16),
-                "objects_create: grid L=%u C=%u not supported by the object kernel", md.grid.num_levels, md.grid.level_dim);
-        OBJ_REQ(!md.re_weights, "objects_create: ObjMLP runs without erf re-weighting (models.py:137)");
+        char msg[256];
+        if (cd.latent_size != lat_size)
+            NLR_FAIL(NLR_ERR_UNSUPPORTED, "objects_create: classes disagree on latent_size (%u vs %u)", cd.latent_size, lat_size);
+        if (!nlr_obj_layers(cd, who, c, t, msg, sizeof(msg))) NLR_FAIL(NLR_ERR_UNSUPPORTED, "%s", msg);
+        if (!(md.grid.table_dtype == 0 || md.grid.table_dtype == 1)) NLR_FAIL(NLR_ERR_UNSUPPORTED, "objects_create: table dtype");
+        if (!((md.grid.level_dim == 2 && md.grid.num_levels <= 8) || (md.grid.level_dim == 4 && md.grid.num_levels <= 4) ||
+              (md.grid.level_dim == 1 && md.grid.num_levels <= 16)))
+            NLR_FAIL(NLR_ERR_UNSUPPORTED, "objects_create: grid L=%u C=%u not supported by the object kernel", md.grid.num_levels, md.grid.level_dim);
+        if (md.grid.level_dim != d->classes[0].mlp.grid.level_dim || md.grid.table_dtype != d->classes[0].mlp.grid.table_dtype)
+            NLR_FAIL(NLR_ERR_UNSUPPORTED,
+                     "objects_create: the classes' grids must share level_dim and table dtype (one kernel instance serves them all)");
         if ((rc = nlr_fill_grid_params(&n.gp, md.grid.table, md.grid.table_dtype, md.grid.offsets, md.grid.num_levels, md.grid.level_dim,
                                        md.grid.log2_per_level_scale, md.grid.base_resolution, md.grid.gridtype, (int)md.grid.align_corners,
                                        md.grid.interp)))
-            return fail(rc);
-        n.n_grid = md.grid.num_levels * md.grid.level_dim;
-        n.lat_size = lat_size;
-        n.lat_shape = lat_size ? (cd.split_latent ? lat_size / 2 : lat_size) : 0;
-        n.lat_tex = (lat_size && cd.split_latent) ? lat_size - lat_size / 2 : 0;
-        n.lat_tex_off = lat_size / 2;
-        n.BW = md.bottleneck_width;
-        n.W = md.net_width_viewdirs;
-        n.D = md.net_depth_viewdirs;
-        n.skip = md.skip_layer_dir;
-        n.deg = md.deg_view;
-        n.DE = 3 + 6 * md.deg_view;
-        n.density_bias = md.density_bias;
-        n.premul = md.rgb_premultiplier;
-        n.rgb_bias = md.rgb_bias;
-        n.rgb_pad = md.rgb_padding;
+            return rc;
+        n.n_grid = t.n_grid, n.lat_size = lat_size, n.lat_shape = t.lat_shape, n.lat_tex = t.lat_tex, n.lat_tex_off = t.lat_tex_off;
+        n.BW = t.BW, n.W = t.W, n.D = t.D, n.skip = t.skip, n.deg = t.deg, n.DE = t.DE;
+        n.density_bias = md.density_bias, n.premul = md.rgb_premultiplier, n.rgb_bias = md.rgb_bias, n.rgb_pad = md.rgb_padding;
         n.class_type = cd.class_type;
         n.latents = lat_dev;
-        const uint32_t f0 = n.n_grid + n.lat_shape, in_rgb = n.BW + n.DE + n.lat_tex;
-        std::vector<float> img;
-        if ((rc = obj_pack_linear(img, md.density0, 64, f0, 64, "density_layer.0", &n.o_d0))) return fail(rc);
-        if ((rc = obj_pack_linear(img, md.density2, n.BW, 64, 64, "density_layer.2", &n.o_d2))) return fail(rc);
-        uint32_t last = in_rgb;
-        for (uint32_t i = 0; i < n.D; ++i) {
-            if ((rc = obj_pack_linear(img, md.view[i], n.W, last, 32, "lin_second_stage", &n.o_v[i]))) return fail(rc);
-            last = n.W + (i == n.skip ? in_rgb : 0);
-        }
-        if ((rc = obj_pack_linear(img, md.rgb_layer, 3, last, 4, "rgb_layer", &n.o_rgb))) return fail(rc);
-        obj_pack_bias(img, md.density0, 64, &n.o_bd0);
-        obj_pack_bias(img, md.density2, 64, &n.o_bd2);
-        for (uint32_t i = 0; i < n.D; ++i) obj_pack_bias(img, md.view[i], 32, &n.o_bv[i]);
-        obj_pack_bias(img, md.rgb_layer, 4, &n.o_brgb);
-        OBJ_REQ(img.size() <= NLR_OBJ_WMAX, "objects_create: class %u needs %zu floats of LDS for its weights, the kernel holds %d", c, img.size(),
-                NLR_OBJ_WMAX);
-        n.wfloats = (uint32_t)img.size();
-        if ((rc = obj_upload(o, img.data(), img.size() * 4, (void **)&n.wpack, st))) return fail(rc);
-        OBJ_REQ(md.grid.level_dim == d->classes[0].mlp.grid.level_dim && md.grid.table_dtype == d->classes[0].mlp.grid.table_dtype,
-                "objects_create: the classes' grids must share level_dim and table dtype (one kernel instance serves them all)");
-#undef OBJ_REQ
+        // the image's offsets: Linear i of the table is density_layer.0, density_layer.2, lin_second_stage_0 .. D-1, rgb_layer
+        const ObjLinear *L = t.lin;
+        n.o_d0 = L[0].img_w, n.o_bd0 = L[0].img_b, n.o_d2 = L[1].img_w, n.o_bd2 = L[1].img_b;
+        for (uint32_t i = 0; i < t.D; ++i) n.o_v[i] = L[2 + i].img_w, n.o_bv[i] = L[2 + i].img_b;
+        n.o_rgb = L[2 + t.D].img_w, n.o_brgb = L[2 + t.D].img_b;
+        n.wfloats = t.img_floats;
+        if ((rc = obj_upload(o, nullptr, (size_t)t.img_floats * 4, (void **)&n.wpack, st))) return rc;
     }
-    if ((rc = obj_upload(o, o->cls.data(), o->cls.size() * sizeof(ObjNet), (void **)&o->nets_dev, st))) return fail(rc);
+    return obj_upload(o, o->cls.data(), o->cls.size() * sizeof(ObjNet), (void **)&o->nets_dev, st);
+}
+
+// Step 2, "fill the images from NlrLinears": nn.Linear weight [out, in] -> [in][outp] at the table's place (the padding stays zero)
+static int obj_fill_images(NlrObjects *o, const NlrObjectsDesc *d, hipStream_t st) {
+    for (uint32_t c = 0; c < d->n_classes; ++c) {
+        const NlrMlpDesc &md = d->classes[c].mlp;
+        const ObjLayers &t = o->layers[c];
+        std::vector<float> img(t.img_floats, 0.0f);
+        for (uint32_t i = 0; i < t.n_lin; ++i) {
+            const ObjLinear &L = t.lin[i];
+            const NlrLinear &l = i == 0 ? md.density0 : i == 1 ? md.density2 : i == t.n_lin - 1 ? md.rgb_layer : md.view[i - 2];
+            NLR_CHECK_ARG(l.weight && l.bias, "objects: %s weight/bias is NULL", L.name);
+            NLR_CHECK_ARG(l.out_features == L.n_out && l.in_features == L.n_in, "objects: %s expected [%u,%u], got [%u,%u]", L.name, L.n_out,
+                          L.n_in, l.out_features, l.in_features);
+            for (uint32_t r = 0; r < L.n_out; ++r) {
+                for (uint32_t k = 0; k < L.n_in; ++k) img[L.img_w + (size_t)k * L.outp + r] = l.weight[(size_t)r * L.n_in + k];
+                img[L.img_b + r] = l.bias[r];
+            }
+        }
+        NLR_HIP(hipMemcpyAsync(const_cast<float *>(o->cls[c].wpack), img.data(), img.size() * 4, hipMemcpyHostToDevice, st));
+        NLR_HIP(hipStreamSynchronize(st));  // the source is a temporary
+    }
+    return NLR_OK;
+}
+
+extern "C" int nlr_objects_create(const NlrObjectsDesc *d, NlrObjects **out, void *stream) {
+    NLR_CHECK_ARG(d && out, "objects_create: NULL argument");
+    hipStream_t st = (hipStream_t)stream;
+    std::unique_ptr<NlrObjects> own;
+    int rc = obj_layout(d, "objects_create", own, st);
+    if (rc) return rc;
+    const uint32_t lat_size = d->classes[0].latent_size;
+    if (lat_size) {
+        NLR_CHECK_ARG(d->latents, "objects_create: latent_size = %u but latents is NULL", lat_size);
+        NLR_HIP(hipMemcpyAsync(const_cast<float *>(own->cls[0].latents), d->latents, (size_t)d->n_tracks * lat_size * 4, hipMemcpyHostToDevice, st));
+        NLR_HIP(hipStreamSynchronize(st));
+    }
+    if ((rc = obj_fill_images(own.get(), d, st))) return rc;
     *out = own.release();
     return NLR_OK;
 }
 
 extern "C" void nlr_objects_destroy(NlrObjects *o) { delete o; }
 
+// ---- launch preparation, shared by nlr_objects_apply and the training form ------------------------------------------------------
+// The workspace: [counts | owner map | per-class lists | per-wave counts / offsets] and, for the training backward,
+// [acts aw x M | gacts gw x M | slabs slices x classes x stride | totals classes x stride] f32.  Every piece starts on a 256-byte
+// boundary; `bytes` is what the pieces take with the slack for aligning the caller's pointer (workspace NULL: the size alone).
+struct ObjWorkspace {
+    uint32_t *counts, *lists, *wave_counts;
+    int32_t *winner;
+    float *acts, *gacts, *slabs, *totals;
+    size_t bytes;
+};
+static ObjWorkspace obj_carve(void *workspace, size_t nc, uint32_t N, uint32_t S, uint32_t aw, uint32_t gw, size_t slab_floats, size_t total_floats) {
+    const size_t M = (size_t)N * S, nw = ((M + 255) / 256) * 4;
+    const uintptr_t p0 = ((uintptr_t)workspace + 255) & ~(uintptr_t)255;
+    uintptr_t p = p0;
+    auto take = [&p](size_t b) {
+        const uintptr_t at = p;
+        p += al(b);
+        return at;
+    };
+    ObjWorkspace w;
+    w.counts = (uint32_t *)take(256);
+    w.winner = (int32_t *)take(M * 4);
+    w.lists = (uint32_t *)take(nc * M * 4);
+    w.wave_counts = (uint32_t *)take(nc * nw * 4);
+    w.acts = (float *)take(M * aw * 4);  // (the four pieces of the backward are empty for a forward: all sizes 0)
+    w.gacts = (float *)take(M * gw * 4);
+    w.slabs = (float *)take(slab_floats * 4);
+    w.totals = (float *)take(total_floats * 4);
+    w.bytes = 256 + (size_t)(p - p0);
+    return w;
+}
+
 extern "C" size_t nlr_objects_workspace_bytes(const NlrObjects *o, uint32_t N, uint32_t S) {
-    if (!o) return 0;
+    return o ? obj_carve(nullptr, o->cls.size(), N, S, 0, 0, 0, 0).bytes : 0;
+}
+
+// owner map + per-class lists of the owned samples: owner -> scan -> scatter; the map is copied to winner_out when given
+static int obj_make_lists(const NlrObjects *o, const ObjWorkspace &w, const NlrRays *rays, const float *tdist, const float *box_params, uint32_t N,
+                          uint32_t S, uint32_t n_obj, int32_t *winner_out, hipStream_t st) {
     const size_t M = (size_t)N * S;
-    const size_t nw = ((M + 255) / 256) * 4;
-    return 256 + 256 /* counts */ + al(M * 4) /* winner */ + al(o->cls.size() * M * 4) /* lists */ +
-           al(o->cls.size() * nw * 4) /* per-wave counts / offsets */;
+    const uint32_t nc = (uint32_t)o->cls.size(), nblk = (uint32_t)((M + 255) / 256), nw = nblk * 4;
+    hipLaunchKernelGGL(nlr_box_owner_kernel, dim3(nblk), dim3(256), 0, st, tdist, rays->origins, rays->directions, box_params, N, S, n_obj,
+                       o->track_class, nc, w.winner, w.wave_counts);
+    NLR_LAUNCH_CHECK("nlr_box_owner_kernel");
+    hipLaunchKernelGGL(nlr_obj_scan_kernel, dim3(nc), dim3(1024), 0, st, w.wave_counts, nw, w.counts);
+    NLR_LAUNCH_CHECK("nlr_obj_scan_kernel");
+    hipLaunchKernelGGL(nlr_obj_scatter_kernel, dim3(nblk), dim3(256), 0, st, w.winner, o->track_class, (uint32_t)M, nc, w.wave_counts, w.lists,
+                       (uint32_t)M);
+    NLR_LAUNCH_CHECK("nlr_obj_scatter_kernel");
+    if (winner_out) NLR_HIP(hipMemcpyAsync(winner_out, w.winner, M * 4, hipMemcpyDeviceToDevice, st));
+    return NLR_OK;
+}
+
+static ObjApply obj_apply_args(const ObjWorkspace &w, const NlrRays *rays, const float *tdist, const float *box_params, uint32_t N, uint32_t S,
+                               uint32_t n_obj, float *density, float *rgb, float *semantic, uint32_t K) {
+    return ObjApply{w.lists, w.counts, /*cap*/ N * S, w.winner, tdist, rays->origins, rays->directions, rays->viewdirs, box_params, N, S, n_obj,
+                    /*K*/ semantic ? K : 0, density, rgb, semantic};
+}
+
+// the networks' grid: one launch, grid.y = class; persistent workgroups (at most one per CU) that read their class's count on the device
+static dim3 obj_net_grid(const NlrObjects *o, uint32_t N, uint32_t S) {
+    const size_t M = (size_t)N * S;
+    const uint32_t per = 64 * NLR_OBJ_WAVES, nb = (uint32_t)((M + per - 1) / per);
+    return dim3(o->cus < nb ? o->cus : nb, (uint32_t)o->cls.size());
 }
 
 int nlr_objects_apply_impl(const NlrObjects *o, const NlrRays *rays, const float *tdist, const float *box_params, uint32_t N, uint32_t S,
@@ -986,53 +1049,19 @@ int nlr_objects_apply_impl(const NlrObjects *o, const NlrRays *rays, const float
     const size_t need = nlr_objects_workspace_bytes(o, N, S);
     if (!workspace || workspace_bytes < need)
         NLR_FAIL(NLR_ERR_WORKSPACE, "objects_apply: workspace %zu B < nlr_objects_workspace_bytes() = %zu B", workspace_bytes, need);
-    const size_t M = (size_t)N * S;
-    NLR_CHECK_ARG(M < (1ull << 32), "objects_apply: N * S = %zu does not fit the 32-bit sample index", M);
-    char *p = (char *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    uint32_t *counts = (uint32_t *)p;
-    p += 256;
-    int32_t *winner = (int32_t *)p;
-    p += al(M * 4);
-    uint32_t *lists = (uint32_t *)p;
-    const uint32_t nc = (uint32_t)o->cls.size();
-    p += al((size_t)nc * M * 4);
-    uint32_t *wave_counts = (uint32_t *)p;
-    const uint32_t nblk = (uint32_t)((M + 255) / 256), nw = nblk * 4;
-    hipLaunchKernelGGL(nlr_box_owner_kernel, dim3(nblk), dim3(256), 0, st, tdist, rays->origins, rays->directions, box_params, N, S, n_obj,
-                       o->track_class, nc, winner, wave_counts);
-    NLR_LAUNCH_CHECK("nlr_box_owner_kernel");
-    hipLaunchKernelGGL(nlr_obj_scan_kernel, dim3(nc), dim3(1024), 0, st, wave_counts, nw, counts);
-    NLR_LAUNCH_CHECK("nlr_obj_scan_kernel");
-    hipLaunchKernelGGL(nlr_obj_scatter_kernel, dim3(nblk), dim3(256), 0, st, winner, o->track_class, (uint32_t)M, nc, wave_counts, lists,
-                       (uint32_t)M);
-    NLR_LAUNCH_CHECK("nlr_obj_scatter_kernel");
-    if (winner_out) NLR_HIP(hipMemcpyAsync(winner_out, winner, M * 4, hipMemcpyDeviceToDevice, st));
-    // the networks: one launch, grid.y = class; persistent workgroups that read their class's count on the device
-    const uint32_t per = 64 * NLR_OBJ_WAVES, nb = (uint32_t)((M + per - 1) / per);
-    const uint32_t grid = o->cus < nb ? o->cus : nb;
-    ObjApply a;
-    a.lists = lists;
-    a.counts = counts;
-    a.cap = (uint32_t)M;
-    a.winner = winner;
-    a.tdist = tdist;
-    a.origins = rays->origins;
-    a.dirs = rays->directions;
-    a.viewdirs = rays->viewdirs;
-    a.box = box_params;
-    a.N = N;
-    a.S = S;
-    a.n_obj = n_obj;
-    a.K = semantic ? K : 0;
-    a.density = density;
-    a.rgb = rgb;
-    a.sem = semantic;
+    NLR_CHECK_ARG((size_t)N * S < (1ull << 32), "objects_apply: N * S = %zu does not fit the 32-bit sample index", (size_t)N * S);
+    const ObjWorkspace w = obj_carve(workspace, o->cls.size(), N, S, 0, 0, 0, 0);
+    int rc = obj_make_lists(o, w, rays, tdist, box_params, N, S, n_obj, winner_out, st);
+    if (rc) return rc;
+    const ObjApply a = obj_apply_args(w, rays, tdist, box_params, N, S, n_obj, density, rgb, semantic, K);
     const GridParams &gp0 = o->cls[0].gp;
-#define OBJ_LAUNCH(T, C, LM) hipLaunchKernelGGL((nlr_objmlp_kernel<T, C, LM>), dim3(grid, nc), dim3(64 * NLR_OBJ_WAVES), 0, st, o->nets_dev, a)
-    const bool f32t = gp0.table_dtype == 0;
-    if (gp0.C == 2) { if (f32t) OBJ_LAUNCH(float, 2, 8); else OBJ_LAUNCH(__half, 2, 8); }
-    else if (gp0.C == 4) { if (f32t) OBJ_LAUNCH(float, 4, 4); else OBJ_LAUNCH(__half, 4, 4); }
-    else { if (f32t) OBJ_LAUNCH(float, 1, 16); else OBJ_LAUNCH(__half, 1, 16); }
+#define OBJ_LAUNCH(C, LM)                                                                                                                 \
+    if (gp0.table_dtype == 0) hipLaunchKernelGGL((nlr_objmlp_kernel<float, C, LM>), obj_net_grid(o, N, S), dim3(64 * NLR_OBJ_WAVES), 0, st, \
+                                                 o->nets_dev, a);                                                                         \
+    else hipLaunchKernelGGL((nlr_objmlp_kernel<__half, C, LM>), obj_net_grid(o, N, S), dim3(64 * NLR_OBJ_WAVES), 0, st, o->nets_dev, a)
+    if (gp0.C == 2) { OBJ_LAUNCH(2, 8); }
+    else if (gp0.C == 4) { OBJ_LAUNCH(4, 4); }
+    else { OBJ_LAUNCH(1, 16); }
 #undef OBJ_LAUNCH
     NLR_LAUNCH_CHECK("nlr_objmlp_kernel");
     return NLR_OK;

@@ -1,10 +1,16 @@
 // Training form of the dynamic-object branch (header section 7e).  This file is the tail of nlr_objects.hip - one translation unit:
 // the kernels below go through the box-frame map, the owner / scan / scatter kernels, the ObjNet image and the obj_* layer helpers of
-// that file, on the plan's own NlrObjects.
+// that file, on the plan's own NlrObjects (laid out and allocated by obj_layout; nothing is filled from a descriptor).  Shapes,
+// offsets and columns come from the one layer table (nlr_obj_layers.h): ObjTrainLin / ObjTrainCls are that table as the
+// weight-gradient kernels read it (obj_train_cls), the flat-buffer layouts are its w_off / b_off, the kernel's columns its nlr_obj_cols.
+// The workspace, the owner -> scan -> scatter launches and ObjApply are those of nlr_objects.hip (obj_carve, obj_make_lists,
+// obj_apply_args).
 //
 //   forward   owner map -> per-class lists (the kernels of nlr_objects_apply) -> nlr_objtrain_kernel<.., FWD = true>: nlr_objmlp_kernel's
 //             layout from the weight image nlr_obj_train_pack made of the flat buffers, every Linear summed in the reference's order
-//             (one FMA chain from zero, bias last: obj_zero / obj_add_bias)
+//             (one FMA chain from zero, bias last: obj_begin / obj_end<BIAS_LAST = true>).  The walk through the layers is stated here
+//             a second time: against nlr_objmlp_kernel it differs in that switch, in the saved layer inputs and ReLU masks, and in
+//             clamping a list entry or an owner outside the batch to an idle lane.  A change to the network is made in both.
 //   backward  (1) nlr_objtrain_kernel<.., FWD = false>: one lane per owned sample.  It repeats that forward (same code, same bits), writes
 //                 every layer's input to `acts` and every Linear's pre-activation gradient to `gacts` (column-major [column][row]:
 //                 a wave stores 256 contiguous bytes per column), and scatters the grid-feature gradient into the class's table
@@ -24,7 +30,6 @@
 
 #include <algorithm>
 
-#define NLR_OBJT_LINEARS (2 + NLR_OBJ_MAX_DEPTH + 1)
 #define NLR_OBJT_SLICES 96      // slabs per (class, Linear)
 #define NLR_OBJT_GS 65          // row stride of the staged gradient chunk (floats): lanes read along a row, stores walk a column
 #define NLR_OBJT_XS 132         // row stride of the staged input chunk: 16-byte aligned rows, broadcast ds_read_b128
@@ -41,7 +46,7 @@ struct ObjTrainLin {
 };
 struct ObjTrainCls {
     uint32_t n_lin, n_params, slab_floats, aw, gw;
-    ObjTrainLin lin[NLR_OBJT_LINEARS];
+    ObjTrainLin lin[NLR_OBJ_LINEARS];
 };
 struct ObjTrainPtrs {
     float *p[NLR_OBJ_MAX_CLASSES];
@@ -88,22 +93,6 @@ __device__ __forceinline__ float obj_dot_row(const float *wrow, const float (&g)
         for (int e = 0; e < 4; ++e) s[e] = fmaf(w[e], g[o + e], s[e]);
     }
     return (s[0] + s[1]) + (s[2] + s[3]);
-}
-
-// A Linear in the reference's own order of operations.  At these widths (K = 64 .. 175) torch's Linear on the CPU (the f32 GEMM the reference
-// runs) was observed to give every output as ONE fused-multiply-add chain over the inputs in their order, started at zero, with the bias
-// added after the last input (DESIGN, round-4 f-1 x f-3): restated that way an output had the reference's bits, where nlr_objmlp_kernel (chain started at the bias) is a few ulp of the hidden units away.
-// Under the x1500 density gain of a trained-like field those ulp are 2e-5 of a density, which the resampler of the next level turns
-// into moved sample positions: training is held to the reference's step, so its forward sums as the reference does.
-template <int OUT>
-__device__ __forceinline__ void obj_zero(float (&acc)[OUT]) {
-#pragma unroll
-    for (int o = 0; o < OUT; ++o) acc[o] = 0.0f;
-}
-template <int OUT>
-__device__ __forceinline__ void obj_add_bias(float (&acc)[OUT], const float *b) {
-#pragma unroll
-    for (int o = 0; o < OUT; ++o) acc[o] = acc[o] + b[o];
 }
 
 // adjoint of nlr_level_accum_m with w_erf = 1: the 8 corner weights times the level's feature gradient, added into the table gradient
@@ -174,9 +163,7 @@ __global__ void __launch_bounds__(64 * NLR_OBJ_WAVES) nlr_objtrain_kernel(const 
     __syncthreads();
     float *sa = slab_a[wave], *sv = slab_v[wave];
     const size_t cap = a.cap;
-    // columns of acts: [grid | hidden 64 | bottleneck | dir enc | view 0 .. D-1]; of gacts: [hidden 64 | bottleneck | view 0 .. D-1 | rgb 4]
-    const uint32_t cH0 = net.n_grid, cBOT = cH0 + 64, cDE = cBOT + net.BW, cV = cDE + net.DE;
-    const uint32_t gBOT = 64, gV = gBOT + net.BW, gRGB = gV + net.D * net.W;
+    const ObjCols col = net.cols();  // columns of acts / gacts (nlr_obj_layers.h)
     float *gt = FWD ? nullptr : t.grad_tables.p[blockIdx.y];
     const bool want_rgb = !FWD || a.rgb != nullptr, save = !FWD;
     for (uint32_t base = (blockIdx.x * NLR_OBJ_WAVES + wave) * 64; base < count; base += gridDim.x * (64 * NLR_OBJ_WAVES)) {
@@ -233,30 +220,30 @@ __global__ void __launch_bounds__(64 * NLR_OBJ_WAVES) nlr_objtrain_kernel(const 
             for (int j = 0; j < LMAX * C; ++j)
                 if ((uint32_t)j < net.n_grid) ar[j * cap] = gf[j];
 #pragma unroll
-            for (int c = 0; c < 3; ++c) ar[(cDE + c) * cap] = de[c];
+            for (int c = 0; c < 3; ++c) ar[(col.cDE + c) * cap] = de[c];
 #pragma unroll
             for (int j = 0; j < 3 * NLR_OBJ_MAX_DEG; ++j)
                 if ((uint32_t)j < 3 * net.deg) {
-                    ar[(cDE + 3 + j) * cap] = ds0[j];
-                    ar[(cDE + 3 + 3 * net.deg + j) * cap] = ds1[j];
+                    ar[(col.cDE + 3 + j) * cap] = ds0[j];
+                    ar[(col.cDE + 3 + 3 * net.deg + j) * cap] = ds1[j];
                 }
         }
         const float *lat = net.latents + (size_t)tr * net.lat_size;
-        // ---- the forward, layer by layer as nlr_objmlp_kernel walks it, every Linear summed as the reference sums it (obj_zero /
-        // obj_add_bias); the backward also writes every layer's output to acts
+        // ---- the forward, layer by layer as nlr_objmlp_kernel walks it, every Linear summed as the reference sums it (obj_begin /
+        // obj_end<true>); the backward also writes every layer's output to acts
         uint64_t mh = 0;  // hidden unit o passed its ReLU
         {
             float h[64];
-            obj_zero<64>(h);
+            obj_begin<true, 64>(h, wl + net.o_bd0);
             obj_seg_reg<64, LMAX * C>(h, wl + net.o_d0, 0, net.n_grid, gf);
             obj_seg_mem<64>(h, wl + net.o_d0, net.n_grid, net.lat_shape, lat);
-            obj_add_bias<64>(h, wl + net.o_bd0);
+            obj_end<true, 64>(h, wl + net.o_bd0);
 #pragma unroll
             for (int o = 0; o < 64; ++o) {
                 const float r = fmaxf(h[o], 0.0f);
                 sa[o * 64 + lane] = r;
                 mh |= (uint64_t)(h[o] > 0.0f) << o;
-                if (save && valid) ar[(cH0 + o) * cap] = r;
+                if (save && valid) ar[(col.cH0 + o) * cap] = r;
             }
         }
         float xd;
@@ -273,13 +260,13 @@ __global__ void __launch_bounds__(64 * NLR_OBJ_WAVES) nlr_objtrain_kernel(const 
                 if (!want_rgb) continue;
             }
             float x[64];
-            obj_zero<64>(x);
+            obj_begin<true, 64>(x, wl + net.o_bd2);
             obj_seg_lds<64>(x, wl + net.o_d2, 0, 64, sa, lane);
-            obj_add_bias<64>(x, wl + net.o_bd2);
+            obj_end<true, 64>(x, wl + net.o_bd2);
 #pragma unroll
             for (int o = 0; o < 64; ++o) {
                 sa[o * 64 + lane] = x[o];
-                if (save && valid && (uint32_t)o < net.BW) ar[(cBOT + o) * cap] = x[o];
+                if (save && valid && (uint32_t)o < net.BW) ar[(col.cBOT + o) * cap] = x[o];
             }
         }
         const float *lat_tex = lat + net.lat_tex_off;
@@ -287,7 +274,7 @@ __global__ void __launch_bounds__(64 * NLR_OBJ_WAVES) nlr_objtrain_kernel(const 
         for (uint32_t i = 0; i < net.D; ++i) {
             float h[32];
             const float *wv = wl + net.o_v[i];
-            obj_zero<32>(h);
+            obj_begin<true, 32>(h, wl + net.o_bv[i]);
             uint32_t row = 0;
             if (i > 0) {
                 obj_seg_lds<32>(h, wv, 0, net.W, sv, lane);
@@ -300,21 +287,21 @@ __global__ void __launch_bounds__(64 * NLR_OBJ_WAVES) nlr_objtrain_kernel(const 
                 obj_seg_reg<32, 3 * NLR_OBJ_MAX_DEG>(h, wv, row + net.BW + 3 + 3 * net.deg, 3 * net.deg, ds1);
                 obj_seg_mem<32>(h, wv, row + net.BW + net.DE, net.lat_tex, lat_tex);
             }
-            obj_add_bias<32>(h, wl + net.o_bv[i]);
+            obj_end<true, 32>(h, wl + net.o_bv[i]);
             uint32_t mk = 0;
 #pragma unroll
             for (int o = 0; o < 32; ++o) {
                 const float r = fmaxf(h[o], 0.0f);
                 sv[o * 64 + lane] = r;
                 mk |= (uint32_t)(h[o] > 0.0f) << o;
-                if (save && valid && (uint32_t)o < net.W) ar[(cV + i * net.W + o) * cap] = r;
+                if (save && valid && (uint32_t)o < net.W) ar[(col.cV + i * net.W + o) * cap] = r;
             }
 #pragma unroll
             for (uint32_t j = 0; j < NLR_OBJ_MAX_DEPTH; ++j) mv[j] = j == i ? mk : mv[j];
         }
         float c4[4];
         const float *wr = wl + net.o_rgb;
-        obj_zero<4>(c4);
+        obj_begin<true, 4>(c4, wl + net.o_brgb);
         obj_seg_lds<4>(c4, wr, 0, net.W, sv, lane);
         if (net.D - 1 == net.skip) {
             obj_seg_lds<4>(c4, wr, net.W, net.BW, sa, lane);
@@ -323,7 +310,7 @@ __global__ void __launch_bounds__(64 * NLR_OBJ_WAVES) nlr_objtrain_kernel(const 
             obj_seg_reg<4, 3 * NLR_OBJ_MAX_DEG>(c4, wr, net.W + net.BW + 3 + 3 * net.deg, 3 * net.deg, ds1);
             obj_seg_mem<4>(c4, wr, net.W + net.BW + net.DE, net.lat_tex, lat_tex);
         }
-        obj_add_bias<4>(c4, wl + net.o_brgb);
+        obj_end<true, 4>(c4, wl + net.o_brgb);
         if (FWD) {
             if (valid) {
 #pragma unroll
@@ -341,7 +328,7 @@ __global__ void __launch_bounds__(64 * NLR_OBJ_WAVES) nlr_objtrain_kernel(const 
             const float sg = 1.0f / (1.0f + expf(-(net.premul * c4[c] + net.rgb_bias)));
             const float up = valid ? t.g_rgb[(size_t)c * a.N * a.S + m] : 0.0f;
             gc[c] = ((up * (1.0f + 2.0f * net.rgb_pad)) * (sg * (1.0f - sg))) * net.premul;
-            if (valid) gr[(gRGB + c) * cap] = gc[c];
+            if (valid) gr[(col.gRGB + c) * cap] = gc[c];
         }
 #pragma unroll
         for (int o = 0; o < 64; ++o) sa[o * 64 + lane] = 0.0f;  // the bottleneck gradient collects here (every read of the bottleneck is done)
@@ -365,7 +352,7 @@ __global__ void __launch_bounds__(64 * NLR_OBJ_WAVES) nlr_objtrain_kernel(const 
             if (valid) {
 #pragma unroll
                 for (int o = 0; o < 32; ++o)
-                    if ((uint32_t)o < net.W) gr[(gV + i * net.W + o) * cap] = gv[o];
+                    if ((uint32_t)o < net.W) gr[(col.gV + i * net.W + o) * cap] = gv[o];
             }
             const float *wv = wl + net.o_v[i];
             uint32_t row = 0;
@@ -396,7 +383,7 @@ __global__ void __launch_bounds__(64 * NLR_OBJ_WAVES) nlr_objtrain_kernel(const 
             if (valid) {
 #pragma unroll
                 for (int o = 0; o < 64; ++o)
-                    if ((uint32_t)o < net.BW) gr[(gBOT + o) * cap] = gb[o];
+                    if ((uint32_t)o < net.BW) gr[(col.gBOT + o) * cap] = gb[o];
             }
             for (uint32_t kk = 0; kk < 64; ++kk) {
                 float s = obj_dot_row<64>(wl + net.o_d2 + kk * 64, gb);
@@ -585,143 +572,67 @@ struct NlrObjTrainPlan {
     }
 };
 
-// The Linears of one class in the order of its flat buffer, from the descriptor's scalars alone: (out, in) per Linear; returns their number
-// (0: a depth outside the envelope).  The one statement of the shapes: the plan's zero-weight descriptor and nlr_obj_train_desc_layout.
-static uint32_t obj_train_shapes(const NlrObjClassDesc &cd, uint32_t (&shape)[NLR_OBJT_LINEARS][2]) {
-    const NlrMlpDesc &md = cd.mlp;
-    if (md.net_depth_viewdirs < 1 || md.net_depth_viewdirs > NLR_OBJ_MAX_DEPTH) return 0;
-    const uint32_t lat = cd.latent_size, lat_shape = lat ? (cd.split_latent ? lat / 2 : lat) : 0;
-    const uint32_t lat_tex = (lat && cd.split_latent) ? lat - lat / 2 : 0;
-    const uint32_t in_rgb = md.bottleneck_width + 3 + 6 * md.deg_view + lat_tex;
-    uint32_t n = 0, last = in_rgb;
-    shape[n][0] = 64, shape[n++][1] = md.grid.num_levels * md.grid.level_dim + lat_shape;
-    shape[n][0] = md.bottleneck_width, shape[n++][1] = 64;
-    for (uint32_t i = 0; i < md.net_depth_viewdirs; ++i) {
-        shape[n][0] = md.net_width_viewdirs, shape[n++][1] = last;
-        last = md.net_width_viewdirs + (i == md.skip_layer_dir ? in_rgb : 0);
-    }
-    shape[n][0] = 3, shape[n++][1] = last;
-    return n;
-}
-
 // host arithmetic only: the offsets (weight, bias per Linear) of class `cls` of a descriptor, then the buffer's length; returns the
 // number of entries written (2 per Linear + 1)
 extern "C" int nlr_obj_train_desc_layout(const NlrObjectsDesc *d, uint32_t cls, uint32_t *offsets_host, uint32_t capacity) {
     NLR_CHECK_ARG(d && d->classes && offsets_host && cls < d->n_classes, "obj_train_desc_layout: NULL argument or class %u outside the descriptor", cls);
-    uint32_t shape[NLR_OBJT_LINEARS][2];
-    const uint32_t n = obj_train_shapes(d->classes[cls], shape);
-    if (!n) NLR_FAIL(NLR_ERR_UNSUPPORTED, "obj_train_desc_layout: net_depth_viewdirs %u outside [1,%d]", d->classes[cls].mlp.net_depth_viewdirs, NLR_OBJ_MAX_DEPTH);
-    NLR_CHECK_ARG(capacity >= 2 * n + 1, "obj_train_desc_layout: buffer too small (%u entries)", 2 * n + 1);
-    uint32_t off = 0;
-    for (uint32_t i = 0; i < n; ++i) {
-        offsets_host[2 * i] = off;
-        offsets_host[2 * i + 1] = off + shape[i][0] * shape[i][1];
-        off += shape[i][0] * shape[i][1] + shape[i][0];
-    }
-    offsets_host[2 * n] = off;
-    return (int)(2 * n + 1);
+    ObjLayers t;
+    char msg[256];
+    if (!nlr_obj_layers(d->classes[cls], "obj_train_desc_layout", cls, t, msg, sizeof(msg))) NLR_FAIL(NLR_ERR_UNSUPPORTED, "%s", msg);
+    NLR_CHECK_ARG(capacity >= 2 * t.n_lin + 1, "obj_train_desc_layout: buffer too small (%u entries)", 2 * t.n_lin + 1);
+    for (uint32_t i = 0; i < t.n_lin; ++i) offsets_host[2 * i] = t.lin[i].w_off, offsets_host[2 * i + 1] = t.lin[i].b_off;
+    offsets_host[2 * t.n_lin] = t.n_params;
+    return (int)(2 * t.n_lin + 1);
 }
 
+// the layer table as the weight-gradient kernels read it: acts blocks and the latent block apart, the per-track sums behind the parameters
+static ObjTrainCls obj_train_cls(const ObjLayers &t, uint32_t n_tracks) {
+    ObjTrainCls tc;
+    memset(&tc, 0, sizeof(tc));
+    tc.n_lin = t.n_lin, tc.n_params = t.n_params, tc.aw = t.col.aw, tc.gw = t.col.gw;
+    tc.slab_floats = t.n_params;
+    for (uint32_t i = 0; i < t.n_lin; ++i) {
+        const ObjLinear &s = t.lin[i];
+        ObjTrainLin &L = tc.lin[i];
+        L.w_off = s.w_off, L.b_off = s.b_off, L.n_out = s.n_out, L.n_in = s.n_in;
+        L.outp = s.outp, L.img_w = s.img_w, L.img_b = s.img_b, L.g_col = s.g_col;
+        L.gt_off = t.n_params;  // (unused where lat_n = 0)
+        for (uint32_t k = 0; k < s.n_inputs; ++k) {
+            const ObjInput &in = s.in[k];
+            if (in.latent()) {  // (a Linear takes at most one half of the code)
+                L.lat_n = in.n, L.lat_wcol = in.wcol, L.lat_off = in.src;
+                L.gt_off = tc.slab_floats;
+                tc.slab_floats += n_tracks * s.n_out;
+            } else {
+                L.blk[L.n_blk][0] = in.src, L.blk[L.n_blk][1] = in.n, L.blk[L.n_blk][2] = in.wcol;
+                ++L.n_blk;
+            }
+        }
+    }
+    return tc;
+}
+
+// The plan is made of shapes: the object set is laid out and allocated (obj_layout: envelope, table, zeroed images and codes), and
+// nlr_obj_train_pack fills the images from the flat buffers.
 extern "C" int nlr_obj_train_plan_create(const NlrObjectsDesc *d, NlrObjTrainPlan **out, uint32_t *n_params_host, void *stream) {
     NLR_CHECK_ARG(d && out && n_params_host, "obj_train_plan_create: NULL argument");
-    NLR_CHECK_ARG(d->n_classes >= 1 && d->n_classes <= NLR_OBJ_MAX_CLASSES && d->classes, "obj_train_plan_create: n_classes = %u outside [1,%d]",
-                  d->n_classes, NLR_OBJ_MAX_CLASSES);
-    NLR_CHECK_ARG(d->n_tracks >= 1 && d->track_class, "obj_train_plan_create: no tracks");
     if (d->n_tracks > NLR_OBJT_MAX_TRACKS)
         NLR_FAIL(NLR_ERR_UNSUPPORTED, "obj_train_plan_create: n_tracks = %u, the weight-gradient kernel keeps per-track sums for at most %d",
                  d->n_tracks, NLR_OBJT_MAX_TRACKS);
-    // The plan is made of shapes: the object set is created on zero weights and zero codes of those shapes (nlr_objects_create checks
-    // the envelope and lays out the images), nlr_obj_train_pack fills the images from the flat buffers.
-    std::vector<NlrObjClassDesc> cds(d->classes, d->classes + d->n_classes);
-    size_t zmax = (size_t)d->n_tracks * d->classes[0].latent_size + 64;
-    for (NlrObjClassDesc &cd : cds) {
-        NlrMlpDesc &md = cd.mlp;
-        if (md.grid.table_dtype != 0) NLR_FAIL(NLR_ERR_UNSUPPORTED, "obj_train_plan_create: the table gradient is f32, table_dtype must be 0");
-        uint32_t shape[NLR_OBJT_LINEARS][2];
-        const uint32_t n = obj_train_shapes(cd, shape);
-        if (!n) NLR_FAIL(NLR_ERR_UNSUPPORTED, "obj_train_plan_create: net_depth_viewdirs %u outside [1,%d]", md.net_depth_viewdirs, NLR_OBJ_MAX_DEPTH);
-        NlrLinear *lin[NLR_OBJT_LINEARS] = {&md.density0, &md.density2};
-        for (uint32_t i = 0; i < md.net_depth_viewdirs; ++i) lin[2 + i] = &md.view[i];
-        lin[n - 1] = &md.rgb_layer;
-        for (uint32_t i = 0; i < n; ++i) {
-            lin[i]->out_features = shape[i][0];
-            lin[i]->in_features = shape[i][1];
-            zmax = std::max(zmax, (size_t)shape[i][0] * shape[i][1]);
-        }
-    }
-    std::vector<float> zeros(zmax, 0.0f);
-    for (NlrObjClassDesc &cd : cds) {
-        NlrMlpDesc &md = cd.mlp;
-        md.density0.weight = md.density0.bias = md.density2.weight = md.density2.bias = zeros.data();
-        for (uint32_t i = 0; i < md.net_depth_viewdirs; ++i) md.view[i].weight = md.view[i].bias = zeros.data();
-        md.rgb_layer.weight = md.rgb_layer.bias = zeros.data();
-    }
-    NlrObjectsDesc od = *d;
-    od.classes = cds.data();
-    od.latents = zeros.data();
-    std::unique_ptr<NlrObjTrainPlan> p(new NlrObjTrainPlan());
-    int rc = nlr_objects_create(&od, &p->objs, stream);
+    for (uint32_t c = 0; d->classes && c < d->n_classes && c < NLR_OBJ_MAX_CLASSES; ++c)
+        if (d->classes[c].mlp.grid.table_dtype != 0)
+            NLR_FAIL(NLR_ERR_UNSUPPORTED, "obj_train_plan_create: the table gradient is f32, table_dtype must be 0");
+    std::unique_ptr<NlrObjects> objs;
+    int rc = obj_layout(d, "obj_train_plan_create", objs, (hipStream_t)stream);
     if (rc) return rc;
+    std::unique_ptr<NlrObjTrainPlan> p(new NlrObjTrainPlan());
+    p->objs = objs.release();
     p->lat_size = d->classes[0].latent_size;
     p->lat_dev = const_cast<float *>(p->objs->cls[0].latents);
-    p->cls.resize(d->n_classes);
     for (uint32_t c = 0; c < d->n_classes; ++c) {
-        const ObjNet &n = p->objs->cls[c];
-        ObjTrainCls &tc = p->cls[c];
-        memset(&tc, 0, sizeof(tc));
-        const uint32_t in_rgb = n.BW + n.DE + n.lat_tex;
-        const uint32_t aH0 = n.n_grid, aBOT = aH0 + 64, aDE = aBOT + n.BW, aV = aDE + n.DE;
-        const uint32_t gBOT = 64, gV = gBOT + n.BW, gRGB = gV + n.D * n.W;
-        tc.aw = aV + n.D * n.W;
-        tc.gw = gRGB + 4;
-        uint32_t off = 0, gt = 0;
-        auto add = [&](uint32_t n_out, uint32_t n_in, uint32_t outp, uint32_t img_w, uint32_t img_b, uint32_t g_col) -> ObjTrainLin & {
-            ObjTrainLin &L = tc.lin[tc.n_lin++];
-            L.w_off = off;
-            L.b_off = off + n_out * n_in;
-            off = L.b_off + n_out;
-            L.n_out = n_out, L.n_in = n_in, L.outp = outp, L.img_w = img_w, L.img_b = img_b, L.g_col = g_col;
-            return L;
-        };
-        auto block = [](ObjTrainLin &L, uint32_t col, uint32_t cnt, uint32_t wcol) {
-            if (!cnt) return;
-            L.blk[L.n_blk][0] = col, L.blk[L.n_blk][1] = cnt, L.blk[L.n_blk][2] = wcol;
-            ++L.n_blk;
-        };
-        auto latent = [&](ObjTrainLin &L, uint32_t cnt, uint32_t wcol, uint32_t lat_off) {
-            if (!cnt) return;
-            L.lat_n = cnt, L.lat_wcol = wcol, L.lat_off = lat_off;
-            L.gt_off = gt;
-            gt += d->n_tracks * L.n_out;
-        };
-        // the view layers' concatenated input [bottleneck | dir enc | texture half] behind `row` columns of the previous layer
-        auto concat = [&](ObjTrainLin &L, uint32_t row) {
-            block(L, aBOT, n.BW, row);
-            block(L, aDE, n.DE, row + n.BW);
-            latent(L, n.lat_tex, row + n.BW + n.DE, n.lat_tex_off);
-        };
-        {
-            ObjTrainLin &L = add(64, n.n_grid + n.lat_shape, 64, n.o_d0, n.o_bd0, 0);
-            block(L, 0, n.n_grid, 0);
-            latent(L, n.lat_shape, n.n_grid, 0);
-        }
-        block(add(n.BW, 64, 64, n.o_d2, n.o_bd2, gBOT), aH0, 64, 0);
-        uint32_t last = in_rgb;
-        for (uint32_t i = 0; i < n.D; ++i) {
-            ObjTrainLin &L = add(n.W, last, 32, n.o_v[i], n.o_bv[i], gV + i * n.W);
-            if (i > 0) block(L, aV + (i - 1) * n.W, n.W, 0);
-            if (i == 0 || i - 1 == n.skip) concat(L, i > 0 ? n.W : 0);
-            last = n.W + (i == n.skip ? in_rgb : 0);
-        }
-        {
-            ObjTrainLin &L = add(3, last, 4, n.o_rgb, n.o_brgb, gRGB);
-            block(L, aV + (n.D - 1) * n.W, n.W, 0);
-            if (n.D - 1 == n.skip) concat(L, n.W);
-        }
-        tc.n_params = off;
-        for (uint32_t li = 0; li < tc.n_lin; ++li) tc.lin[li].gt_off += off;  // (unused where lat_n = 0)
-        tc.slab_floats = off + gt;
-        n_params_host[c] = off;
+        p->cls.push_back(obj_train_cls(p->objs->layers[c], d->n_tracks));
+        const ObjTrainCls &tc = p->cls.back();
+        n_params_host[c] = tc.n_params;
         p->slab_stride = std::max(p->slab_stride, (tc.slab_floats + 63u) & ~63u);
         p->aw = std::max(p->aw, tc.aw);
         p->gw = std::max(p->gw, tc.gw);
@@ -753,23 +664,20 @@ extern "C" int nlr_obj_train_pack(NlrObjTrainPlan *p, const float *const *params
         NLR_CHECK_ARG(params[c], "obj_train_pack: params[%zu] is NULL", c);
         pp.p[c] = const_cast<float *>(params[c]);
     }
-    hipLaunchKernelGGL(nlr_objtrain_pack_kernel, dim3(8, NLR_OBJT_LINEARS, (unsigned)p->cls.size()), dim3(256), 0, (hipStream_t)stream, p->cls_dev,
+    hipLaunchKernelGGL(nlr_objtrain_pack_kernel, dim3(8, NLR_OBJ_LINEARS, (unsigned)p->cls.size()), dim3(256), 0, (hipStream_t)stream, p->cls_dev,
                        p->objs->nets_dev, pp);
     NLR_LAUNCH_CHECK("nlr_objtrain_pack_kernel");
     return NLR_OK;
 }
 
-// workspace: [what nlr_objects_apply carves: counts | owner map | lists | per-wave counts] and, for the backward,
-// [acts aw x M | gacts gw x M | slabs SLICES x classes x stride | totals classes x stride] f32
-static size_t obj_train_fwd_bytes(const NlrObjTrainPlan *p, uint32_t N, uint32_t S) { return nlr_objects_workspace_bytes(p->objs, N, S); }
+// the workspace of nlr_objects_apply and, for the backward, acts / gacts / slabs / totals behind it (obj_carve, nlr_objects.hip)
+static ObjWorkspace obj_train_carve(const NlrObjTrainPlan *p, void *workspace, uint32_t N, uint32_t S, int backward) {
+    const size_t nc = p->cls.size();
+    if (!backward) return obj_carve(workspace, nc, N, S, 0, 0, 0, 0);
+    return obj_carve(workspace, nc, N, S, p->aw, p->gw, (size_t)NLR_OBJT_SLICES * nc * p->slab_stride, nc * p->slab_stride);
+}
 extern "C" size_t nlr_obj_train_workspace_bytes(const NlrObjTrainPlan *p, uint32_t N, uint32_t S, int backward) {
-    if (!p) return 0;
-    size_t b = obj_train_fwd_bytes(p, N, S);
-    if (backward) {
-        const size_t M = (size_t)N * S, nc = p->cls.size();
-        b += al(M * p->aw * 4) + al(M * p->gw * 4) + al((size_t)NLR_OBJT_SLICES * nc * p->slab_stride * 4) + al(nc * p->slab_stride * 4);
-    }
-    return b;
+    return p ? obj_train_carve(p, nullptr, N, S, backward).bytes : 0;
 }
 
 // the checks both passes share; *run = 0: nothing to do
@@ -806,6 +714,20 @@ static int obj_train_bind(NlrObjTrainPlan *p, const float *const *tables, const 
     return NLR_OK;
 }
 
+static int obj_train_launch(const NlrObjTrainPlan *p, bool fwd, uint32_t N, uint32_t S, const ObjApply &a, const ObjTrainB &tb, hipStream_t st) {
+    const NlrObjects *o = p->objs;
+    const uint32_t C = o->cls[0].gp.C;
+#define OBJT_LAUNCH(C_, LM)                                                                                                                      \
+    if (fwd) hipLaunchKernelGGL((nlr_objtrain_kernel<C_, LM, true>), obj_net_grid(o, N, S), dim3(64 * NLR_OBJ_WAVES), 0, st, o->nets_dev, a, tb); \
+    else hipLaunchKernelGGL((nlr_objtrain_kernel<C_, LM, false>), obj_net_grid(o, N, S), dim3(64 * NLR_OBJ_WAVES), 0, st, o->nets_dev, a, tb)
+    if (C == 2) { OBJT_LAUNCH(2, 8); }
+    else if (C == 4) { OBJT_LAUNCH(4, 4); }
+    else { OBJT_LAUNCH(1, 16); }
+#undef OBJT_LAUNCH
+    NLR_LAUNCH_CHECK(fwd ? "nlr_objtrain_kernel (forward)" : "nlr_objtrain_kernel (backward)");
+    return NLR_OK;
+}
+
 extern "C" int nlr_obj_train_forward(NlrObjTrainPlan *p, const float *const *tables, const float *latents, const NlrRays *rays,
                                      const float *tdist, const float *box_params, uint32_t N, uint32_t S, uint32_t n_obj, float *density,
                                      float *rgb, float *semantic, uint32_t K, int32_t *winner, void *workspace, size_t workspace_bytes,
@@ -816,52 +738,12 @@ extern "C" int nlr_obj_train_forward(NlrObjTrainPlan *p, const float *const *tab
     NLR_CHECK_ARG(winner, "obj_train_forward: winner is NULL");
     hipStream_t st = (hipStream_t)stream;
     if ((rc = obj_train_bind(p, tables, latents, st))) return rc;
-    // owner map and lists as nlr_objects_apply_impl makes them (same kernels, same carving), then this file's forward
-    const size_t M = (size_t)N * S;
-    const uint32_t nc = (uint32_t)p->cls.size();
-    char *w = (char *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    uint32_t *counts = (uint32_t *)w;
-    int32_t *own = (int32_t *)(w + 256);
-    uint32_t *lists = (uint32_t *)(w + 256 + al(M * 4));
-    uint32_t *wave_counts = (uint32_t *)(w + 256 + al(M * 4) + al((size_t)nc * M * 4));
-    const uint32_t nblk = (uint32_t)((M + 255) / 256), nw = nblk * 4;
-    hipLaunchKernelGGL(nlr_box_owner_kernel, dim3(nblk), dim3(256), 0, st, tdist, rays->origins, rays->directions, box_params, N, S, n_obj,
-                       p->objs->track_class, nc, own, wave_counts);
-    NLR_LAUNCH_CHECK("nlr_box_owner_kernel");
-    hipLaunchKernelGGL(nlr_obj_scan_kernel, dim3(nc), dim3(1024), 0, st, wave_counts, nw, counts);
-    NLR_LAUNCH_CHECK("nlr_obj_scan_kernel");
-    hipLaunchKernelGGL(nlr_obj_scatter_kernel, dim3(nblk), dim3(256), 0, st, own, p->objs->track_class, (uint32_t)M, nc, wave_counts, lists, (uint32_t)M);
-    NLR_LAUNCH_CHECK("nlr_obj_scatter_kernel");
-    NLR_HIP(hipMemcpyAsync(winner, own, M * 4, hipMemcpyDeviceToDevice, st));
-    ObjApply a;
-    a.lists = lists;
-    a.counts = counts;
-    a.cap = (uint32_t)M;
-    a.winner = own;
-    a.tdist = tdist;
-    a.origins = rays->origins;
-    a.dirs = rays->directions;
-    a.viewdirs = rays->viewdirs;
-    a.box = box_params;
-    a.N = N;
-    a.S = S;
-    a.n_obj = n_obj;
-    a.K = semantic ? K : 0;
-    a.density = density;
-    a.rgb = rgb;
-    a.sem = semantic;
+    // owner map and lists as nlr_objects_apply_impl makes them (same function, same carving), then this file's forward
+    const ObjWorkspace w = obj_train_carve(p, workspace, N, S, 0);
+    if ((rc = obj_make_lists(p->objs, w, rays, tdist, box_params, N, S, n_obj, winner, st))) return rc;
     ObjTrainB tb;
     memset(&tb, 0, sizeof(tb));
-    const uint32_t per = 64 * NLR_OBJ_WAVES, nb = (uint32_t)((M + per - 1) / per);
-    const uint32_t grid = p->objs->cus < nb ? p->objs->cus : nb;
-    const uint32_t C = p->objs->cls[0].gp.C;
-#define OBJT_LAUNCH(C_, LM) hipLaunchKernelGGL((nlr_objtrain_kernel<C_, LM, true>), dim3(grid, nc), dim3(64 * NLR_OBJ_WAVES), 0, st, p->objs->nets_dev, a, tb)
-    if (C == 2) OBJT_LAUNCH(2, 8);
-    else if (C == 4) OBJT_LAUNCH(4, 4);
-    else OBJT_LAUNCH(1, 16);
-#undef OBJT_LAUNCH
-    NLR_LAUNCH_CHECK("nlr_objtrain_kernel (forward)");
-    return NLR_OK;
+    return obj_train_launch(p, true, N, S, obj_apply_args(w, rays, tdist, box_params, N, S, n_obj, density, rgb, semantic, K), tb, st);
 }
 
 extern "C" int nlr_obj_train_backward(NlrObjTrainPlan *p, const float *const *tables, const float *latents, const NlrRays *rays,
@@ -885,68 +767,22 @@ extern "C" int nlr_obj_train_backward(NlrObjTrainPlan *p, const float *const *ta
     }
     hipStream_t st = (hipStream_t)stream;
     if ((rc = obj_train_bind(p, tables, latents, st))) return rc;
-    const size_t M = (size_t)N * S;
-    // the forward's part of the workspace, as nlr_objects_apply_impl carved it
-    char *w = (char *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    const uint32_t *counts = (const uint32_t *)w;
-    const int32_t *winner = (const int32_t *)(w + 256);
-    const uint32_t *lists = (const uint32_t *)(w + 256 + al(M * 4));
-    w += obj_train_fwd_bytes(p, N, S) - 256;
-    float *acts = (float *)w;
-    w += al(M * p->aw * 4);
-    float *gacts = (float *)w;
-    w += al(M * p->gw * 4);
-    float *slabs = (float *)w;
-    w += al((size_t)NLR_OBJT_SLICES * nc * p->slab_stride * 4);
-    float *totals = (float *)w;
-    ObjApply a;
-    a.lists = lists;
-    a.counts = counts;
-    a.cap = (uint32_t)M;
-    a.winner = winner;
-    a.tdist = tdist;
-    a.origins = rays->origins;
-    a.dirs = rays->directions;
-    a.viewdirs = rays->viewdirs;
-    a.box = box_params;
-    a.N = N;
-    a.S = S;
-    a.n_obj = n_obj;
-    a.K = 0;
-    a.density = a.rgb = a.sem = nullptr;
-    tb.g_density = g_density;
-    tb.g_rgb = g_rgb;
-    tb.acts = acts;
-    tb.gacts = gacts;
-    const uint32_t per = 64 * NLR_OBJ_WAVES, nb = (uint32_t)((M + per - 1) / per);
-    const uint32_t grid = p->objs->cus < nb ? p->objs->cus : nb;
-    const uint32_t C = p->objs->cls[0].gp.C;
-#define OBJT_LAUNCH(C_, LM) hipLaunchKernelGGL((nlr_objtrain_kernel<C_, LM, false>), dim3(grid, nc), dim3(64 * NLR_OBJ_WAVES), 0, st, p->objs->nets_dev, a, tb)
-    if (C == 2) OBJT_LAUNCH(2, 8);
-    else if (C == 4) OBJT_LAUNCH(4, 4);
-    else OBJT_LAUNCH(1, 16);
-#undef OBJT_LAUNCH
-    NLR_LAUNCH_CHECK("nlr_objtrain_kernel (backward)");
-    ObjTrainW tw;
-    tw.lists = lists;
-    tw.counts = counts;
-    tw.winner = winner;
-    tw.cap = (uint32_t)M;
-    tw.n_tracks = n_obj;
-    tw.acts = acts;
-    tw.gacts = gacts;
-    tw.slabs = slabs;
-    tw.slab_stride = p->slab_stride;
-    hipLaunchKernelGGL(nlr_objtrain_wgrad_kernel, dim3(NLR_OBJT_SLICES, NLR_OBJT_LINEARS, nc), dim3(256), 0, st, p->cls_dev, tw);
+    // counts, owner map and lists are the forward's, where it left them in this workspace
+    const ObjWorkspace w = obj_train_carve(p, workspace, N, S, 1);
+    tb.g_density = g_density, tb.g_rgb = g_rgb, tb.acts = w.acts, tb.gacts = w.gacts;
+    if ((rc = obj_train_launch(p, false, N, S, obj_apply_args(w, rays, tdist, box_params, N, S, n_obj, nullptr, nullptr, nullptr, 0), tb, st)))
+        return rc;
+    const ObjTrainW tw = {w.lists, w.counts, w.winner, /*cap*/ N * S, /*n_tracks*/ n_obj, w.acts, w.gacts, w.slabs, p->slab_stride};
+    hipLaunchKernelGGL(nlr_objtrain_wgrad_kernel, dim3(NLR_OBJT_SLICES, NLR_OBJ_LINEARS, nc), dim3(256), 0, st, p->cls_dev, tw);
     NLR_LAUNCH_CHECK("nlr_objtrain_wgrad_kernel");
-    hipLaunchKernelGGL(nlr_objtrain_sum_kernel, dim3((p->slab_stride + 255) / 256, nc), dim3(256), 0, st, p->cls_dev, slabs, p->slab_stride, totals);
+    hipLaunchKernelGGL(nlr_objtrain_sum_kernel, dim3((p->slab_stride + 255) / 256, nc), dim3(256), 0, st, p->cls_dev, w.slabs, p->slab_stride, w.totals);
     NLR_LAUNCH_CHECK("nlr_objtrain_sum_kernel");
-    hipLaunchKernelGGL(nlr_objtrain_params_kernel, dim3((p->slab_stride + 255) / 256, nc), dim3(256), 0, st, p->cls_dev, totals, p->slab_stride,
+    hipLaunchKernelGGL(nlr_objtrain_params_kernel, dim3((p->slab_stride + 255) / 256, nc), dim3(256), 0, st, p->cls_dev, w.totals, p->slab_stride,
                        p->lat_dev, p->lat_size, n_obj, dp);
     NLR_LAUNCH_CHECK("nlr_objtrain_params_kernel");
     if (p->lat_size) {
         hipLaunchKernelGGL(nlr_objtrain_latents_kernel, dim3((n_obj * p->lat_size + 255) / 256), dim3(256), 0, st, p->cls_dev, p->objs->nets_dev,
-                           p->objs->track_class, totals, p->slab_stride, p->lat_size, n_obj, d_latents);
+                           p->objs->track_class, w.totals, p->slab_stride, p->lat_size, n_obj, d_latents);
         NLR_LAUNCH_CHECK("nlr_objtrain_latents_kernel");
     }
     return NLR_OK;

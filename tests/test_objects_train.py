@@ -53,6 +53,28 @@ def test_param_layout_follows_the_linear_shapes(depth, skip, split, lat):
     assert _lib.lib().nlr_obj_train_desc_layout(C.byref(od), 1, offs, 32) == -1
 
 
+def test_layer_table_at_the_edges_of_the_envelope():
+    """The one layer table of the object network (csrc/nlr_obj_layers.h, read through `nlr_obj_train_desc_layout`) against
+    `weights.mlp_param_shapes`, the independent Python statement, at the envelope's edges: depth 1, depth 4 with the skip concatenation
+    behind every layer 0..3, no latent code, next to `LAYOUT_CASES`.  A depth of 0 or 5 is refused with the message of today."""
+    from nerflidar_hip import _lib, training as ntrain
+    L = _lib.lib()
+    cases = LAYOUT_CASES + [(1, 0, True, 16), (1, 4, False, 16)] + [(4, s, split, 16) for s in range(4) for split in (True, False)]
+    cases += [(d, s, True, 0) for d, s in ((1, 0), (2, 0), (4, 3))]
+    offs = (C.c_uint32 * 32)()
+    for depth, skip, split, lat in cases:
+        cfg = _layout_cfg(depth, skip, split, lat)
+        od, keep = ntrain.objects_desc([ntrain.TrainableObjMLP(cfg)], [0, 0], lat)
+        n = L.nlr_obj_train_desc_layout(C.byref(od), 0, offs, 32)
+        want, total = _layout(cfg)
+        assert n == 2 * (depth + 3) + 1 == len(want) + 1 and list(offs[:n]) == want + [total], (depth, skip, split, lat)
+    od, keep = ntrain.objects_desc([ntrain.TrainableObjMLP(_layout_cfg(2, 4, True, 16))], [0, 0], 16)
+    for depth in (0, 5):
+        od.classes[0].mlp.net_depth_viewdirs = depth
+        assert L.nlr_obj_train_desc_layout(C.byref(od), 0, offs, 32) == -2   # NLR_ERR_UNSUPPORTED
+        assert L.nlr_last_error().decode() == f"obj_train_desc_layout: net_depth_viewdirs {depth} outside [1,4]"
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("depth,skip,split,lat", LAYOUT_CASES[:4])
 def test_plan_layout_is_the_descriptor_layout(depth, skip, split, lat):
