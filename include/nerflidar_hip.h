@@ -601,7 +601,21 @@ int nlr_render_lidar_dynamic(const NlrModel *m, const NlrObjects *o, const NlrRa
  *      and summed in slab order: no atomics, and the same inputs give the same bits in d_params and d_latents.  The latent code
  *      enters through Linear layers only, so its gradient and that of the weights it multiplies are products of weight slices / codes
  *      with the PER-TRACK sums of the pre-activation gradients, formed in the same reduction; no [samples, latent_size] tensor exists.
- *      Not here: gradients of the box frame (tracks, rays) - see 7c / 7d.
+ *
+ * nlr_obj_train_backward_frame: nlr_obj_train_backward plus the cotangents of the box frame, for track and pose refinement.  g_pts,
+ *      g_dirs [N*S, 3] f32, each may be NULL (then neither computed nor written); when non-NULL every row is OVERWRITTEN: row
+ *      m = ray * S + k holds d loss / d (box-frame point) and d loss / d (normalised box-frame direction) of sample k of the ray, the
+ *      two tensors the ObjMLP of the sample's owner takes; rows of samples no track owns are exact zeros.  The LAUNCHER clears both
+ *      buffers on the stream (hipMemsetAsync) and the kernel writes the rows of the owned samples.  The point enters through the
+ *      hash grid alone (derivative of the trilinear gather in the cell, and on the smoothstep branch, the forward took; zero outside
+ *      the unit cube), the direction through its positional encoding in every Linear that takes the concatenated input (view layer 0,
+ *      view layer skip_layer_dir + 1, rgb_layer); both are formed by the lane that owns the sample in a fixed order, so the same
+ *      inputs give the same bits, and each buffer has the same bits whether or not the other is requested.  d_params, d_latents and
+ *      grad_tables are those of nlr_obj_train_backward (d_params and d_latents bit for bit); with both pointers NULL the call IS
+ *      nlr_obj_train_backward (same kernel instance).  Same workspace, same refusals.
+ *      Together with the owner map `winner` of the forward the two buffers are what 7c and 7d take, as a DENSE list: K = N * S,
+ *      ray_idx[m] = m / S, sample_idx[m] = m % S, track_idx[m] = winner[m].  The list is sorted by (ray, sample), and by the contracts
+ *      of 7c and 7d an entry whose track is -1 contributes nothing: no count and no compaction reaches the host.
  *
  * nlr_obj_train_workspace_bytes(plan, N, S, backward): backward = 0 for a forward whose backward never runs (the size of
  *      nlr_objects_workspace_bytes), 1 adds (act_width + gact_width) * N * S * 4 bytes and the slabs (REF shape 65 536 x 32, shipped
@@ -624,6 +638,11 @@ int nlr_obj_train_backward(NlrObjTrainPlan *p, const float *const *tables, const
                            const float *box_params, uint32_t N, uint32_t S, uint32_t n_obj, const float *g_density, const float *g_rgb,
                            float *const *d_params, float *d_latents, float *const *grad_tables, void *workspace, size_t workspace_bytes,
                            void *stream);
+int nlr_obj_train_backward_frame(NlrObjTrainPlan *p, const float *const *tables, const float *latents, const NlrRays *rays,
+                                 const float *tdist, const float *box_params, uint32_t N, uint32_t S, uint32_t n_obj,
+                                 const float *g_density, const float *g_rgb, float *const *d_params, float *d_latents,
+                                 float *const *grad_tables, float *g_pts, float *g_dirs,
+                                 void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * (8) PropMLP density network for training (ZI/models.py:887-889,996-997 with disable_rgb = True):

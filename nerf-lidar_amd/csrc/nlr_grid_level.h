@@ -76,6 +76,61 @@ __device__ __forceinline__ void nlr_level_accum(const GridParams &gp, uint32_t l
     else nlr_level_accum_m<T, C, 2>(gp, level, g, werf, acc);
 }
 
+// d (sum_c gf[c] tri_c) / d x01[0..2] and the sum itself at one level, from the 8 corner values the forward gathers (the caller has
+// checked that the point lies inside the unit cube).  At a cell face the derivative is that of the cell nlr_level_cell chooses, the
+// branch the forward takes.  Used by the ray gradient of the static field (nlr_encode_rays.hip) and by the box-frame cotangent of the
+// object networks (nlr_objects_train.h).
+template <typename T, int C, int MODE>
+__device__ __forceinline__ void nlr_level_grad_m(const GridParams &gp, uint32_t level, const Gauss &g, const float *__restrict__ gf,
+                                                 float (&dpos)[3], float &tri) {
+    const T *grid = (const T *)gp.table + (size_t)gp.offset[level] * C;
+    float pos[3];
+    uint32_t pg[3];
+    nlr_level_cell(gp, level, g, pg, pos);
+    float slope[3] = {1.0f, 1.0f, 1.0f};  // d (interpolation weight) / d (position in the cell)
+    if (gp.interp == 1) {
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            slope[d] = 6.0f * pos[d] * (1.0f - pos[d]);
+            pos[d] = pos[d] * pos[d] * (3.0f - 2.0f * pos[d]);
+        }
+    }
+    uint32_t idx[8];
+    nlr_corner_idx<MODE>(gp, level, pg, idx);
+    float s[8];  // corner values contracted with the upstream gradient
+#pragma unroll
+    for (int c8 = 0; c8 < 8; ++c8) {
+        float a = 0.0f;
+#pragma unroll
+        for (int c = 0; c < C; ++c) a = fmaf(gf[c], nlr_ld<T>(grid + (size_t)idx[c8] * C + c), a);
+        s[c8] = a;
+    }
+    const float wx[2] = {1 - pos[0], pos[0]}, wy[2] = {1 - pos[1], pos[1]}, wz[2] = {1 - pos[2], pos[2]};
+    float v = 0.0f, dx = 0.0f, dy = 0.0f, dz = 0.0f;
+#pragma unroll
+    for (int c8 = 0; c8 < 8; ++c8) {
+        const int ix = c8 & 1, iy = (c8 >> 1) & 1, iz = (c8 >> 2) & 1;
+        v = fmaf((wx[ix] * wy[iy]) * wz[iz], s[c8], v);
+        dx = fmaf((ix ? wy[iy] : -wy[iy]) * wz[iz], s[c8], dx);
+        dy = fmaf((iy ? wx[ix] : -wx[ix]) * wz[iz], s[c8], dy);
+        dz = fmaf((iz ? wx[ix] : -wx[ix]) * wy[iy], s[c8], dz);
+    }
+    const float scale = gp.scale[level];  // d (position on the level) / d x01
+    dpos[0] = dx * (slope[0] * scale);
+    dpos[1] = dy * (slope[1] * scale);
+    dpos[2] = dz * (slope[2] * scale);
+    tri = v;
+}
+
+template <typename T, int C>
+__device__ __forceinline__ void nlr_level_grad(const GridParams &gp, uint32_t level, const Gauss &g, const float *__restrict__ gf,
+                                               float (&dpos)[3], float &tri) {
+    const uint32_t mode = gp.mode[level];
+    if (mode == 0) nlr_level_grad_m<T, C, 0>(gp, level, g, gf, dpos, tri);
+    else if (mode == 1) nlr_level_grad_m<T, C, 1>(gp, level, g, gf, dpos, tri);
+    else nlr_level_grad_m<T, C, 2>(gp, level, g, gf, dpos, tri);
+}
+
 
 // ---- atomics of a backward pass over ray-ordered points -----------------------------------------------------------------
 template <int CTRL>

@@ -16,6 +16,8 @@
 //                 a wave stores 256 contiguous bytes per column), and scatters the grid-feature gradient into the class's table
 //                 gradient (float atomics, like every grid scatter here).  Rows are numbered class after class: the rows of class c
 //                 start at the sum of the counts of the classes before it, so both tensors have N * S rows whatever the classes own.
+//                 Its FRAME instance (nlr_obj_train_backward_frame) also writes the cotangents of the sample's box-frame point and
+//                 direction, [N * S, 3] each, for track and pose refinement (7c / 7d take them with the owner map as a dense list).
 //             (2) nlr_objtrain_wgrad_kernel: dW = gacts_l^T . input_l per Linear as a register-tiled f32 FMA GEMM over the rows.  A
 //                 workgroup (class, Linear, slice) walks the 64-row chunks slice, slice + 96, ... of the class, stages the chunk in
 //                 LDS, and keeps a [64 outputs x 128 inputs] accumulator tile in its 256 threads' registers; the bias gradient and
@@ -81,6 +83,7 @@ struct ObjTrainB {
     const float *g_density, *g_rgb;  // [N,S], [3,N,S]
     float *acts, *gacts;             // [aw][cap], [gw][cap]
     ObjTrainPtrs grad_tables;
+    float *g_pts, *g_dirs;           // [N*S, 3] each, NULL = not wanted: read by the FRAME instance only
 };
 
 template <int OUT>
@@ -147,7 +150,17 @@ __device__ __forceinline__ void obj_class_rows(const uint32_t *counts, uint32_t 
 
 // FWD: the forward alone - results written over a.density / a.rgb / a.sem (rgb NULL: density and semantic only), nothing saved.
 // Otherwise the backward: the same forward again (same code, same bits), then the layers walked back.
-template <int C, int LMAX, bool FWD>
+// FRAME (backward only): also the cotangents of the box frame, row m = ray * S + k of t.g_pts = d loss / d po (the point
+// nlr_box_coords returns) and of t.g_dirs = d loss / d de (the direction nlr_box_dir returns); either pointer may be NULL.
+//   po enters through the grid alone, g.x = (po + 1) / 2: g_po = 0.5 * sum over the levels of nlr_level_grad on the level's feature
+//   gradient (the cell and the smoothstep branch of the forward; zero outside the unit cube).
+//   de enters every Linear that takes the concatenated input (view layer 0, view layer skip + 1, rgb_layer when D - 1 == skip) through
+//   the columns [de | sin(2^j de) | sin(2^j de + pi/2)].  While the walk has a consumer's pre-activation gradient in hand it adds
+//   W[column] . g to that column's gradient (consumers in the order of the walk, columns ascending), and the chain through the
+//   sines needs no new transcendental: cos(x) = ds1, cos(x + pi/2) = -ds0.
+// Only rows of owned samples are written: the launcher clears both buffers on the stream first.  Everything the plain instance
+// computes is computed by the same expressions in the same order.
+template <int C, int LMAX, bool FWD, bool FRAME = false>
 __global__ void __launch_bounds__(64 * NLR_OBJ_WAVES) nlr_objtrain_kernel(const ObjNet *__restrict__ nets, ObjApply a, ObjTrainB t) {
     const ObjNet &net = nets[blockIdx.y];
     const uint32_t *list = a.lists + (size_t)blockIdx.y * a.cap;
@@ -347,6 +360,26 @@ __global__ void __launch_bounds__(64 * NLR_OBJ_WAVES) nlr_objtrain_kernel(const 
                     sa[kk * 64 + lane] += (w[0] * gc[0] + w[1] * gc[1]) + w[2] * gc[2];
                 }
         }
+        // FRAME: gradient of the direction encoding's columns, [de | ds0 | ds1]
+        float ge_de[3] = {0.0f, 0.0f, 0.0f}, ge_s0[3 * NLR_OBJ_MAX_DEG], ge_s1[3 * NLR_OBJ_MAX_DEG];
+#pragma unroll
+        for (int j = 0; j < 3 * NLR_OBJ_MAX_DEG; ++j) ge_s0[j] = ge_s1[j] = 0.0f;
+        const bool want_dirs = FRAME && t.g_dirs != nullptr;
+        if (want_dirs && net.D - 1 == net.skip) {
+            const float *we = wr + (net.W + net.BW) * 4;
+            auto dot3 = [&](uint32_t q) {
+                const f32x4 w = *reinterpret_cast<const f32x4 *>(we + q * 4);
+                return (w[0] * gc[0] + w[1] * gc[1]) + w[2] * gc[2];
+            };
+#pragma unroll
+            for (int c = 0; c < 3; ++c) ge_de[c] += dot3(c);
+#pragma unroll
+            for (int j = 0; j < 3 * NLR_OBJ_MAX_DEG; ++j)
+                if ((uint32_t)j < 3 * net.deg) ge_s0[j] += dot3(3 + j);
+#pragma unroll
+            for (int j = 0; j < 3 * NLR_OBJ_MAX_DEG; ++j)
+                if ((uint32_t)j < 3 * net.deg) ge_s1[j] += dot3(3 + 3 * net.deg + j);
+        }
         for (uint32_t ii = net.D; ii > 0; --ii) {
             const uint32_t i = ii - 1;
             if (valid) {
@@ -362,6 +395,17 @@ __global__ void __launch_bounds__(64 * NLR_OBJ_WAVES) nlr_objtrain_kernel(const 
             }
             if (i == 0 || i - 1 == net.skip)
                 for (uint32_t kk = 0; kk < net.BW; ++kk) sa[kk * 64 + lane] += obj_dot_row<32>(wv + (row + kk) * 32, gv);
+            if (want_dirs && (i == 0 || i - 1 == net.skip)) {
+                const float *we = wv + (row + net.BW) * 32;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) ge_de[c] += obj_dot_row<32>(we + c * 32, gv);
+#pragma unroll
+                for (int j = 0; j < 3 * NLR_OBJ_MAX_DEG; ++j)
+                    if ((uint32_t)j < 3 * net.deg) ge_s0[j] += obj_dot_row<32>(we + (3 + j) * 32, gv);
+#pragma unroll
+                for (int j = 0; j < 3 * NLR_OBJ_MAX_DEG; ++j)
+                    if ((uint32_t)j < 3 * net.deg) ge_s1[j] += obj_dot_row<32>(we + (3 + 3 * net.deg + j) * 32, gv);
+            }
             if (i > 0) {
                 const uint32_t mk = obj_pick_mask(mv, i - 1);
 #pragma unroll
@@ -402,6 +446,32 @@ __global__ void __launch_bounds__(64 * NLR_OBJ_WAVES) nlr_objtrain_kernel(const 
 #pragma unroll
             for (int l = 0; l < LMAX; ++l)
                 if ((uint32_t)l < net.gp.L) obj_level_scatter<C>(net.gp, l, g, gfe + l * C, gt);
+        }
+        if (want_dirs && valid) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                float s = ge_de[c];
+#pragma unroll
+                for (int j = 0; j < NLR_OBJ_MAX_DEG; ++j)
+                    if ((uint32_t)j < net.deg)
+                        s += (float)(1 << j) * (ds1[3 * j + c] * ge_s0[3 * j + c] - ds0[3 * j + c] * ge_s1[3 * j + c]);
+                t.g_dirs[(size_t)m * 3 + c] = s;
+            }
+        }
+        if (FRAME && t.g_pts && valid) {
+            float gpo[3] = {0.0f, 0.0f, 0.0f};
+            if (!nlr_outside_unit_cube(g)) {  // (an owned sample is strictly inside its box; outside the cube the encoding is constant zero)
+#pragma unroll
+                for (int l = 0; l < LMAX; ++l)
+                    if ((uint32_t)l < net.gp.L) {
+                        float dp[3], tri;
+                        nlr_level_grad<float, C>(net.gp, l, g, gfe + l * C, dp, tri);
+#pragma unroll
+                        for (int d = 0; d < 3; ++d) gpo[d] += dp[d];
+                    }
+            }
+#pragma unroll
+            for (int d = 0; d < 3; ++d) t.g_pts[(size_t)m * 3 + d] = 0.5f * gpo[d];
         }
     }
 }
@@ -714,11 +784,15 @@ static int obj_train_bind(NlrObjTrainPlan *p, const float *const *tables, const 
     return NLR_OK;
 }
 
+// the backward with tb.g_pts or tb.g_dirs set takes the FRAME instance, everything else the plain ones
 static int obj_train_launch(const NlrObjTrainPlan *p, bool fwd, uint32_t N, uint32_t S, const ObjApply &a, const ObjTrainB &tb, hipStream_t st) {
     const NlrObjects *o = p->objs;
     const uint32_t C = o->cls[0].gp.C;
+    const bool frame = !fwd && (tb.g_pts || tb.g_dirs);
 #define OBJT_LAUNCH(C_, LM)                                                                                                                      \
     if (fwd) hipLaunchKernelGGL((nlr_objtrain_kernel<C_, LM, true>), obj_net_grid(o, N, S), dim3(64 * NLR_OBJ_WAVES), 0, st, o->nets_dev, a, tb); \
+    else if (frame)                                                                                                                              \
+        hipLaunchKernelGGL((nlr_objtrain_kernel<C_, LM, false, true>), obj_net_grid(o, N, S), dim3(64 * NLR_OBJ_WAVES), 0, st, o->nets_dev, a, tb); \
     else hipLaunchKernelGGL((nlr_objtrain_kernel<C_, LM, false>), obj_net_grid(o, N, S), dim3(64 * NLR_OBJ_WAVES), 0, st, o->nets_dev, a, tb)
     if (C == 2) { OBJT_LAUNCH(2, 8); }
     else if (C == 4) { OBJT_LAUNCH(4, 4); }
@@ -746,22 +820,23 @@ extern "C" int nlr_obj_train_forward(NlrObjTrainPlan *p, const float *const *tab
     return obj_train_launch(p, true, N, S, obj_apply_args(w, rays, tdist, box_params, N, S, n_obj, density, rgb, semantic, K), tb, st);
 }
 
-extern "C" int nlr_obj_train_backward(NlrObjTrainPlan *p, const float *const *tables, const float *latents, const NlrRays *rays,
-                                      const float *tdist, const float *box_params, uint32_t N, uint32_t S, uint32_t n_obj,
-                                      const float *g_density, const float *g_rgb, float *const *d_params, float *d_latents,
-                                      float *const *grad_tables, void *workspace, size_t workspace_bytes, void *stream) {
-    int run = 0, rc = obj_train_check("obj_train_backward", p, tables, latents, rays, tdist, box_params, N, S, n_obj, workspace, workspace_bytes, 1, &run);
+// the backward of both entry points; g_pts / g_dirs NULL: not wanted (both NULL: the plain instance of the kernel)
+static int obj_train_backward_impl(const char *fn, NlrObjTrainPlan *p, const float *const *tables, const float *latents, const NlrRays *rays,
+                                   const float *tdist, const float *box_params, uint32_t N, uint32_t S, uint32_t n_obj, const float *g_density,
+                                   const float *g_rgb, float *const *d_params, float *d_latents, float *const *grad_tables, float *g_pts,
+                                   float *g_dirs, void *workspace, size_t workspace_bytes, void *stream) {
+    int run = 0, rc = obj_train_check(fn, p, tables, latents, rays, tdist, box_params, N, S, n_obj, workspace, workspace_bytes, 1, &run);
     if (rc || !run) return rc;
-    NLR_CHECK_ARG(g_density && g_rgb, "obj_train_backward: g_density / g_rgb is NULL");
-    NLR_CHECK_ARG(d_params && grad_tables, "obj_train_backward: d_params / grad_tables is NULL");
-    NLR_CHECK_ARG(d_latents || p->lat_size == 0, "obj_train_backward: d_latents is NULL");
+    NLR_CHECK_ARG(g_density && g_rgb, "%s: g_density / g_rgb is NULL", fn);
+    NLR_CHECK_ARG(d_params && grad_tables, "%s: d_params / grad_tables is NULL", fn);
+    NLR_CHECK_ARG(d_latents || p->lat_size == 0, "%s: d_latents is NULL", fn);
     const uint32_t nc = (uint32_t)p->cls.size();
     ObjTrainB tb;
     ObjTrainPtrs dp;
     memset(&dp, 0, sizeof(dp));
     memset(&tb, 0, sizeof(tb));
     for (uint32_t c = 0; c < nc; ++c) {
-        NLR_CHECK_ARG(d_params[c] && grad_tables[c], "obj_train_backward: d_params[%u] / grad_tables[%u] is NULL", c, c);
+        NLR_CHECK_ARG(d_params[c] && grad_tables[c], "%s: d_params[%u] / grad_tables[%u] is NULL", fn, c, c);
         dp.p[c] = d_params[c];
         tb.grad_tables.p[c] = grad_tables[c];
     }
@@ -770,6 +845,10 @@ extern "C" int nlr_obj_train_backward(NlrObjTrainPlan *p, const float *const *ta
     // counts, owner map and lists are the forward's, where it left them in this workspace
     const ObjWorkspace w = obj_train_carve(p, workspace, N, S, 1);
     tb.g_density = g_density, tb.g_rgb = g_rgb, tb.acts = w.acts, tb.gacts = w.gacts;
+    tb.g_pts = g_pts, tb.g_dirs = g_dirs;
+    // the kernel writes the rows of owned samples only: every other row is the zero of this clear
+    for (float *g : {g_pts, g_dirs})
+        if (g) NLR_HIP(hipMemsetAsync(g, 0, (size_t)N * S * 3 * sizeof(float), st));
     if ((rc = obj_train_launch(p, false, N, S, obj_apply_args(w, rays, tdist, box_params, N, S, n_obj, nullptr, nullptr, nullptr, 0), tb, st)))
         return rc;
     const ObjTrainW tw = {w.lists, w.counts, w.winner, /*cap*/ N * S, /*n_tracks*/ n_obj, w.acts, w.gacts, w.slabs, p->slab_stride};
@@ -786,4 +865,21 @@ extern "C" int nlr_obj_train_backward(NlrObjTrainPlan *p, const float *const *ta
         NLR_LAUNCH_CHECK("nlr_objtrain_latents_kernel");
     }
     return NLR_OK;
+}
+
+extern "C" int nlr_obj_train_backward(NlrObjTrainPlan *p, const float *const *tables, const float *latents, const NlrRays *rays,
+                                      const float *tdist, const float *box_params, uint32_t N, uint32_t S, uint32_t n_obj,
+                                      const float *g_density, const float *g_rgb, float *const *d_params, float *d_latents,
+                                      float *const *grad_tables, void *workspace, size_t workspace_bytes, void *stream) {
+    return obj_train_backward_impl("obj_train_backward", p, tables, latents, rays, tdist, box_params, N, S, n_obj, g_density, g_rgb, d_params,
+                                   d_latents, grad_tables, nullptr, nullptr, workspace, workspace_bytes, stream);
+}
+
+extern "C" int nlr_obj_train_backward_frame(NlrObjTrainPlan *p, const float *const *tables, const float *latents, const NlrRays *rays,
+                                            const float *tdist, const float *box_params, uint32_t N, uint32_t S, uint32_t n_obj,
+                                            const float *g_density, const float *g_rgb, float *const *d_params, float *d_latents,
+                                            float *const *grad_tables, float *g_pts, float *g_dirs, void *workspace, size_t workspace_bytes,
+                                            void *stream) {
+    return obj_train_backward_impl("obj_train_backward_frame", p, tables, latents, rays, tdist, box_params, N, S, n_obj, g_density, g_rgb,
+                                   d_params, d_latents, grad_tables, g_pts, g_dirs, workspace, workspace_bytes, stream);
 }

@@ -736,7 +736,7 @@ def obj_frame_backward_rays(box, viewdirs, td, ri, si, tr, g_pts, g_dirs, want=(
     samples (int32 lists ri, si, tr sorted by (ray, sample); box [N, n_obj, 8] from `track_box_params`) contracted with their
     cotangents g_pts, g_dirs [K, 3].  An output that `want` leaves out is None and is neither computed nor written."""
     n, S, K = td.shape[0], td.shape[1] - 1, ri.shape[0]
-    g_pts, g_dirs = g_pts.contiguous().float(), g_dirs.contiguous().float()
+    g_pts, g_dirs = (None if g is None else g.contiguous().float() for g in (g_pts, g_dirs))   # (None: the outputs that read it are not wanted)
     out = [torch.empty(n, 3, dtype=torch.float32, device=td.device) if w else None for w in want]
     _lib.call("nlr_obj_frame_backward_rays", box, viewdirs, td, n, S, box.shape[1], ri, si, tr, K, g_pts, g_dirs, *out)
     return tuple(out)
@@ -857,19 +857,36 @@ def objects_forward(plan: _ObjTrainPlan, tables, latents, rays_desc, td, box, de
     return winner
 
 
+def _dense_sample_index(n: int, S: int, dev):
+    """(ray_idx, sample_idx) int32 [n*S] of the dense list of header section 7e: m -> (m // S, m % S).  Made on the device, nothing is
+    read back; two small kernels per backward, not worth keeping between steps."""
+    m = torch.arange(n * S, dtype=torch.int32, device=dev)
+    return torch.div(m, S, rounding_mode="floor").contiguous(), (m % S).contiguous()
+
+
 class _ObjectsFused(torch.autograd.Function):
     """The object branch of the last level as one operator (header section 7e): (density [N,S], rgb [N,S,3], semantic [N,S,K] of the
     static field, latent table [n_tracks, latent_size], the classes' hash tables, the classes' flat parameter buffers) -> (merged
     density, rgb, semantic, owner mask).  forward = `nlr_obj_train_forward`; backward = `nlr_obj_train_backward` for tables, flat
     buffers and latent codes, and the upstream gradient with the owned samples zeroed for the static tensors (the merge overwrote
-    them).  The box frame carries no gradient here.
+    them).
+    Behind the flat buffers the call may carry the five tensors the box frame depends on - tracks [n_obj, T, 9], timestamps [N], origins,
+    directions, viewdirs [N, 3] - any of which may be plain data.  When one of them needs a gradient the backward takes
+    `nlr_obj_train_backward_frame`, which also writes the cotangents of the box-frame points and directions of every sample [N*S, 3],
+    and hands them with the owner map to `obj_frame_backward` (tracks) / `obj_frame_backward_rays` (rays) as the dense list of the
+    header: K = N*S entries, an unowned one with track -1.  Nothing is read back: K is a Python int and the owner map is the forward's.
+    Without them, or when none needs a gradient, the box frame carries no gradient and the backward is `nlr_obj_train_backward`.
     The backward runs on the plan's weight images as the LAST `pack` left them (`TrainableModel.forward` packs once per forward): run a
     forward's backward before the same model's parameters change and its next forward packs again, as `training_step` does."""
 
     @staticmethod
-    def forward(ctx, plan, rays_desc, keep, td, box, density, rgbs, sem, latents, *tables_flats):
+    def forward(ctx, plan, rays_desc, keep, td, box, density, rgbs, sem, latents, *tables_flats_frame):
         nc = plan.n_classes
-        tabs = [t.detach() for t in tables_flats[:nc]]
+        if len(tables_flats_frame) not in (2 * nc, 2 * nc + 5):
+            raise ValueError(f"_ObjectsFused: {nc} tables and {nc} flat buffers, then nothing or (tracks, timestamps, origins, directions, "
+                             f"viewdirs); got {len(tables_flats_frame)} tensors")
+        tabs = [t.detach() for t in tables_flats_frame[:nc]]
+        frame = [t.detach().float().contiguous() for t in tables_flats_frame[2 * nc:]]
         n, S = td.shape[0], td.shape[1] - 1
         cf = torch.contiguous_format
         dens = density.detach().float().clone(memory_format=cf)
@@ -880,15 +897,18 @@ class _ObjectsFused(torch.autograd.Function):
         ws = torch.empty(need, dtype=torch.uint8, device=td.device)  # holds the lists until the backward: not shared between calls
         winner = objects_forward(plan, tabs, lat, rays_desc, td, box, dens, rgb_t, sem_t, workspace=ws)
         mask = winner >= 0
-        ctx.save_for_backward(td, box, lat, ws, mask, *tabs)
+        ctx.save_for_backward(td, box, lat, ws, mask, winner, *tabs, *frame)
         ctx.misc = (plan, rays_desc, keep)
         ctx.mark_non_differentiable(mask)
         return dens, rgb_t.permute(1, 2, 0), None if sem_t is None else sem_t.permute(1, 2, 0), mask
 
     @staticmethod
     def backward(ctx, g_dens, g_rgb, g_sem, _g_mask):
-        td, box, lat, ws, mask, *tabs = ctx.saved_tensors
+        td, box, lat, ws, mask, winner, *rest = ctx.saved_tensors
         plan, rays_desc, _keep = ctx.misc
+        nc = plan.n_classes
+        tabs, frame = rest[:nc], rest[nc:]
+        need = ctx.needs_input_grad[9 + 2 * nc:] if frame else ()   # (tracks, timestamps, origins, directions, viewdirs)
         n, S = td.shape[0], td.shape[1] - 1
         dev = td.device
         gd = torch.zeros(n, S, device=dev) if g_dens is None else g_dens.float().contiguous()
@@ -896,12 +916,31 @@ class _ObjectsFused(torch.autograd.Function):
         d_flats = [torch.empty(k, device=dev) for k in plan.n_params]
         d_lat = torch.empty_like(lat)
         g_tabs = [torch.zeros_like(t) for t in tabs]
-        _lib.call("nlr_obj_train_backward", plan.handle, _ptr_array(tabs), lat, rays_desc, td, box, n, S, box.shape[1], gd, gr,
-                  _ptr_array(d_flats), d_lat, _ptr_array(g_tabs), ws, ws.numel())
+        g_frame = ()
+        if not any(need):
+            _lib.call("nlr_obj_train_backward", plan.handle, _ptr_array(tabs), lat, rays_desc, td, box, n, S, box.shape[1], gd, gr,
+                      _ptr_array(d_flats), d_lat, _ptr_array(g_tabs), ws, ws.numel())
+            g_frame = (None,) * len(frame)
+        else:
+            tracks, ts, origins, dirs, viewdirs = frame
+            want_p, want_d = need[0] or need[2] or need[3], need[0] or need[4]
+            g_pts = torch.empty(n * S, 3, device=dev) if want_p else None
+            g_dirs = torch.empty(n * S, 3, device=dev) if want_d else None
+            _lib.call("nlr_obj_train_backward_frame", plan.handle, _ptr_array(tabs), lat, rays_desc, td, box, n, S, box.shape[1], gd, gr,
+                      _ptr_array(d_flats), d_lat, _ptr_array(g_tabs), g_pts, g_dirs, ws, ws.numel())
+            ri, si = _dense_sample_index(n, S, dev)
+            tr = winner.reshape(-1)
+            g_tracks = obj_frame_backward(tracks, ts, origins, dirs, viewdirs, td, ri, si, tr, g_pts, g_dirs) if need[0] else None
+            g_rays = (None, None, None)
+            if any(need[2:5]):
+                # an output that is not wanted is not computed, so the cotangent it alone would read may be missing
+                g_rays = obj_frame_backward_rays(box, viewdirs, td, ri, si, tr, g_pts, g_dirs, want=tuple(need[2:5]))
+            g_frame = (g_tracks, None) + tuple(g_rays)
 
         def static(g, m):
             return None if g is None else torch.where(m, torch.zeros_like(g), g)
-        return (None,) * 5 + (static(g_dens, mask), static(g_rgb, mask[..., None]), static(g_sem, mask[..., None]), d_lat, *g_tabs, *d_flats)
+        return (None,) * 5 + (static(g_dens, mask), static(g_rgb, mask[..., None]), static(g_sem, mask[..., None]), d_lat, *g_tabs, *d_flats,
+                              *g_frame)
 
 
 class TrainableModel(torch.nn.Module):
@@ -919,7 +958,7 @@ class TrainableModel(torch.nn.Module):
     forward / backward (`fused_mlp=True`), compositing and its gradient from `nlr_composite_level` / `nlr_composite_backward`."""
 
     def __init__(self, mc, fused_mlp: bool = False, fused_wgrad: bool = False, tracks=None, class_names=None, obj_log2_hashmap: int = 21,
-                 fused_objects: bool = False):
+                 fused_objects: bool = False, fused_object_frame: bool = False):
         """fused_objects (with `instance_obj`): every level's object merge runs through the operator of header section 7e
         (`nlr_obj_train_forward` / `_backward`: owner map, per-class lists and the object networks on the device, weight / latent / table
         gradients from fixed-order reductions) instead of the torch chain of `_object_merge`; a step then reads nothing back to the host.
@@ -927,10 +966,19 @@ class TrainableModel(torch.nn.Module):
         reference's merge and `_object_merge` do: a PropMLP returns a black rgb (models.py:1119-1122) which they overwrite with the
         detached object rgb inside the boxes, so with `fused_objects=True` a proposal level's rendered rgb stays black there and a
         nonzero `data_coarse_mult` gives another coarse data loss than the reference's (the shipped value is 0: no difference).
-        Not wired on this path, refused with NotImplementedError: tracks that require a gradient (track refinement) and ray tensors that require one (pose refinement)."""
+        Tracks that require a gradient (track refinement) and ray tensors that require one (pose refinement) are refused on this path
+        with NotImplementedError, unless `fused_object_frame=True`.
+        fused_object_frame (needs `fused_objects=True`, else ValueError): the last level's fused operator also forms the cotangents of
+        the box-frame points and directions (`nlr_obj_train_backward_frame`) and hands them to `nlr_obj_frame_backward` /
+        `nlr_obj_frame_backward_rays` as a dense list over all N * S samples, so track and pose refinement run through the fused object
+        path as well, still without a host read.  Proposal levels stay the density-only form without gradient (models.py:447-449).
+        Values of a forward are the same bits with or without it, and whether or not anything requires a gradient."""
         super().__init__()
         self.mc = mc
         self.fused_objects = bool(fused_objects)
+        self.fused_object_frame = bool(fused_object_frame)
+        if self.fused_object_frame and not self.fused_objects:
+            raise ValueError("fused_object_frame=True is an option of the fused object operator: pass fused_objects=True as well")
         self._obj_plan = None
         for i in range(mc.num_levels - 1):
             self.add_module(f"prop_mlp_{i}", TrainablePropLevel(mc.prop_cfg(i), fused=fused_mlp))
@@ -1040,9 +1088,11 @@ class TrainableModel(torch.nn.Module):
         rays_desc, keep = _lib.rays({k: batch[k].detach() for k in ("origins", "directions", "viewdirs")}, n, optional=_lib.RAY_KEYS)
         return plan, flats, tables, latents, rays_desc, keep
 
-    def _object_merge_fused(self, o: Dict[str, torch.Tensor], rgbs: torch.Tensor, tdist: torch.Tensor, box: torch.Tensor, last: bool, state):
+    def _object_merge_fused(self, o: Dict[str, torch.Tensor], rgbs: torch.Tensor, tdist: torch.Tensor, box: torch.Tensor, last: bool, state,
+                            frame=()):
         """`_object_merge` through `nlr_obj_train_forward`: nothing is read back.  Proposal levels: the density-only form under no
-        gradient (models.py:447-449), the static density keeps its gradient outside the boxes.  Last level: `_ObjectsFused`."""
+        gradient (models.py:447-449), the static density keeps its gradient outside the boxes.  Last level: `_ObjectsFused`, with
+        frame = (tracks, timestamps, origins, directions, viewdirs) when the box frame is to carry a gradient (`fused_object_frame`)."""
         plan, flats, tables, latents, rays_desc, keep = state
         td = tdist.detach().contiguous()
         density = o["density"]
@@ -1055,7 +1105,7 @@ class TrainableModel(torch.nn.Module):
         sem = o.get("semantic")
         use_sem = sem is not None and all(getattr(self, f"obj_mlp_{cid}").cfg.use_semantic for cid in self._class_list)
         dens, rgbs, sem_m, mask = _ObjectsFused.apply(plan, rays_desc, keep, td, box, density, rgbs, sem if use_sem else None, latents, *tables,
-                                                      *flats)
+                                                      *flats, *frame)
         return dens, rgbs, sem_m if use_sem else sem, mask
 
     def forward(self, batch: Dict[str, torch.Tensor], train_frac: float = 1.0, rand: Optional[torch.Generator] = None, randomized: bool = False,
@@ -1089,9 +1139,10 @@ class TrainableModel(torch.nn.Module):
                                       "of the dynamic-object branch leads back to origins / directions / viewdirs only on request, "
                                       "pass object_ray_grads=True")
         fused_obj = self.instance_obj and self.fused_objects
-        if fused_obj and ray_grads:
+        if fused_obj and ray_grads and not self.fused_object_frame:
             raise NotImplementedError("fused_objects=True with ray tensors that require a gradient (pose refinement, object_ray_grads=True): "
-                                      "the fused object operator has no box-frame gradient, use fused_objects=False")
+                                      "the fused object operator has no box-frame gradient, use fused_objects=False or pass "
+                                      "fused_object_frame=True")
         if self.instance_obj:
             if "timestamp" not in batch:
                 raise RuntimeError("batch['timestamp'] is missing (ZI/models.py:315)")
@@ -1101,11 +1152,14 @@ class TrainableModel(torch.nn.Module):
             # track refinement (train.py:244-268): a track that requires a gradient gets one from the last level's object samples
             # pose refinement (train.py:199-243) on request: ray tensors that require one get theirs through the same samples
             refine = (tracks, ts) if (tracks.requires_grad and torch.is_grad_enabled()) or ray_grads else None
-            if fused_obj and refine is not None:
+            if fused_obj and refine is not None and not self.fused_object_frame:
                 raise NotImplementedError("fused_objects=True with tracks that require a gradient (track refinement): the fused object "
-                                          "operator has no box-frame gradient, use fused_objects=False")
+                                          "operator has no box-frame gradient, use fused_objects=False or pass fused_object_frame=True")
             if fused_obj:
                 fused_state = self._fused_objects_begin(batch, n, dev)
+                fused_frame = ()
+                if refine is not None:  # the tensors the box frame is made of, as `_object_merge` reads them
+                    fused_frame = (tracks, ts) + tuple(batch[k].reshape(n, 3).float() for k in ("origins", "directions", "viewdirs"))
         for li, ((S, dilation, anneal), level) in enumerate(zip(mc.level_schedule(train_frac), self.levels())):
             last = li == n_levels - 1
             sdist, tdist = torch.empty(n, S + 1, device=dev), torch.empty(n, S + 1, device=dev)
@@ -1118,7 +1172,7 @@ class TrainableModel(torch.nn.Module):
             obj_mask = None
             if box is not None:
                 if fused_obj:
-                    dens_m, rgbs, sem_m, obj_mask = self._object_merge_fused(o, rgbs, tdist, box, last, fused_state)
+                    dens_m, rgbs, sem_m, obj_mask = self._object_merge_fused(o, rgbs, tdist, box, last, fused_state, fused_frame if last else ())
                 else:
                     dens_m, rgbs, sem_m, obj_mask = self._object_merge(o, rgbs, batch, tdist, box, last, refine if last else None)
                 o = dict(o, density=dens_m)
@@ -1338,7 +1392,9 @@ def training_step(model: TrainableModel, optimizer: torch.optim.Optimizer, batch
     gradient clipping incl. the unconditional nan_to_num_ (train_utils.clip_gradients), step.  Returns the loss terms as floats, or
     with `as_tensors` as detached device scalars: reading them is the only host synchronisation of a step (without object tracks, or
     with them on a `TrainableModel(fused_objects=True)`; the torch object merge reads its owner lists back on every level), so a
-    loop that logs every n-th step keeps the next step's launches ahead of the GPU in between.
+    loop that logs every n-th step keeps the next step's launches ahead of the GPU in between.  Inside the refinement windows the
+    same holds on a `TrainableModel(fused_objects=True, fused_object_frame=True)`: the box-frame cotangents of the fused object
+    operator reach the TrackNet and the refined rays as a dense list over all samples, without a count or an index list on the host.
     color_rays: None, or the number n of leading rays with colour supervision (`TrainableModel.forward`): the caller promises
     `batch['mask_rgb']` = 0 on the rays [n, N), as train.py:316-320 sets it for the LiDAR rays at the end of a batch
     (`losses.nusc_masks(lidar_supervision=True)` and `scene.supervise(colourless=..)` build such masks).  check_color_rays (off by default: it reads the mask back, one host
