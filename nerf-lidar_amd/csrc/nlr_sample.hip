@@ -10,7 +10,8 @@
 //   ZI/coord.py:103-162   power_transformation ray warp (s_to_t)
 // The reference materialises [N, 3S'+1, S'] and [N, S'+1, S] boolean masks in HBM; here a ray's
 // <= 3*512+1 fenceposts live in LDS, the sort is a 3-way merge by binary-search ranking, the dilation maximum a
-// range-max table query, the CDF a wavefront scan and each sample does a binary search.
+// range-max table query, the CDF a wavefront scan and each sample does a binary search (how the searches are laid out over the
+// lanes: the comment above the kernel).
 // Precondition (as in the reference's step functions): prev_sdist is non-decreasing along each ray.
 #include "nlr_kernels.h"
 
@@ -39,7 +40,31 @@ __device__ __forceinline__ float nlr_warp_inv(float y, float lam, float lam1, fl
     return ((powf(((y * lam) / lam1 + 1.0f) + NLR_EPS, inv_exp) - 1.0f) * lam1) / 2.0f;
 }
 
-// LDS carve (floats): t[n+1] | p[n] | U[3n+2] | W[3n] | Mx[(LV-1) n]  (dilate)  then  cw[m+1] | cen[S]
+// Two prefix counts over sorted LDS lists at once: c = #{i < len : l[i] < v}, or with eq #{i < len : l[i] <= v}, given
+// lo <= c <= hi on entry; the result is left in lo.  The two searches are independent, so every step has two ds_reads in flight
+// where two searches in a row would wait for each read in turn.  A finished search (lo == hi) goes on reading l[lo] and keeps its
+// bounds; lo can be len there, so the float behind each list must be LDS of the same ray (it is: see the carve).
+__device__ __forceinline__ void nlr_count2(const float *l1, uint32_t &lo1, uint32_t hi1, bool eq1, const float *l2, uint32_t &lo2,
+                                           uint32_t hi2, bool eq2, float v) {
+    while (lo1 < hi1 || lo2 < hi2) {
+        const uint32_t m1 = (lo1 + hi1) >> 1, m2 = (lo2 + hi2) >> 1;
+        const float x1 = l1[m1], x2 = l2[m2];
+        const bool b1 = (x1 < v) | ((x1 == v) & eq1), b2 = (x2 < v) | ((x2 == v) & eq2);
+        lo1 = (b1 & (lo1 < hi1)) ? m1 + 1 : lo1;
+        hi1 = b1 ? hi1 : m1;  // m1 == hi1 in a finished search
+        lo2 = (b2 & (lo2 < hi2)) ? m2 + 1 : lo2;
+        hi2 = b2 ? hi2 : m2;
+    }
+}
+
+// How the integer ranks are found (the merge position of a fencepost, the covering range of a dilated bin, the CDF interval of a
+// sample): the queries of each search are non-decreasing, and so are their ranks.  A lane takes a contiguous run of queries,
+// binary-searches the first over the whole list and every further one only over [rank of the previous query, rank of the next lane's
+// first query] (one __shfl_down), which is as wide as the fenceposts that lie between two neighbouring runs: a step or two where the
+// ray's mass is spread, never more than the full search where it is concentrated.  The ranks, and so every value written, are those
+// of a full search per query.
+// LDS carve (floats): t[n+1] | p[n] | U[3n+2] | W[3n] | Mx[(LV-1) n]  (dilate)  then  cw[m+1] | cen[S] | 8 spare; while dilating
+// t0[n] | t1[n] lie where cw | cen follow (2n + 1 <= m + 1 + S + 8)
 __global__ void __launch_bounds__(64) nlr_resample_kernel(ResampleParams P) {
     extern __shared__ __align__(16) float lds[];
     const uint32_t ray = blockIdx.x;
@@ -51,6 +76,7 @@ __global__ void __launch_bounds__(64) nlr_resample_kernel(ResampleParams P) {
     float *ww;  // its bin weights, m entries
     uint32_t m;
     float *scratch;
+    bool uniform = false;  // level 0 with a finite logit: the step function is the single bin [0,1], its CDF is the identity
 
     if (n == 0) {
         tt = lds;
@@ -62,6 +88,8 @@ __global__ void __launch_bounds__(64) nlr_resample_kernel(ResampleParams P) {
         }
         m = 1;
         scratch = lds + 4;
+        const float lg = P.anneal * logf(1.0f + P.pad);
+        uniform = (lg - lg) == 0.0f;
     } else {
         float *t = lds;           // n+1
         float *p = t + (n + 1);   // n
@@ -80,41 +108,60 @@ __global__ void __launch_bounds__(64) nlr_resample_kernel(ResampleParams P) {
             float *W = U + (3 * n + 2);  // 3n
             float *Mx = W + 3 * n;       // (LV-1) * n: sparse table of range maxima over p (level 0 is p itself)
             const float d = P.dilation;
-            // weight_to_pdf (stepfun.py:64-67)
-            for (uint32_t j = lane; j < n; j += 64) p[j] = p[j] / fmaxf(t[j + 1] - t[j], NLR_EPS);
-            // sort(cat([t, t0, t1])) (stepfun.py:77-79) with t0_j = t_j - d, t1_j = t_{j+1} + d.  The three lists are
+            uint32_t LV = 1;
+            while ((2u << (LV - 1)) <= n) ++LV;  // levels 0 .. LV-1 of the range-maximum table, 2^(LV-1) <= n
+            // t0_j = t_j - d and t1_j = t_{j+1} + d (stepfun.py:77-78), kept as lists of their own where cw | cen go later: every
+            // search step below is then one ds_read and one compare, whichever list it walks
+            float *t0 = Mx + (size_t)(LV - 1) * n;  // n
+            float *t1 = t0 + n;                     // n
+            for (uint32_t j = lane; j < n; j += 64) {
+                const float a = t[j], b = t[j + 1];
+                p[j] = p[j] / fmaxf(b - a, NLR_EPS);  // weight_to_pdf (stepfun.py:64-67)
+                t0[j] = a - d;
+                t1[j] = b + d;
+            }
+            __syncthreads();
+            // sort(cat([t, t0, t1])) (stepfun.py:77-79).  The three lists are
             // each non-decreasing (t is a step function's fenceposts; float add/sub of a constant is monotone), so the
             // sort is a 3-way merge: an element's position is its index in its own list plus the number of elements of
-            // the other two lists that precede it (ties: t before t0 before t1), two binary searches per element
+            // the other two lists that precede it (ties: t before t0 before t1), two prefix counts per element
             // instead of a 36-pass bitonic network.  The sorted VALUES are what a full sort gives.
-            auto count = [&](uint32_t len, auto pred) {  // #{i < len : pred(i)}, pred true on a prefix
-                uint32_t lo = 0, hi = len;
-                while (lo < hi) {
-                    const uint32_t mid = (lo + hi) >> 1;
-                    if (pred(mid)) lo = mid + 1; else hi = mid;
+            //   element v of   first count                    second count
+            //   t              #{q < n   : t0[q] <  v}        #{q < n : t1[q] <  v}
+            //   t0             #{q < n+1 : t[q]  <= v}        #{q < n : t1[q] <  v}
+            //   t1             #{q < n+1 : t[q]  <= v}        #{q < n : t0[q] <= v}
+            // A lane takes `per` consecutive elements of ONE list (lanes [0, LA) the n+1 of t, the next LB the n of t0, the next LB
+            // those of t1), so that its queries and both of their counts are non-decreasing; which list is data of the lane (three
+            // pointers, a length, strict or not), not a branch.  per = ceil((3n+1)/64), one more where the three lists' ragged
+            // last runs would need more than 64 lanes (n = 85: 22 + 22 + 22).
+            {
+                uint32_t per = (3 * n + 1 + 63) / 64;
+                while ((n + per) / per + 2 * ((n + per - 1) / per) > 64) ++per;
+                const uint32_t LA = (n + per) / per, LB = (n + per - 1) / per;  // ceil((n+1)/per), ceil(n/per)
+                const uint32_t kind = (uint32_t)lane < LA ? 0u : ((uint32_t)lane < LA + LB ? 1u : 2u);
+                const float *own = kind == 0 ? t : (kind == 1 ? t0 : t1);
+                const float *l1 = kind == 0 ? t0 : t, *l2 = kind == 2 ? t0 : t1;
+                const uint32_t own_len = kind == 0 ? n + 1 : n, len1 = kind == 0 ? n : n + 1, len2 = n;
+                const bool eq1 = kind != 0, eq2 = kind == 2;
+                const uint32_t first_lane = kind == 0 ? 0u : (kind == 1 ? LA : LA + LB);
+                const uint32_t o0 = ((uint32_t)lane - first_lane) * per;
+                const uint32_t o1 = o0 + per < own_len ? o0 + per : own_len;  // the run is [o0, o1); empty on the lanes left over
+                const bool act = o0 < own_len;
+                uint32_t c1 = 0, c2 = 0;
+                float v = act ? own[o0] : 0.0f;
+                nlr_count2(l1, c1, act ? len1 : 0u, eq1, l2, c2, act ? len2 : 0u, eq2, v);
+                // the next lane's first counts bound this run's, if that lane holds a run of the same list
+                const uint32_t n1 = __shfl_down(c1, 1, 64), n2 = __shfl_down(c2, 1, 64);
+                const bool next_same = ((uint32_t)lane + 1 - first_lane) * per < own_len && lane < 63;
+                const uint32_t up1 = next_same ? n1 : len1, up2 = next_same ? n2 : len2;
+                if (act) U[o0 + c1 + c2] = fminf(fmaxf(v, 0.0f), 1.0f);  // clip to the domain [0,1] (stepfun.py:80)
+                for (uint32_t o = o0 + 1; o < o1; ++o) {
+                    v = own[o];
+                    nlr_count2(l1, c1, up1, eq1, l2, c2, up2, eq2, v);
+                    U[o + c1 + c2] = fminf(fmaxf(v, 0.0f), 1.0f);
                 }
-                return lo;
-            };
-            for (uint32_t i = lane; i <= 3 * n; i += 64) {
-                float v;
-                uint32_t r;
-                if (i <= n) {
-                    v = t[i];
-                    r = i + count(n, [&](uint32_t q) { return (t[q] - d) < v; }) + count(n, [&](uint32_t q) { return (t[q + 1] + d) < v; });
-                } else if (i <= 2 * n) {
-                    const uint32_t o = i - (n + 1);
-                    v = t[o] - d;
-                    r = o + count(n + 1, [&](uint32_t q) { return t[q] <= v; }) + count(n, [&](uint32_t q) { return (t[q + 1] + d) < v; });
-                } else {
-                    const uint32_t o = i - (2 * n + 1);
-                    v = t[o + 1] + d;
-                    r = o + count(n + 1, [&](uint32_t q) { return t[q] <= v; }) + count(n, [&](uint32_t q) { return (t[q] - d) <= v; });
-                }
-                U[r] = fminf(fmaxf(v, 0.0f), 1.0f);  // clip to the domain [0,1] (stepfun.py:80)
             }
             // range-maximum table: Mx[l-1][j] = max p[j .. j + 2^l - 1] (indices clamped to n-1)
-            uint32_t LV = 1;
-            while ((2u << (LV - 1)) <= n) ++LV;  // levels 0 .. LV-1, 2^(LV-1) <= n
             __syncthreads();
             for (uint32_t l = 1; l < LV; ++l) {
                 const float *src = l == 1 ? p : Mx + (size_t)(l - 2) * n;
@@ -126,25 +173,41 @@ __global__ void __launch_bounds__(64) nlr_resample_kernel(ResampleParams P) {
                 }
                 __syncthreads();
             }
-            // max over covering intervals (stepfun.py:81-87): interval j covers t_k iff (t_j - d) <= t_k < (t_{j+1} + d);
-            // both bounds are monotone in j, so the covering set is the index range [j0, j1) found by two binary searches
+            // max over covering intervals (stepfun.py:81-87): interval j covers t_k iff t0_j <= t_k < t1_j;
+            // both bounds are monotone in j, so the covering set is the index range [j0, j1) found by two prefix counts
             // and its maximum comes from the table (the reference builds an [3n+1, n] mask).  Then pdf_to_weight
-            // (stepfun.py:70-72).
-            float part = 0.0f;
-            for (uint32_t k = lane; k < 3 * n; k += 64) {
-                const float tk = U[k];
-                const uint32_t j1 = count(n, [&](uint32_t q) { return (t[q] - d) <= tk; });
-                const uint32_t j0 = count(n, [&](uint32_t q) { return (t[q + 1] + d) <= tk; });
-                float best = 0.0f;
-                if (j0 < j1) {
-                    const uint32_t len = j1 - j0, l = 31u - (uint32_t)__clz((int)len);
-                    const float *row = l == 0 ? p : Mx + (size_t)(l - 1) * n;
-                    best = fmaxf(best, fmaxf(row[j0], row[j1 - (1u << l)]));
+            // (stepfun.py:70-72).  U is sorted, so j0 and j1 are non-decreasing in k: lane l takes the bins [l*per, (l+1)*per).
+            {
+                const uint32_t per = (3 * n + 63) / 64;
+                const uint32_t k0 = (uint32_t)lane * per, k1 = k0 + per < 3 * n ? k0 + per : 3 * n;
+                float tk = 0.0f;
+                const auto emit = [&](uint32_t k, uint32_t j0, uint32_t j1) {
+                    float best = 0.0f;
+                    if (j0 < j1) {
+                        const uint32_t len = j1 - j0, l = 31u - (uint32_t)__clz((int)len);
+                        const float *row = l == 0 ? p : Mx + (size_t)(l - 1) * n;
+                        best = fmaxf(best, fmaxf(row[j0], row[j1 - (1u << l)]));
+                    }
+                    W[k] = best * (U[k + 1] - tk);
+                };
+                const bool act = k0 < 3 * n;
+                uint32_t j1 = 0, j0 = 0;
+                if (act) tk = U[k0];
+                nlr_count2(t0, j1, act ? n : 0u, true, t1, j0, act ? n : 0u, true, tk);
+                const uint32_t nj1 = __shfl_down(j1, 1, 64), nj0 = __shfl_down(j0, 1, 64);
+                const bool next_act = ((uint32_t)lane + 1) * per < 3 * n && lane < 63;
+                const uint32_t up1 = next_act ? nj1 : n, up0 = next_act ? nj0 : n;
+                if (act) emit(k0, j0, j1);
+                for (uint32_t k = k0 + 1; k < k1; ++k) {
+                    tk = U[k];
+                    nlr_count2(t0, j1, up1, true, t1, j0, up0, true, tk);
+                    emit(k, j0, j1);
                 }
-                const float wk = best * (U[k + 1] - tk);
-                W[k] = wk;
-                part += wk;
             }
+            __syncthreads();
+            // the sum keeps its order: lane l adds the bins l, l + 64, ... in turn, then the wave sum
+            float part = 0.0f;
+            for (uint32_t k = lane; k < 3 * n; k += 64) part += W[k];
             const float tot = fmaxf(nlr_wave_sum(part), NLR_EPS);  // renormalize (stepfun.py:103-104)
             __syncthreads();
             for (uint32_t k = lane; k < 3 * n; k += 64) W[k] = W[k] / tot;
@@ -158,79 +221,104 @@ __global__ void __launch_bounds__(64) nlr_resample_kernel(ResampleParams P) {
     }
     __syncthreads();
 
-    // logits -> softmax (models.py:352-355, stepfun.py:157).  e = exp(logit - max) held in cw[1..m].
     float *cw = scratch;          // m+1
     float *cen = cw + (m + 1);    // S
-    float mx = -INFINITY;
-    for (uint32_t k = lane; k < m; k += 64) {
-        const float lg = (tt[k + 1] > tt[k]) ? P.anneal * logf(ww[k] + P.pad) : -INFINITY;
-        cw[k + 1] = lg;
-        mx = fmaxf(mx, lg);
-    }
-    mx = nlr_wave_max(mx);
-    float se = 0.0f;
-    for (uint32_t k = lane; k < m; k += 64) {
-        const float e = expf(cw[k + 1] - mx);
-        cw[k + 1] = e;
-        se += e;
-    }
-    se = nlr_wave_sum(se);
-    __syncthreads();
-    // integrate_weights (stepfun.py:123-127): cw_0 = 0, cw_j = min(cumsum(w)[j-1], 1) for j<m, cw_m = 1.
-    // Lane l owns the contiguous chunk [l*per, (l+1)*per) of the m weights.
-    {
-        const uint32_t per = (m + 63) / 64;
-        const uint32_t b0 = lane * per;
-        float run = 0.0f;
-        for (uint32_t i = 0; i < per; ++i) {
-            const uint32_t k = b0 + i;
-            if (k < m) run += cw[k + 1] / se;
+    if (uniform) {  // softmax of the one finite logit is 1: the CDF is {0, 1} whatever anneal and padding are
+        if (lane == 0) {
+            cw[0] = 0.0f;
+            cw[1] = 1.0f;
         }
-        const float incl = nlr_wave_incl_scan_add(run, lane);
-        float base = incl - run;
-        // a float tree-scan is not guaranteed monotone to the last ulp; sorted_interp needs xp sorted
-        float prevmax = nlr_wave_incl_scan_max(incl, lane);
-        prevmax = __shfl_up(prevmax, 1, 64);
-        if (lane == 0) prevmax = 0.0f;
+    } else {
+        // logits -> softmax (models.py:352-355, stepfun.py:157).  e = exp(logit - max) held in cw[1..m].
+        float mx = -INFINITY;
+        for (uint32_t k = lane; k < m; k += 64) {
+            const float lg = (tt[k + 1] > tt[k]) ? P.anneal * logf(ww[k] + P.pad) : -INFINITY;
+            cw[k + 1] = lg;
+            mx = fmaxf(mx, lg);
+        }
+        mx = nlr_wave_max(mx);
+        float se = 0.0f;
+        for (uint32_t k = lane; k < m; k += 64) {
+            const float e = expf(cw[k + 1] - mx);
+            cw[k + 1] = e;
+            se += e;
+        }
+        se = nlr_wave_sum(se);
         __syncthreads();
-        float acc = base;
-        float hi = prevmax;
-        for (uint32_t i = 0; i < per; ++i) {
-            const uint32_t k = b0 + i;
-            if (k < m) {
-                acc += cw[k + 1] / se;
-                hi = fmaxf(hi, acc);
-                cw[k + 1] = (k + 1 == m) ? 1.0f : fminf(hi, 1.0f);
+        // integrate_weights (stepfun.py:123-127): cw_0 = 0, cw_j = min(cumsum(w)[j-1], 1) for j<m, cw_m = 1.
+        // Lane l owns the contiguous chunk [l*per, (l+1)*per) of the m weights.
+        {
+            const uint32_t per = (m + 63) / 64;
+            const uint32_t b0 = lane * per;
+            float run = 0.0f;
+            for (uint32_t i = 0; i < per; ++i) {
+                const uint32_t k = b0 + i;
+                if (k < m) run += cw[k + 1] / se;
             }
+            const float incl = nlr_wave_incl_scan_add(run, lane);
+            float base = incl - run;
+            // a float tree-scan is not guaranteed monotone to the last ulp; sorted_interp needs xp sorted
+            float prevmax = nlr_wave_incl_scan_max(incl, lane);
+            prevmax = __shfl_up(prevmax, 1, 64);
+            if (lane == 0) prevmax = 0.0f;
+            __syncthreads();
+            float acc = base;
+            float hi = prevmax;
+            for (uint32_t i = 0; i < per; ++i) {
+                const uint32_t k = b0 + i;
+                if (k < m) {
+                    acc += cw[k + 1] / se;
+                    hi = fmaxf(hi, acc);
+                    cw[k + 1] = (k + 1 == m) ? 1.0f : fminf(hi, 1.0f);
+                }
+            }
+            if (lane == 0) cw[0] = 0.0f;
         }
-        if (lane == 0) cw[0] = 0.0f;
     }
     __syncthreads();
 
     // invert the CDF at u (stepfun.py:160, math.py:89-108)
+    // u is increasing in k, so is the count: lane l takes the samples [l*per, (l+1)*per)
     const float jit = P.jitter ? P.jitter[ray] * P.max_jitter : 0.0f;
-    for (uint32_t k = lane; k < P.S; k += 64) {
-        const float u = P.jitter ? P.u[k] + jit : P.u[k];
-        // hi = #{j in [0,m] : cw_j <= u}
-        uint32_t lo = 0, hi = m + 1;
-        while (lo < hi) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (cw[mid] <= u) lo = mid + 1; else hi = mid;
+    {
+        const uint32_t per = (P.S + 63) / 64;
+        const uint32_t k0 = (uint32_t)lane * per, k1 = k0 + per < P.S ? k0 + per : P.S;
+        const auto emit = [&](uint32_t k, float u, uint32_t lo) {  // lo = #{j in [0,m] : cw_j <= u}
+            const uint32_t i0 = lo > 0 ? (lo - 1 > m ? m : lo - 1) : 0;
+            const uint32_t i1 = lo > m ? m : lo;
+            const float x0 = cw[i0], x1 = cw[i1];
+            float off = (u - x0) / (x1 - x0);
+            if (off != off) off = 0.0f;
+            off = fminf(fmaxf(off, 0.0f), 1.0f);
+            cen[k] = tt[i0] + off * (tt[i1] - tt[i0]);
+        };
+        const auto search = [&](float u, uint32_t lo, uint32_t hi) {
+            while (lo < hi) {
+                const uint32_t mid = (lo + hi) >> 1;
+                if (cw[mid] <= u) lo = mid + 1; else hi = mid;
+            }
+            return lo;
+        };
+        const bool act = k0 < P.S;
+        float u = 0.0f;
+        if (act) u = P.jitter ? P.u[k0] + jit : P.u[k0];
+        uint32_t lo = search(u, 0, act ? m + 1 : 0u);
+        const uint32_t nlo = __shfl_down(lo, 1, 64);
+        const uint32_t up = (((uint32_t)lane + 1) * per < P.S && lane < 63) ? nlo : m + 1;
+        if (act) emit(k0, u, lo);
+        for (uint32_t k = k0 + 1; k < k1; ++k) {
+            u = P.jitter ? P.u[k] + jit : P.u[k];
+            lo = search(u, lo, up);
+            emit(k, u, lo);
         }
-        const uint32_t i0 = lo > 0 ? (lo - 1 > m ? m : lo - 1) : 0;
-        const uint32_t i1 = lo > m ? m : lo;
-        const float x0 = cw[i0], x1 = cw[i1];
-        float off = (u - x0) / (x1 - x0);
-        if (off != off) off = 0.0f;
-        off = fminf(fmaxf(off, 0.0f), 1.0f);
-        cen[k] = tt[i0] + off * (tt[i1] - tt[i0]);
     }
     __syncthreads();
 
     // fenceposts: midpoints + reflected, clamped ends (stepfun.py:284-293), then s_to_t
-    const float nearv = P.near[ray], farv = P.far[ray];
-    const float s_near = nlr_warp_fwd(nearv, P.lam, P.lam1, P.c_fwd);
-    const float s_far = nlr_warp_fwd(farv, P.lam, P.lam1, P.c_fwd);
+    // both ends of the ray go through the warp in one pass (odd lanes far, even lanes near): a powf costs the wave the same
+    // whether one lane needs it or all
+    const float s_end = nlr_warp_fwd((lane & 1) ? P.far[ray] : P.near[ray], P.lam, P.lam1, P.c_fwd);
+    const float s_near = __shfl(s_end, 0, 64), s_far = __shfl(s_end, 1, 64);
     float *so = P.sdist + (size_t)ray * (P.S + 1);
     float *to = P.tdist ? P.tdist + (size_t)ray * (P.S + 1) : nullptr;
     for (uint32_t k = lane; k <= P.S; k += 64) {
