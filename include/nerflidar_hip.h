@@ -715,6 +715,49 @@ int nlr_patch_smooth_backward(const float *depth, const float *semantic, const f
                               uint32_t K, const float *stats, const float *g_terms, float *d_depth, float *d_semantic, void *workspace,
                               size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * (11) Ray-history losses: the two loss terms that read the ray history, values and gradients with respect to the weights, as one
+ *     operator.  sdist [N, S+1] / weights [N, S] are the final level's normalised distances and weights, prop_sdist[i] [N, S_i+1] /
+ *     prop_weights[i] [N, S_i] those of proposal level i (host arrays of device pointers, S_i in prop_S_host, the blur half-widths
+ *     `Config.pulse_width` in pulse_width_host).  Every sdist is data (the reference detaches it, ZI/models.py:358-369).
+ *       terms[0]      distortion loss (train_utils.py:175-181, stepfun.py:297-308 lossfun_distortion): the mean over the rays of
+ *                     2 sum_k w_k D_k + sum_k w_k^2 (t_{k+1} - t_k) / 3, D_k = sum_{j<k} w_j (u_k - u_j), u the bin midpoints (a
+ *                     running sum of non-negative terms instead of the reference's [S, S] array).
+ *       terms[1 + i]  anti-aliased interlevel loss of level i (train_utils.py:134-172): the final histogram c, pdf = min(w / dc, 10)
+ *                     blurred with a box of half-width r = pulse_width[i] (stepfun.py:425-433 blur_stepfun: 2S + 2 knots c - r, c + r),
+ *                     its cdf read at the proposal edges (math.py:111-131 sorted_interp_quad, with the reference's running max /
+ *                     reverse running min of the blurred pdf at the bracket's ends), w_target = the cdf's differences, and the mean
+ *                     over the KEPT samples of max(w_target - wp, 0)^2 / (wp + 1e-5).  Kept: prop_obj_mask[i] [N, S_i] bytes == 0
+ *                     (train_utils.py:153-154; the array or an entry NULL: every sample).  c, w are constants of this term.
+ *     float32 values and IEEE division in the order of losses.py; the running sums of the scans are carried in float64 and rounded
+ *     to float32 per element, as torch's CPU cumsum does.  NaNs travel as on torch: a zero-width final bin with w > 0 has pdf 10, one
+ *     with w = 0 makes w_target of its ray NaN (the term NaN, d_prop_weights NaN on that ray's kept samples only).  No kept sample in
+ *     a level: the term is 0 / 0 = NaN (the reference's mean of nothing) and d_prop_weights[i] all 0.
+ *     forward:  terms [1 + n_prop]; stats [2 (1 + n_prop)] = the sums, then the counts (N, kept samples) - what the backward reads;
+ *               w_target[i] [N, S_i] written (the only thing kept between the passes).
+ *     backward: d_weights [N, S] = g_terms[0] d terms[0] / d weights (the scans recomputed), d_prop_weights[i] [N, S_i] =
+ *               g_terms[1 + i] d terms[1 + i] / d prop_weights[i] (elementwise on w_target; 0 on masked samples), both OVERWRITTEN.
+ *               g_terms [1 + n_prop] dev: the upstream scalars stay on the device.
+ *     N >= 1, 1 <= S, S_i <= NLR_RAY_LOSSES_MAX_S, 0 <= n_prop <= NLR_RAY_LOSSES_MAX_PROP (n_prop = 0: the distortion term alone, the
+ *     arrays may be NULL), every pulse width finite and > 0, workspace_bytes >= nlr_ray_losses_workspace_bytes(N, n_prop) (per-workgroup
+ *     partial sums and counts of the forward; the backward takes the same buffer and leaves it alone); anything else, or a NULL
+ *     required pointer, is NLR_ERR_INVALID with nothing launched.  No atomics: fixed-order reductions, bitwise repeatable values and
+ *     gradients; terms[0] and d_weights do not depend on the proposal levels.
+ * ------------------------------------------------------------------------------------------ */
+#define NLR_RAY_LOSSES_MAX_PROP 4
+#define NLR_RAY_LOSSES_MAX_S 512
+size_t nlr_ray_losses_workspace_bytes(uint32_t N, uint32_t n_prop);
+int nlr_ray_losses_forward(const float *sdist, const float *weights, uint32_t N, uint32_t S, const float *const *prop_sdist,
+                           const float *const *prop_weights, const uint8_t *const *prop_obj_mask /* array or entries may be NULL */,
+                           const uint32_t *prop_S_host, const float *pulse_width_host, uint32_t n_prop, float *terms /* [1+n_prop] */,
+                           float *stats /* [2*(1+n_prop)] */, float *const *w_target /* [N,S_i] each, written */, void *workspace,
+                           size_t workspace_bytes, void *stream);
+int nlr_ray_losses_backward(const float *sdist, const float *weights, uint32_t N, uint32_t S, const float *const *prop_sdist,
+                            const float *const *prop_weights, const uint8_t *const *prop_obj_mask, const uint32_t *prop_S_host,
+                            const float *pulse_width_host, uint32_t n_prop, const float *stats, const float *g_terms,
+                            const float *const *w_target, float *d_weights /* [N,S], overwritten */,
+                            float *const *d_prop_weights /* [N,S_i], overwritten */, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

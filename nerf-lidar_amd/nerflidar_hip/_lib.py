@@ -121,7 +121,7 @@ _SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "uint32_t": C.c_uint32, "float
 _RETURNS = {"void": None, "const char *": C.c_char_p, **_SCALARS}
 # what a tensor behind a `T *` must hold (torch, numpy); void takes any
 _POINTEE_DTYPE = {"float": (torch.float32, np.float32), "double": (torch.float64, np.float64), "int32_t": (torch.int32, np.int32),
-                  "uint32_t": (torch.int32, np.int32), "void": (None, None)}
+                  "uint32_t": (torch.int32, np.int32), "uint8_t": (torch.uint8, np.uint8), "void": (None, None)}
 
 
 class Param(NamedTuple):
@@ -144,7 +144,7 @@ class Signature(NamedTuple):
 
 def signatures(text: Optional[str] = None) -> Dict[str, Signature]:
     """name -> Signature of every `nlr_*` prototype, of the header next to the package or of a header `text`.  Anything outside the
-    ABI's vocabulary - int, int32_t, uint32_t, float, double, size_t, void, const char *, pointers to those, to the bound structs, to
+    ABI's vocabulary - int, int32_t, uint32_t, uint8_t (behind a pointer), float, double, size_t, void, const char *, pointers to those, to the bound structs, to
     the opaque handles, and `T **` - is an error that quotes the prototype: no type is ever guessed."""
     if text is None:
         return _SIGNATURES

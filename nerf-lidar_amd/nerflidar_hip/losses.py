@@ -4,7 +4,9 @@ Small elementwise / scan work on [rays, samples] arrays, written with torch ops 
 the stages that have HIP backward kernels (compositing, fused MLP, hash grid).  Each function states the reference lines it
 follows; `tests/golden/fn_losses.npz` holds the reference's own values and gradients for the first four.  The one exception is
 `patch_smoothness` (the two terms of the patch rays, `fn_smooth.npz`): on CUDA tensors it is a HIP operator with its own backward
-(`training.patch_smooth`), because written with torch ops it is ~80 launches per step.
+(`training.patch_smooth`), because written with torch ops it is ~80 launches per step.  The two terms that read the ray history
+(anti-aliased interlevel, distortion) exist both ways: the torch functions below, and one HIP operator with its own backward
+(`ray_history_terms`, `training.ray_losses`, `total_loss(ray_loss_backend=)`).
 
 Formulations differ from the reference where that is cheaper and numerically at least as good:
   * interval look-ups use one `torch.searchsorted` per query instead of an [.., n, m] comparison cube
@@ -73,10 +75,11 @@ def _quad_cdf_at(q: torch.Tensor, knots: torch.Tensor, pdf: torch.Tensor, cdf: t
     return c0 + (q - x0) * (p0 + p1 * frac + p0 * (1 - frac)) / 2
 
 
-def anti_interlevel_loss(ray_history: Sequence[Dict[str, torch.Tensor]], mult: float, pulse_width: Sequence[float]) -> torch.Tensor:
+def anti_interlevel_terms(ray_history: Sequence[Dict[str, torch.Tensor]], pulse_width: Sequence[float]) -> List[torch.Tensor]:
+    """The unscaled term of every proposal level, in level order."""
     c, w = ray_history[-1]["sdist"].detach(), ray_history[-1]["weights"].detach()
     pdf = (w / (c[..., 1:] - c[..., :-1])).clamp_max(10)
-    total = 0.0
+    terms = []
     for i, h in enumerate(ray_history[:-1]):
         knots, val = blur_stepfun(c, pdf, pulse_width[i])
         area = 0.5 * (val[..., 1:] + val[..., :-1]) * torch.diff(knots, dim=-1)
@@ -88,9 +91,16 @@ def anti_interlevel_loss(ray_history: Sequence[Dict[str, torch.Tensor]], mult: f
             # selected with `torch.where` and divided by the count, like the masked terms below `depth_loss`: no host read.  A level
             # whose samples are all inside boxes gives 0 / 0, the reference's mean of nothing
             keep = ~h["obj_mask"]
-            total = total + torch.where(keep, term, torch.zeros_like(term)).sum() / keep.sum().to(term.dtype)
+            terms.append(torch.where(keep, term, torch.zeros_like(term)).sum() / keep.sum().to(term.dtype))
         else:
-            total = total + term.mean()
+            terms.append(term.mean())
+    return terms
+
+
+def anti_interlevel_loss(ray_history: Sequence[Dict[str, torch.Tensor]], mult: float, pulse_width: Sequence[float]) -> torch.Tensor:
+    total = 0.0
+    for term in anti_interlevel_terms(ray_history, pulse_width):
+        total = total + term
     return mult * total
 
 
@@ -107,6 +117,29 @@ def distortion(t: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
 
 def distortion_loss(ray_history: Sequence[Dict[str, torch.Tensor]], mult: float) -> torch.Tensor:
     return mult * distortion(ray_history[-1]["sdist"], ray_history[-1]["weights"]).mean()
+
+
+# ---- the two of them together (header section 11) ------------------------------------------------------------------------------------------
+def ray_history_terms(ray_history: Sequence[Dict[str, torch.Tensor]], pulse_width: Sequence[float], backend: str = "auto"):
+    """(anti_terms, distortion), unscaled: the anti-aliased interlevel term of every proposal level (a list of scalars or one tensor
+    [n_prop]; empty for a history of one level) and the distortion term of the final level, i.e. `anti_interlevel_loss` = mult *
+    sum(anti_terms) and `distortion_loss` = mult * distortion.
+    backend: "torch" = the functions above, "hip" = `training.ray_losses` (nlr_ray_losses_forward / _backward: float32 CUDA tensors, no
+    fallback, no gradient to any sdist, at most 4 proposal levels of at most 512 samples), "auto" = "hip" for CUDA tensors and "torch"
+    for CPU tensors."""
+    if backend not in ("auto", "hip", "torch"):
+        raise ValueError(f"ray_history_terms: backend {backend!r} (auto, hip, torch)")
+    last = ray_history[-1]["weights"]
+    if backend == "hip" or (backend == "auto" and last.is_cuda):
+        for h in ray_history:
+            for k in ("sdist", "weights"):
+                if not h[k].is_cuda or h[k].dtype != torch.float32:
+                    raise ValueError(f"ray_history_terms: backend 'hip' takes float32 CUDA tensors, {k} is {h[k].dtype} on {h[k].device} "
+                                     "(no fallback)")
+        from .training import ray_losses
+        terms = ray_losses(ray_history, pulse_width)
+        return terms[1:], terms[0]
+    return anti_interlevel_terms(ray_history, pulse_width), distortion(ray_history[-1]["sdist"], ray_history[-1]["weights"]).mean()
 
 
 # ---- data terms ----------------------------------------------------------------------------------------------------------------
@@ -261,14 +294,17 @@ def total_loss(renderings: List[Dict[str, torch.Tensor]], ray_history: List[Dict
                data_kind: str = "charb", charb_padding: float = 1e-3, data_coarse_mult: float = 0.0, data_mult: float = 1.0,
                interlevel_mult: float = 0.0, anti_interlevel_mult: float = 0.01, pulse_width: Sequence[float] = (0.03, 0.003),
                distortion_mult: float = 0.005, depth_lam: float = 0.1, sem_lam: float = 0.01, patch_size: int = 0,
-               patch_rays: Optional[Sequence[int]] = None, smo_lam: float = 0.01, s_lam: float = 0.01) -> Dict[str, torch.Tensor]:
+               patch_rays: Optional[Sequence[int]] = None, smo_lam: float = 0.01, s_lam: float = 0.01,
+               ray_loss_backend: str = "torch") -> Dict[str, torch.Tensor]:
     """The dictionary `losses` of train.py:326-446 for the terms this path covers (defaults = configs.py); the caller adds the
     hash-decay term (`training.hash_decay_loss`) and sums.  Batch keys (all optional except rgb): rgb [N,3], mask_rgb [N],
     depth [N] + depth_mask [N], semantic [N] + sem_mask [N], intensity [N] + lidar_mask [N].
     patch_size > 1 with patch_rays = (row0, P): the rays [row0, row0 + P * patch_size^2) are P pixel patches, flattened patch-major
     (`Config.patch_size`, datasets.py:357-399; the masks take them out of every other data term), and get the smoothness terms of
     train.py:365-388: `d_smo` on the rendered depth and, when the rendering has `semantic`, `s_smo` on the class probabilities
-    (`patch_smoothness`; valid pixels from batch['patch_valid'], see `nusc_masks`; without that key every pixel is valid)."""
+    (`patch_smoothness`; valid pixels from batch['patch_valid'], see `nusc_masks`; without that key every pixel is valid).
+    ray_loss_backend: "torch" = `interlevel` and `distortion` from the torch functions above; "hip" / "auto" = the anti-aliased
+    interlevel term and the distortion term from the HIP operator (`ray_history_terms` with that backend; same keys)."""
     out = {"data": data_loss(renderings, batch["rgb"], batch.get("mask_rgb"), data_kind, charb_padding, data_coarse_mult, data_mult)}
     last = renderings[-1]
     if patch_size > 1 and patch_rays is not None:
@@ -288,6 +324,21 @@ def total_loss(renderings: List[Dict[str, torch.Tensor]], ray_history: List[Dict
         out["sem"] = semantic_loss(last["semantic"], batch["semantic"], batch.get("sem_mask", batch["semantic"] != 255), sem_lam)
     if "intensity" in batch and "intensity" in last:
         out["int"] = intensity_loss(last["intensity"], batch["intensity"], batch.get("lidar_mask", torch.ones_like(batch["intensity"], dtype=torch.bool)))
+    if ray_loss_backend not in ("auto", "hip", "torch"):
+        raise ValueError(f"total_loss: ray_loss_backend {ray_loss_backend!r} (auto, hip, torch)")
+    if ray_loss_backend != "torch":
+        # one operator for the anti-aliased interlevel term and the distortion term (`ray_history_terms`); the mip-NeRF 360 term stays
+        # on torch, and without the anti-aliased term the operator gets the final level alone
+        anti = len(ray_history) > 1 and anti_interlevel_mult > 0
+        if len(ray_history) > 1 and interlevel_mult > 0 and not anti:
+            out["interlevel"] = interlevel_loss(ray_history, interlevel_mult)
+        if anti or distortion_mult > 0:
+            anti_terms, dist = ray_history_terms(ray_history if anti else ray_history[-1:], pulse_width, backend=ray_loss_backend)
+            if anti:
+                out["interlevel"] = anti_interlevel_mult * (anti_terms.sum() if isinstance(anti_terms, torch.Tensor) else sum(anti_terms))
+            if distortion_mult > 0:
+                out["distortion"] = distortion_mult * dist
+        return out
     if len(ray_history) > 1:
         if interlevel_mult > 0:
             out["interlevel"] = interlevel_loss(ray_history, interlevel_mult)

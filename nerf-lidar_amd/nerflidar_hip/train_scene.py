@@ -54,6 +54,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--fused", type=int, default=1, help="1: fused bf16 MFMA NerfMLP forward / backward; 0: torch Linear modules in fp32")
     ap.add_argument("--fused-wgrad", action="store_true",
                     help="weight gradients of the fused NerfMLP from nlr_mlp_train_wgrad (one MFMA kernel) instead of library GEMMs; requires --fused 1")
+    ap.add_argument("--fused-ray-losses", action="store_true",
+                    help="the anti-aliased interlevel and distortion losses from the HIP operator nlr_ray_losses_forward / _backward "
+                         "(total_loss(ray_loss_backend='hip')) instead of torch ops")
     ap.add_argument("--lr-init", type=float, default=0.01)
     ap.add_argument("--lr-final", type=float, default=0.001)
     ap.add_argument("--lr-delay-steps", type=int, default=None, help="default: a fifth of the run (5 000 of 25 000 in configs.py:87)")
@@ -153,6 +156,8 @@ def main(argv=None) -> int:
             g["lr"] = lr_fn(step)                                          # train.py:187-190
         batch, patch_rays = make_batch(a.rays, a.seed, step, dev, a.scale_factor, colourless, n_patches, a.patch_size)
         patch_kw = dict(patch_size=a.patch_size, patch_rays=patch_rays) if patch_rays else {}
+        if a.fused_ray_losses:
+            patch_kw["ray_loss_backend"] = "hip"
         if posenet is not None:
             batch, _, _ = nscene.perturb_frames(batch, a.pose_frames, a.seed)
         train_frac = float(np.clip((step - 1) / max(a.steps - 1, 1), 0, 1))  # train.py:184
@@ -174,7 +179,7 @@ def main(argv=None) -> int:
     model, step, ignored = nckpt.model_from_checkpoint(a.out, base=mc)
     ev = evaluate(model, a.scale_factor, seed=a.seed)
     summary = dict(workload=a.workload, log2_hashmap=a.log2_hashmap, steps=a.steps, rays_per_step=a.rays, fused=bool(a.fused), fused_wgrad=a.fused_wgrad,
-                   colourless_fraction=a.colourless_fraction, train_seconds=round(train_s, 1), train_rays_per_s=round(a.steps * a.rays / train_s), checkpoint=path,
+                   fused_ray_losses=a.fused_ray_losses, colourless_fraction=a.colourless_fraction, train_seconds=round(train_s, 1), train_rays_per_s=round(a.steps * a.rays / train_s), checkpoint=path,
                    checkpoint_bytes=os.path.getsize(path), restored_step=step, held_out_sweep=ev, final_terms=log[-1])
     if n_patches:  # the final step's smoothness terms (also in final_terms): zero would mean the patches saw no valid pair
         summary.update(patch_size=a.patch_size, patches_per_step=n_patches, d_smo=log[-1].get("d_smo"), s_smo=log[-1].get("s_smo"))

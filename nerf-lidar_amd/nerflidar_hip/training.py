@@ -2,6 +2,7 @@
 
   * differentiable compositing (`nlr_composite_level` / `nlr_composite_backward`) and the hash-decay regulariser;
   * the edge-aware smoothness terms of the patch rays (`nlr_patch_smooth_forward` / `_backward`, `patch_smooth`);
+  * the two losses that read the ray history, anti-aliased interlevel and distortion (`nlr_ray_losses_forward` / `_backward`, `ray_losses`);
   * `gridencoder.GridEncoder` (HIP forward + backward + total-variation gradient, Z/gridencoder/grid.py:24-198);
   * the NerfMLP either as torch Linear modules or through the fused MFMA forward / backward (`_FusedMLP`);
   * `TrainableNerfLevel`, `TrainablePropLevel`, `TrainableModel`: the reference's `Model.forward` with autograd (proposal
@@ -171,6 +172,86 @@ def patch_smooth(depth, semantic, rgb, valid, patch_size: int):
     None (T_s is then a constant 0).  The refusals are the library's (2 <= patch_size <= 64, at most 32 classes)."""
     terms = _PatchSmooth.apply(depth, semantic, rgb, valid, int(patch_size))
     return terms[0], terms[1]
+
+
+class _RayLosses(torch.autograd.Function):
+    """nlr_ray_losses_forward / _backward (header section 11): the distortion loss of the final level and the anti-aliased interlevel
+    loss of every proposal level as one operator.  Arguments: pulse_width, final sdist, final weights, then (sdist, weights, obj_mask or
+    None) per proposal level.  Returns terms [1 + n_prop] = (distortion, anti term of level 0, ..); gradients to the weights, every
+    sdist and mask is data.  Between the passes it keeps w_target [N, S_i] per level and the counts; the upstream gradient stays on the
+    device."""
+    _workspaces: Dict = {}  # device -> uint8 tensor, grown on demand (only the forward writes it, and reads it back in the same call)
+
+    @staticmethod
+    def _workspace(dev, N, n_prop):
+        need = int(_lib.lib().nlr_ray_losses_workspace_bytes(N, n_prop))
+        ws = _RayLosses._workspaces.get(dev)
+        if ws is None or ws.numel() < need:
+            ws = _RayLosses._workspaces[dev] = torch.empty(need, dtype=torch.uint8, device=dev)
+        return ws
+
+    @staticmethod
+    def _args(sd, w, psd, pw, pm, pulse_width):
+        N, S, n_prop = w.shape[0], w.shape[1], len(pw)
+        mask_ptrs = (C.c_void_p * n_prop)(*[None if m is None else m.data_ptr() for m in pm]) if n_prop else None
+        prop_S = np.asarray([p.shape[1] for p in pw], np.int32) if n_prop else None
+        widths = np.asarray([float(r) for r in pulse_width[:n_prop]], np.float32) if n_prop else None
+        return (sd, w, N, S, _ptr_array(psd) if n_prop else None, _ptr_array(pw) if n_prop else None, mask_ptrs, prop_S, widths, n_prop)
+
+    @staticmethod
+    def forward(ctx, pulse_width, sdist, weights, *levels):
+        n_prop = len(levels) // 3
+        if len(pulse_width) < n_prop:
+            raise ValueError(f"ray_losses: {n_prop} proposal levels, {len(pulse_width)} pulse widths")
+        rows = lambda t: t.reshape(-1, t.shape[-1]).contiguous().float()
+        sd, w = rows(sdist), rows(weights)
+        psd = [rows(t) for t in levels[0::3]]
+        pw = [rows(t) for t in levels[1::3]]
+        pm = [None if m is None else m.reshape(-1, m.shape[-1]).to(torch.bool).contiguous().view(torch.uint8) for m in levels[2::3]]  # bool: its bytes
+        N, dev = w.shape[0], w.device
+        for name, a, b in [("final", sd, w)] + [(f"proposal {i}", a, b) for i, (a, b) in enumerate(zip(psd, pw))]:
+            if a.shape != (N, b.shape[1] + 1) or b.shape[0] != N:
+                raise ValueError(f"ray_losses: {name} level has sdist {tuple(a.shape)} and weights {tuple(b.shape)} for {N} rays")
+        for i, (m, b) in enumerate(zip(pm, pw)):
+            if m is not None and m.shape != b.shape:
+                raise ValueError(f"ray_losses: obj_mask of proposal {i} is {tuple(m.shape)}, its weights {tuple(b.shape)}")
+        terms, stats = torch.empty(1 + n_prop, device=dev), torch.empty(2 * (1 + n_prop), device=dev)
+        w_target = [torch.empty_like(p) for p in pw]
+        ws = _RayLosses._workspace(dev, N, n_prop)
+        args = _RayLosses._args(sd, w, psd, pw, pm, pulse_width)
+        _lib.call("nlr_ray_losses_forward", *args, terms, stats, _ptr_array(w_target) if n_prop else None, ws, ws.numel())
+        ctx.save_for_backward(sd, w, stats, *psd, *pw, *w_target, *[m for m in pm if m is not None])
+        ctx.meta = (n_prop, tuple(pulse_width), [m is not None for m in pm], weights.shape, [t.shape for t in levels[1::3]])
+        return terms
+
+    @staticmethod
+    def backward(ctx, g_terms):
+        n_prop, pulse_width, has_mask, w_shape, pw_shapes = ctx.meta
+        sd, w, stats, *rest = ctx.saved_tensors
+        psd, pw, w_target, masks = rest[:n_prop], rest[n_prop:2 * n_prop], rest[2 * n_prop:3 * n_prop], list(rest[3 * n_prop:])
+        pm = [masks.pop(0) if h else None for h in has_mask]
+        d_w, d_pw = torch.empty_like(w), [torch.empty_like(p) for p in pw]
+        ws = _RayLosses._workspace(w.device, w.shape[0], n_prop)
+        args = _RayLosses._args(sd, w, psd, pw, pm, pulse_width)
+        _lib.call("nlr_ray_losses_backward", *args, stats, g_terms.contiguous().float(), _ptr_array(w_target) if n_prop else None, d_w,
+                  _ptr_array(d_pw) if n_prop else None, ws, ws.numel())
+        out = [None, None, d_w.reshape(w_shape)]
+        for d, shape in zip(d_pw, pw_shapes):
+            out += [None, d.reshape(shape), None]
+        return tuple(out)
+
+
+def ray_losses(ray_history, pulse_width):
+    """terms [1 + n_prop] on the device = (distortion loss, anti-aliased interlevel loss of every proposal level), unscaled, of a ray
+    history (dicts with `sdist`, `weights` and optionally `obj_mask`; the last one is the final level) on the HIP operator: float32
+    CUDA tensors.  Every `sdist` is data: one that requires a gradient is refused.  The refusals of the sizes are the library's
+    (at most 4 proposal levels, 512 samples per level, pulse widths finite and > 0)."""
+    if any(h["sdist"].requires_grad for h in ray_history):
+        raise ValueError("ray_losses: an sdist of the ray history requires a gradient; the operator treats sdist as data (detach it)")
+    levels = []
+    for h in ray_history[:-1]:
+        levels += [h["sdist"], h["weights"], h.get("obj_mask")]
+    return _RayLosses.apply(tuple(pulse_width), ray_history[-1]["sdist"], ray_history[-1]["weights"], *levels)
 
 
 # ---- a trainable NerfMLP level: fused cast/contract + HIP grid op (fwd/bwd) + torch Linear stack + HIP compositing (fwd/bwd) ----------
