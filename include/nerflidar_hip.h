@@ -758,6 +758,33 @@ int nlr_ray_losses_backward(const float *sdist, const float *weights, uint32_t N
                             const float *const *w_target, float *d_weights /* [N,S], overwritten */,
                             float *const *d_prop_weights /* [N,S_i], overwritten */, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * (12) Density normals: the surface normals the reference derives from its density field (ZI/models.py:1070-1094 with
+ *     disable_density_normals = False and analytic_gradient = True; composited by ZI/models.py:525-529 through the `extras` of
+ *     render.py:255-261).  The operator runs after a render, on a level's tdist [N, S+1] (and weights [N, S]); all f32.
+ *       f           [N*S, F], F = L*C: the features of nlr_encode_features_forward (that kernel is called)
+ *       g_f         = W0^T (1[W0 f + b0 > 0] . w2_row0): the cotangent of raw_density = density_layer(f)[..., 0] (models.py:996-997).
+ *                   w0 [hidden, F], b0 [hidden] = density_layer.0, w2_row0 [hidden] = row 0 of density_layer.2.weight (its bias
+ *                   does not enter a gradient); dev f32
+ *       raw_grad    [N, S, 3] = (1/n) sum_j gm_j, gm_j = d raw_density / d (multisample position j) exactly as in (9) backward_rays
+ *                   for the upstream g_f: the 1/n of the feature mean, the footprint term of the contraction, zero for a point
+ *                   outside the unit cube; the outer 1/n is the reference's `.mean(-2)` (models.py:1089)
+ *       normals     [N, S, 3] = -raw_grad / max(|raw_grad|, 1e-5) (ref_utils.py:23-25 l2_normalize); a zero gradient gives a zero normal
+ *       ray_normals [N, 3] = sum_s weights[ray, s] normals[ray, s] (render.py:255-261), whether or not `normals` is requested
+ *     Every output is OVERWRITTEN and may be NULL (ray_normals needs weights).  No atomics: every sum has a fixed order (j ascending per
+ *     sample; s ascending per lane, then a butterfly over the wave), bitwise repeatable and independent of the launch.
+ *     workspace: nlr_density_normals_workspace_bytes(N, S, F) = 2 N S F 4 bytes, 16-byte aligned; after the call its first N*S*F
+ *     floats hold f, the next N*S*F hold g_f.  NULL or short: NLR_ERR_WORKSPACE.
+ *     Envelope: that of (9) backward_rays (level_dim 1, 2, 4, 8; f32 / f16 tables; every gridtype / align_corners / interp), and
+ *     F <= 64 with F % 4 == 0, hidden == 64; anything else NLR_ERR_UNSUPPORTED with a message.  N == 0: NLR_OK.  S >= 1 arbitrary.
+ * ------------------------------------------------------------------------------------------ */
+size_t nlr_density_normals_workspace_bytes(uint32_t N, uint32_t S, uint32_t F);
+int nlr_density_normals(const NlrRays *rays, const float *tdist /* [N,S+1] */, uint32_t N, uint32_t S, uint32_t sample_n, uint32_t sample_m,
+                        float std_scale, const float *rand_deg /* [N,S,n] or NULL */, const NlrGridDesc *grid, uint32_t re_weights,
+                        uint32_t hidden, const float *w0 /* [hidden,F] */, const float *b0 /* [hidden] */, const float *w2_row0 /* [hidden] */,
+                        const float *weights /* [N,S] or NULL */, float *raw_grad /* [N,S,3] or NULL */, float *normals /* [N,S,3] or NULL */,
+                        float *ray_normals /* [N,3] or NULL */, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,6 +19,9 @@ from .config import MLPConfig, ModelConfig
 from .weights import grid_layout, mlp_names, mlp_param_shapes
 
 _RAY_KEYS = _lib.RAY_KEYS
+# the reference builds every MLP's GridEncoder with its defaults (hash, align_corners=False, linear; ZI/models.py:868): one statement
+# for the render descriptor and for the encoder the normals operator is handed
+_GRID_OPTIONS = dict(gridtype=0, align_corners=0, interp=0)
 
 
 def _f32c(a) -> np.ndarray:
@@ -77,6 +80,33 @@ class Model:
         desc.mlp_precision = precision
         _lib.call("nlr_model_create", desc, self._handle, device=self.device)
         self._keep.clear()
+        # density normals (ZI/models.py:1070-1094): device f32 copies of the last level's density layers and its grid, for the operator
+        # of normals.py, which runs after the render and is f32 whatever `precision` is.  Off (the default): nothing is kept.
+        self._normals = None
+        if not mc.nerf_mlp.disable_density_normals:
+            if not mc.config.analytic_gradient:
+                raise NotImplementedError("Config.analytic_gradient = False with NerfMLP.disable_density_normals = False asks for the "
+                                          "finite-difference normals (ZI/models.py:1097-1100), which are outside the fused path")
+            self._normals = self._normals_state(list(mlp_names(mc))[-1], sd)
+
+    @property
+    def has_density_normals(self) -> bool:
+        """Was the model built with `NerfMLP.disable_density_normals = False`?  Its history and extras then carry normals."""
+        return self._normals is not None
+
+    def _normals_state(self, last, sd):
+        """What `normals.density_normals` takes besides rays, tdist and weights: the last level's encoder (duck type of
+        `training.encode_features_fused`) over the model's own table, and density_layer.0 / row 0 of density_layer.2 on the device."""
+        from types import SimpleNamespace
+        prefix, cfg = last
+        offsets, _, pls = grid_layout(cfg)
+        enc = SimpleNamespace(num_levels=cfg.grid_num_levels, output_dim=cfg.grid_num_levels * cfg.grid_level_dim,
+                              base_resolution=cfg.grid_base_resolution, per_level_scale=float(pls),
+                              _offsets_host=torch.from_numpy(np.ascontiguousarray(offsets, np.int32)), gridtype_id=_GRID_OPTIONS["gridtype"],
+                              align_corners=bool(_GRID_OPTIONS["align_corners"]), interp_id=_GRID_OPTIONS["interp"], embeddings=self.tables[prefix])
+        dev = lambda a: torch.from_numpy(_f32c(a)).to(self.device)
+        return SimpleNamespace(encoder=enc, w0=dev(sd[f"{prefix}.density_layer.0.weight"]), b0=dev(sd[f"{prefix}.density_layer.0.bias"]),
+                               w2=dev(sd[f"{prefix}.density_layer.2.weight"][0]), re_weights=bool(cfg.re_weights))
 
     # -- descriptor assembly ---------------------------------------------------------------------
     def _linear(self, sd, name) -> _lib.NlrLinear:
@@ -106,7 +136,7 @@ class Model:
         g.base_resolution = cfg.grid_base_resolution
         g.log2_per_level_scale = float(np.log2(pls))
         g.offsets = off.ctypes.data
-        g.gridtype, g.align_corners, g.interp = 0, 0, 0
+        g.gridtype, g.align_corners, g.interp = _GRID_OPTIONS["gridtype"], _GRID_OPTIONS["align_corners"], _GRID_OPTIONS["interp"]
         md.density0 = self._linear(sd, f"{prefix}.density_layer.0")
         md.density2 = self._linear(sd, f"{prefix}.density_layer.2")
         md.disable_rgb = int(cfg.disable_rgb)
@@ -241,6 +271,15 @@ class Model:
         self._render_call(rays, n, cfg, out, lidar_only)
         if want_history:  # back to the reference's [N, S, C] layout (ZI/models.py:553-557)
             last = hist[-1]
+            if self._normals is not None:  # ZI/models.py:1082-1094, :525-529: after the render, on the last level's own tdist / weights / rand_deg
+                from .normals import density_normals
+                ns = self._normals
+                got = density_normals(ns.encoder, batch, last["tdist"], ns.w0, ns.b0, ns.w2, weights=last["weights"], sample_n=sample_n,
+                                      sample_m=sample_m, std_scale=self.mc.std_scale, rand_deg=None if rand_deg is None else rand_deg[-1],
+                                      re_weights=ns.re_weights, want=("raw_grad", "normals") + (("ray_normals",) if compute_extras else ()))
+                last["normals"], last["raw_grad_density"] = got["normals"], got["raw_grad"]
+                if compute_extras:
+                    r["normals"] = got["ray_normals"]
             if "rgb" in last:
                 last["rgb"] = last["rgb"].permute(1, 2, 0)
             if "semantic" in last:
@@ -304,6 +343,9 @@ class CapturedRender:
     ONE capture must still be ordered with respect to each other (same stream, or events), like any kernel sequence over fixed buffers."""
 
     def __init__(self, model: "Model", batch: Dict[str, torch.Tensor], **kw):
+        if model.has_density_normals:
+            raise NotImplementedError("CapturedRender of a model with NerfMLP.disable_density_normals = False: the normals operator allocates "
+                                      "its outputs and workspace per call and is not part of a captured sweep")
         self.model, self.batch = model, batch
         side = torch.cuda.Stream(model.device)
         self.graph = torch.cuda.CUDAGraph()

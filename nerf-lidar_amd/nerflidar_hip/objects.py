@@ -215,6 +215,9 @@ class DynamicModel(Model):
 
     def __init__(self, mc: ModelConfig, state_dict, tracks, class_names: Sequence[str], device="cuda:0", obj_log2_hashmap: int = 21, **kw):
         import dataclasses
+        if not mc.nerf_mlp.disable_density_normals:
+            raise NotImplementedError("NerfMLP.disable_density_normals = False with the dynamic-object branch: the reference's merge gives object "
+                                      "samples no normals (ZI/models.py:401-477), so a merged ray has none to composite")
         static_mc = dataclasses.replace(mc, config=dataclasses.replace(mc.config, instance_obj=False))
         super().__init__(static_mc, state_dict, device=device, **kw)
         check_instance_obj(mc.config)

@@ -3,6 +3,7 @@
 Restates Z/render_lidar.py:106-162 around `nerflidar_hip.models.render_image`: per sweep, render the LiDAR ray batch with
 `image=False`, then `points = (origins + depth * directions) / scale_factor`, `labels = argmax(semantic)` and save
 `points_%04d.npy`, `points_semantic_%04d.npy`, `points_rgb_%04d.npy` under `<render_dir>/lidar_replay` (names at :157-162).
+`--normals` adds `points_normals_%04d.npy`, the rendered density normals of every ray (ZI/models.py:525-529, 1070-1094).
 Optionally continues into the ray-drop stage without the `.npy` round trip (rows f-2 / f-4): GPU range projection ->
 UNet feature stack -> UNet -> drop mask -> KITTI `.bin/.label`.
 
@@ -38,6 +39,8 @@ def render_sweep(model: Model, batch: Dict[str, np.ndarray], scale_factor: float
                labels=torch.argmax(r["semantic"], dim=-1))
     if "intensity" in r:
         out["intensity"] = r["intensity"].reshape(-1)
+    if "normals" in r:  # a model with NerfMLP.disable_density_normals = False
+        out["normals"] = r["normals"].reshape(-1, 3)
     return out
 
 
@@ -48,6 +51,13 @@ def save_sweep(out_dir: str, idx: int, res: Dict[str, torch.Tensor]) -> None:
     np.save(os.path.join(out_dir, "points_{:04d}.npy".format(idx)), npy(res["points"]))
     np.save(os.path.join(out_dir, "points_semantic_{:04d}.npy".format(idx)), npy(res["labels"]))
     np.save(os.path.join(out_dir, "points_rgb_{:04d}.npy".format(idx)), npy(res["rgb"]))
+    save_sweep_normals(out_dir, idx, res)
+
+
+def save_sweep_normals(out_dir: str, idx: int, res: Dict[str, torch.Tensor]) -> None:
+    """`points_normals_%04d.npy` [N, 3] float32 beside the reference's files, when the sweep carries normals."""
+    if "normals" in res:
+        np.save(os.path.join(out_dir, "points_normals_{:04d}.npy".format(idx)), res["normals"].detach().cpu().numpy().astype(np.float32))
 
 
 def to_lidar_frame(points: torch.Tensor, origin_m: torch.Tensor, lidar2world: torch.Tensor) -> torch.Tensor:
@@ -72,8 +82,10 @@ def drop_rays(res: Dict[str, torch.Tensor], points_lidar: torch.Tensor, unet, ma
 def render_sweep_device(model: Model, batch: Dict[str, torch.Tensor], scale_factor: float, lidar_only: bool = False) -> Dict[str, torch.Tensor]:
     """One sweep through ONE `nlr_render_rays` call (no chunk loop, nothing leaves the device): the LiDAR post-step outputs `points`
     (metres), `labels`, `rgb`, `depth`, `intensity` of render_lidar.py:142-161, written by the compositing kernel itself.
-    lidar_only: ONE `nlr_render_lidar` call - the same outputs without `rgb`, and the view MLP is not run."""
-    r, _ = model.render_rays(batch, compute_extras=False, scale_factor=scale_factor, lidar_only=lidar_only)
+    lidar_only: ONE `nlr_render_lidar` call - the same outputs without `rgb`, and the view MLP is not run.
+    A model with density normals enabled is rendered with its history and extras, which the normals are part of (r["normals"])."""
+    normals = model.has_density_normals
+    r, _ = model.render_rays(batch, compute_extras=normals, scale_factor=scale_factor, lidar_only=lidar_only, want_history=normals)
     return r
 
 
@@ -85,6 +97,7 @@ def save_sweep_lidar(out_dir: str, idx: int, res: Dict[str, torch.Tensor]) -> No
     np.save(os.path.join(out_dir, "points_semantic_{:04d}.npy".format(idx)), npy(res["labels"]).astype(np.int64))
     if "intensity" in res:
         np.save(os.path.join(out_dir, "points_intensity_{:04d}.npy".format(idx)), npy(res["intensity"]))
+    save_sweep_normals(out_dir, idx, res)
 
 
 def sweep_unet_input(res: Dict[str, torch.Tensor], origin_m: torch.Tensor, lidar2world: torch.Tensor, var: bool = True, width: int = 1024):
@@ -166,6 +179,8 @@ def build_parser() -> argparse.ArgumentParser:
                     "the refined tracks instead of the recorded ones; needs --tracks or --synthetic-tracks")
     ap.add_argument("--lidar-only", action="store_true", help="render without colour (one nlr_render_lidar call per sweep, no view MLP): "
                     "writes points, points_semantic and points_intensity, no points_rgb; not with --raydrop-unet")
+    ap.add_argument("--normals", action="store_true", help="render the density normals as well (NerfMLP.disable_density_normals = False): "
+                    "writes points_normals_%%04d.npy [N, 3] float32 beside the other files; not with --tracks / --synthetic-tracks")
     return ap
 
 
@@ -175,6 +190,9 @@ def parse_args(argv=None) -> argparse.Namespace:
     if a.lidar_only and a.raydrop_unet:
         ap.error("--lidar-only renders no colour, and the ray-drop UNet's feature stack (raydrop.unet_features) takes the rgb channels: "
                  "drop one of --lidar-only / --raydrop-unet")
+    if a.normals and (a.tracks or a.synthetic_tracks):
+        ap.error("--normals (NerfMLP.disable_density_normals = False) is not available with the dynamic-object branch: the reference's "
+                 "merge gives object samples no normals")
     if a.tracknet_ckpt and not (a.tracks or a.synthetic_tracks):
         ap.error("--tracknet-ckpt refines box tracks: give --tracks (with --track-classes) or --synthetic-tracks")
     return a
@@ -208,12 +226,14 @@ def main(argv=None) -> int:
     elif a.ckpt:
         from .checkpoints import model_from_checkpoint
         base = nconfig.ModelConfig()
+        base.nerf_mlp.disable_density_normals = not a.normals
         if a.num_nerf_samples:
             base.num_nerf_samples = a.num_nerf_samples
         model, step, ignored = model_from_checkpoint(a.ckpt, base=base, precision=a.precision)
         print(f"restored step {step}; {len(ignored)} keys outside the fused path ignored")
     else:
         mc = nconfig.workload(a.workload, a.log2_hashmap)
+        mc.nerf_mlp.disable_density_normals = not a.normals
         if a.num_nerf_samples:
             mc.num_nerf_samples = a.num_nerf_samples
         sd = nweights.synth_state_dict(mc, seed=a.seed, trained_like=True)

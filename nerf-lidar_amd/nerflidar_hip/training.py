@@ -1055,6 +1055,9 @@ class TrainableModel(torch.nn.Module):
         path as well, still without a host read.  Proposal levels stay the density-only form without gradient (models.py:447-449).
         Values of a forward are the same bits with or without it, and whether or not anything requires a gradient."""
         super().__init__()
+        if not mc.nerf_mlp.disable_density_normals:
+            raise NotImplementedError("NerfMLP.disable_density_normals = False in training: losses on normals need the second derivative of the "
+                                      "grid; normals are an inference output (models.Model, normals.density_normals)")
         self.mc = mc
         self.fused_objects = bool(fused_objects)
         self.fused_object_frame = bool(fused_object_frame)
